@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one block of the hot path over one batch of synthetic input: L new samples on
 each of the 64 input channels -> forward FFTs -> 64x64 crossbar multiply-accumulate over 32
@@ -382,11 +382,17 @@ def main():
     ap.add_argument("--host-io", action="store_true",
                     help="time bfhip_engine_block() with HOST raw buffers (PCIe both ways and a "
                          "sync per block included) -- informative, never the headline value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the raw output block(s) the last timed step handed "
+                         "its caller to DIR/<name>.npy as float64 samples [L][O] (inputs and IRs are seeded: "
+                         "the same arguments give the same inputs on every run)")
     ap.add_argument("--cpu-worker", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help=argparse.SUPPRESS)
     ap.add_argument("--ref-worker", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--ref-shape", default="8192,4", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.ref_worker is not None:
         Lr, rsr = (int(v) for v in args.ref_shape.split(","))
         print(json.dumps(_ref_loop_worker(Lr, rsr, args.cpu_seconds, 128)), flush=True)
@@ -629,6 +635,34 @@ def main():
             dist.barrier(device_ids=[dev_index]) if backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
+    def dump_outputs():
+        """--dump-outputs: what the last timed step handed its caller -- the raw output buffer the
+        step loop wrote (pairs: the two of the last pair) -- as float64 samples [L][O], exact for
+        every raw format a workload uses.  A rank writes outputs [fo, fo + co) only: N > 1 ranks
+        are gathered to rank 0; a rehearsal keeps its own outputs.  Called after the drain, before
+        verify() runs blocks of its own."""
+        if args.host_io:
+            bufs_ = {"out": np.frombuffer(host_out, raw_out.cpu().numpy().dtype).reshape(L, O)}
+        elif args.pairs:
+            bufs_ = {"out_pair0": raw_out.cpu().numpy(), "out_pair1": raw_out2.cpu().numpy()}
+        else:
+            bufs_ = {"out": raw_out.cpu().numpy()}
+        arrays = {k: v[:, fo:fo + co].astype(np.float64) for k, v in bufs_.items()}
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, (fo, arrays))
+            arrays = {k: np.zeros((L, O), np.float64) for k in arrays}
+            for f0, part in parts:
+                for k, v in part.items():
+                    arrays[k][:, f0:f0 + v.shape[1]] = v
+        if rank != 0:
+            return None
+        assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+        return {"dir": args.dump_outputs, "arrays": {k: list(v.shape) for k, v in arrays.items()}, "dtype": "float64"}
+
     for k in range(args.warmup):
         step(k)
     drain()
@@ -653,6 +687,7 @@ def main():
     tm = eng.timing()
     src_hash = source_hash()
     eng.enable_timing(0)
+    dumped = dump_outputs() if args.dump_outputs else None
 
     def verify():
         """End-to-end check of the very configuration that was just timed, through the same step
@@ -791,6 +826,8 @@ def main():
             out["config"]["io"] = "host buffers through bfhip_engine_rt_submit/rt_wait, two blocks in flight (PCIe-inclusive)"
         out["source_hash"] = src_hash
         out["verify"] = ver
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1:
             traffic, traffic_stale, traffic_src = None, None, None
             tp = os.path.join(ROOT, "profiles", "traffic_config%s.json" % args.workload)

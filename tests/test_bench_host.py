@@ -48,3 +48,12 @@ def test_source_hash_names_the_sources_of_the_binary():
 def test_usable_cores_is_bounded_by_the_affinity_mask():
     cores, note = bench.usable_cores()
     assert 1 <= cores <= len(os.sched_getaffinity(0)) and isinstance(note, str)
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    """--steps is the number of timed steps: zero would time nothing (and ms_per_step divides by it);
+    refused before anything touches the GPU"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

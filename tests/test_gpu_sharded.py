@@ -252,3 +252,31 @@ def test_bench_verification_notices_wrong_outputs():
     assert bad.returncode != 0 and "WRONG" in bad.stderr
     v = json.loads([ln for ln in bad.stdout.splitlines() if ln.startswith("{")][0])["verify"]
     assert not v["ok"] and v["max_abs_err"] > 10.0
+
+
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """--dump-outputs: after the timed steps bench.py writes the raw output block its last timed step
+    handed the caller, as float64 samples [L][O]; --steps is the number of timed steps.  The inputs are
+    seeded, so a second run with the same arguments dumps the same block, and so does a longer run whose
+    last step saw the same input history (same step index modulo the pool of 4 input blocks, rings of
+    N = 8 blocks full in both)."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BFHIP_DIST_BACKEND"):
+        env.pop(k, None)
+
+    def run(steps, name):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "8",
+                            "--workload", "B", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=280, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["verify"]["ok"]
+        assert d["dump_outputs"]["arrays"] == {"out": [8192, 8]}
+        return np.load(tmp_path / name / "out.npy")
+
+    a, b, c = run(8, "a"), run(8, "b"), run(12, "c")
+    assert a.dtype == np.float64 and a.shape == (8192, 8)
+    assert np.array_equal(a, np.round(a)) and 100 < np.abs(a).max() < 2 ** 23     # S24 counts of a real signal
+    assert np.abs(a - b).max() <= 1.0 and np.abs(a - c).max() <= 1.0
