@@ -173,6 +173,14 @@ def lib():
     L.bfhip_nupc_block_dev.argtypes = [vp, vp, vp]
     L.bfhip_nupc_sync.argtypes = [vp]
     L.bfhip_nupc_get_overflow.argtypes = [vp, ci, C.POINTER(Overflow)]
+    L.bfhip_nupc_add_coeff.argtypes = [vp, ci, vp, C.c_long]
+    L.bfhip_nupc_set_crossfade.argtypes = [vp, ci]
+    L.bfhip_nupc_set_coeff.argtypes = [vp, ci, ci]
+    L.bfhip_nupc_switch_frame.restype = C.c_long
+    L.bfhip_nupc_switch_frame.argtypes = [vp]
+    L.bfhip_nupc_switch_busy.argtypes = [vp]
+    L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
+    L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -580,6 +588,33 @@ class Nupc:
         of = Overflow()
         self._chk(lib().bfhip_nupc_get_overflow(self.h, ch, C.byref(of)))
         return of
+
+    # run-time control (include/bfhip_nupc.h): coefficient switches and output gain
+    def add_coeff(self, filt, taps):
+        """another impulse response for filter `filt` (add_filter order); returns the set index"""
+        taps = np.ascontiguousarray(taps, self.dt)
+        return self._chk(lib().bfhip_nupc_add_coeff(self.h, filt, _ptr(taps), len(taps)))
+
+    def set_crossfade(self, frames):
+        self._chk(lib().bfhip_nupc_set_crossfade(self.h, frames))
+
+    def set_coeff(self, filt, coeff):
+        self._chk(lib().bfhip_nupc_set_coeff(self.h, filt, coeff))
+
+    def switch_frame(self):
+        """t_sw of the last committed switch, -1 if none yet"""
+        r = lib().bfhip_nupc_switch_frame(self.h)
+        return self._chk(r) if r != -1 else -1
+
+    def switch_busy(self):
+        return bool(self._chk(lib().bfhip_nupc_switch_busy(self.h)))
+
+    def update_coeff(self, filt, coeff, taps):
+        taps = np.ascontiguousarray(taps, self.dt)
+        self._chk(lib().bfhip_nupc_update_coeff(self.h, filt, coeff, _ptr(taps), len(taps)))
+
+    def set_output_gain(self, ch, gain):
+        self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))
 
 
 def device_count():

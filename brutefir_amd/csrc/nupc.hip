@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,24 +40,32 @@ using namespace bfhip;
 
 namespace {
 
-// acc[(pos + j) mod A][o] += seg[j][o] for an L_k x n_out block of a segment's output
+// acc[(pos + j) mod A][o] += seg[j][o] for an L_k x n_out block of a segment's output; during a
+// coefficient switch a block that ran under both assignments adds its second output (seg2) into
+// the other ring (acc2) in the same pass
 template <typename T>
 __global__ __launch_bounds__(256) void
-nupc_accumulate_kernel(T *__restrict__ acc, const T *__restrict__ seg, unsigned long long pos,
-                       int A, int n_out, int n_frames) {
+nupc_accumulate_kernel(T *__restrict__ acc, const T *__restrict__ seg, T *__restrict__ acc2,
+                       const T *__restrict__ seg2, unsigned long long pos, int A, int n_out, int n_frames) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n_frames * n_out) return;
     const size_t j = i / n_out, o = i % n_out;
-    acc[(size_t)((pos + j) % (unsigned long long)A) * n_out + o] += seg[i];
+    const size_t cell = (size_t)((pos + j) % (unsigned long long)A) * n_out + o;
+    acc[cell] += seg[i];
+    if (acc2) acc2[cell] += seg2[i];
 }
 
-// output block b: L_0 frames out of the ring, scaled into output units, requantised like
-// convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114), ring region cleared.  One workgroup
-// per output channel.
+// output block b: L_0 frames out of the ring, scaled into output units (output gain folded into
+// inv_scale), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114), ring
+// region cleared.  One workgroup per output channel.
+// Outside a coefficient switch (acc_new == nullptr) only the live ring is read.  Inside one,
+// acc_old holds the old assignment's output and acc_new the new one's; frame t of the block
+// (rel = t - t_sw) is old before the switch frame, new from t_sw + F on, and the linear ramp
+// (1 - w) old + w new, w = rel / (F - 1), in between; both rings' cells are cleared.
 template <typename T>
 __global__ __launch_bounds__(256) void
-nupc_emit_kernel(T *__restrict__ acc, unsigned long long pos, int A, int n_out, int L0,
-                 const DevFormat *__restrict__ fmt, const double *__restrict__ inv_scale,
+nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
+                 long long rel0, int F, const DevFormat *__restrict__ fmt, const double *__restrict__ inv_scale,
                  DevOverflow *__restrict__ over, uint8_t *__restrict__ raw, double safety_limit,
                  int *__restrict__ status, unsigned int *__restrict__ arrive, int *__restrict__ host_status) {
     const int ch = blockIdx.x, tid = threadIdx.x;
@@ -68,10 +77,20 @@ nupc_emit_kernel(T *__restrict__ acc, unsigned long long pos, int A, int n_out, 
     Quantiser<T> qz;
     qz.init(f, of, safety_limit);
     for (int n = tid; n < L0; n += 256) {
-        T *cell = &acc[(size_t)((pos + n) % (unsigned long long)A) * n_out + ch];
-        const T x = *cell * sc;
-        *cell = (T)0;
-        qz.put(x, base + (size_t)n * stride);
+        const size_t c = (size_t)((pos + n) % (unsigned long long)A) * n_out + ch;
+        T y = acc_old[c];
+        acc_old[c] = (T)0;
+        if (acc_new) {
+            const T y_new = acc_new[c];
+            acc_new[c] = (T)0;
+            const long long rel = rel0 + n;
+            if (rel >= F) y = y_new;
+            else if (rel >= 0) {
+                const T w = (T)((double)rel / (double)(F - 1));
+                y = ((T)1 - w) * y + w * y_new;
+            }
+        }
+        qz.put(y * sc, base + (size_t)n * stride);
     }
     qz.reduce(tid, 256);
     if (tid == 0) {
@@ -125,6 +144,12 @@ struct Seg {
     hipEvent_t ev_done = nullptr, ev_consumed = nullptr;
     bool pending = false, consumed_once = false;
     unsigned long long pending_pos = 0, due_block = 0;
+    void *pending_acc[2] = {nullptr, nullptr};   // the rings d_out / d_out2 of the pending block go to
+    // coefficient switches (only allocated when some filter has more than one set)
+    void *d_out2 = nullptr;     // [L][n_out]: the second assignment's output of a block run under both
+    void *d_z = nullptr;        // spectra between the split-phase MAC and output calls
+    std::vector<int> eng_set;   // per filter: the set the engine's filter runs now
+    std::vector<std::vector<int>> n_blocks;   // [filter][set]: partitions the set has in this engine
 };
 
 }  // namespace
@@ -154,6 +179,26 @@ struct bfhip_nupc {
     double *d_inv_scale = nullptr;
     DevOverflow *d_over = nullptr;
     int *d_status = nullptr;
+    // coefficient sets and switches (filters numbered in add_filter order; set j of filter f is
+    // engine coefficient coeff[f][j] in every segment engine)
+    std::vector<std::vector<int>> coeff;
+    std::vector<int> live;                 // per filter: the set of the newest committed assignment
+    std::vector<int> queued;               // per filter: requested set, -1 = none
+    int crossfade = 0;                     // frames for the next switch (default L0)
+    bool can_switch = false;               // some filter has a second set: the spare ring exists
+    void *d_acc2 = nullptr;                // the spare ring
+    int cur = 0;                           // ring of the live assignment: 0 = d_acc, 1 = d_acc2
+    bool sw = false;                       // a committed switch has old-assignment work or fade frames left
+    long long t_sw = -1;                   // its switch frame (-1: none committed yet)
+    int sw_F = 0;                          // its fade length
+    long long old_hi = 0;                  // end of the frames the old assignment has written
+    std::vector<int> sw_old;               // the old assignment (the new one is `live`)
+    // output gain, folded into the emit step's 1/scale
+    std::vector<double> gain;
+    bool gain_dirty = false;
+    double *h_inv = nullptr;               // pinned staging of the per-channel factors
+    hipEvent_t ev_gain = nullptr;          // the last upload out of h_inv has been done
+    void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
 extern "C" {
@@ -197,6 +242,8 @@ bfhip_nupc *bfhip_nupc_create(int device, int realsize, int n_in, int n_out, int
             f.sample_spacing = c; f.byte_offset = ch * realsize;         // interleaved frames
         }
     }
+    n->crossfade = seg_length[0];          // the reference's one-block fade
+    n->gain.assign(n_out, 1.0);
     return n;
 }
 
@@ -209,16 +256,20 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     for (auto &s : n->seg) {
         if (s.eng) bfhip_engine_destroy(s.eng);
         if (s.d_out) (void)hipFree(s.d_out);
+        if (s.d_out2) (void)hipFree(s.d_out2);
+        if (s.d_z) (void)hipFree(s.d_z);
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
         if (s.ev_consumed) (void)hipEventDestroy(s.ev_consumed);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
-    void *p[] = {n->d_acc, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive};
+    void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive};
     for (void *q : p) if (q) (void)hipFree(q);
     if (n->h_status) (void)hipHostFree(n->h_status);
     if (n->h_in) (void)hipHostFree(n->h_in);
     if (n->h_out) (void)hipHostFree(n->h_out);
     if (n->h_over) (void)hipHostFree(n->h_over);
+    if (n->h_inv) (void)hipHostFree(n->h_inv);
+    if (n->ev_gain) (void)hipEventDestroy(n->ev_gain);
     if (n->ev_in) (void)hipEventDestroy(n->ev_in);
     if (n->stream) (void)hipStreamDestroy(n->stream);
     delete n;
@@ -245,6 +296,7 @@ int bfhip_nupc_add_filter(bfhip_nupc *n, int in_ch, int out_ch, const void *taps
                           double in_scale, double out_scale) {
     if (!n || !taps || n_taps < 1 || in_ch < 0 || in_ch >= n->n_in || out_ch < 0 || out_ch >= n->n_out) return nfail(BFHIP_EINVAL, "nupc_add_filter: bad argument");
     if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_add_filter after finalize");
+    int set0 = -1;
     for (auto &s : n->seg) {
         const long avail = n_taps - s.off;
         const long cap = (long)s.L * s.N;
@@ -254,11 +306,44 @@ int bfhip_nupc_add_filter(bfhip_nupc *n, int in_ch, int out_ch, const void *taps
         if (take == 0) { zero.assign((size_t)n->rs, 0); src = zero.data(); }
         const int c = bfhip_engine_add_coeff(s.eng, src, take == 0 ? 1 : (int)take, 1.0, take == 0 ? 1 : 0);
         if (c < 0) return nfail(c, std::string("nupc_add_filter: ") + bfhip_last_error());
+        if (set0 >= 0 && c != set0) return nfail(BFHIP_EINVAL, "nupc_add_filter: the segment engines disagree on coefficient numbering");
+        set0 = c;
+        s.eng_set.push_back(0);
+        s.n_blocks.push_back({take == 0 ? 1 : (int)((take + s.L - 1) / s.L)});
         // the engines emit plain reals: the output format's 1/scale is applied at the emit step
         const int r = bfhip_engine_add_filter(s.eng, 1, &in_ch, &in_scale, 0, nullptr, nullptr, 1, &out_ch, &out_scale, c, 0, 0);
         if (r < 0) return nfail(r, std::string("nupc_add_filter: ") + bfhip_last_error());
     }
+    n->coeff.push_back({set0});
+    n->live.push_back(0);
+    n->queued.push_back(-1);
     return BFHIP_OK;
+}
+
+// another impulse response for a filter (before finalize): loaded into every segment engine as a
+// set of its own with the segment's full partition count, so that update_coeff can rewrite all of it
+int bfhip_nupc_add_coeff(bfhip_nupc *n, int filter, const void *taps, long n_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_add_coeff after finalize");
+    if (filter < 0 || filter >= (int)n->coeff.size() || !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
+        return nfail(BFHIP_EINVAL, "nupc_add_coeff: bad argument");
+    OWNER(n);
+    int c0 = -1;
+    for (auto &s : n->seg) {
+        const long cap = (long)s.L * s.N;
+        const long avail = n_taps - s.off;
+        const long take = avail < 0 ? 0 : (avail > cap ? cap : avail);
+        std::vector<unsigned char> zero;
+        const void *src = (const unsigned char *)taps + (size_t)s.off * n->rs;
+        if (take == 0) { zero.assign((size_t)n->rs, 0); src = zero.data(); }
+        const int c = bfhip_engine_add_coeff(s.eng, src, take == 0 ? 1 : (int)take, 1.0, s.N);
+        if (c < 0) return nfail(c, std::string("nupc_add_coeff: ") + bfhip_last_error());
+        if (c0 >= 0 && c != c0) return nfail(BFHIP_EINVAL, "nupc_add_coeff: the segment engines disagree on coefficient numbering");
+        c0 = c;
+    }
+    for (auto &s : n->seg) s.n_blocks[filter].push_back(s.N);
+    n->coeff[filter].push_back(c0);
+    return (int)n->coeff[filter].size() - 1;
 }
 
 static int nupc_finalize_impl(bfhip_nupc *n);
@@ -311,7 +396,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
         const bfhip_format &f = n->fmt[1][ch];
         df[ch].isfloat = f.isfloat; df[ch].swap = f.swap; df[ch].bytes = f.bytes; df[ch].sbytes = f.sbytes;
         df[ch].sample_spacing = f.sample_spacing; df[ch].byte_offset = f.byte_offset; df[ch].alt = nullptr;
-        inv[ch] = 1.0 / f.scale;                                         // bfrun.c:1850
+        inv[ch] = 1.0 / f.scale * n->gain[ch];                           // bfrun.c:1850
         memset(&ov[ch], 0, sizeof(DevOverflow));
         ov[ch].max = f.isfloat ? 1.0 : (double)((uint64_t)1 << ((f.sbytes << 3) - 1)) - 1;
     }
@@ -330,6 +415,15 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_out, (size_t)L0 * n->frame_bytes[1], hipHostMallocDefault));
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_over, (size_t)n->n_out * sizeof(DevOverflow), hipHostMallocDefault));
     *n->h_status = 0;
+    NCHK(bfhip_internal_pin_alloc((void **)&n->h_inv, (size_t)n->n_out * sizeof(double), hipHostMallocDefault));
+    NCHK(hipEventCreateWithFlags(&n->ev_gain, hipEventDisableTiming));
+    NCHK(hipEventRecord(n->ev_gain, n->stream));
+    n->gain_dirty = false;
+    for (auto &c : n->coeff) n->can_switch = n->can_switch || c.size() > 1;
+    if (n->can_switch) {
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_acc2, (size_t)A * n->n_out * n->rs));
+        NCHK(hipMemset(n->d_acc2, 0, (size_t)A * n->n_out * n->rs));
+    }
     for (auto &s : n->seg) {
         for (int ch = 0; ch < n->n_in; ch++) ECHK(bfhip_engine_set_format(s.eng, BFHIP_IN, ch, &n->fmt[0][ch]));
         for (int ch = 0; ch < n->n_out; ch++) {
@@ -351,6 +445,11 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
         ECHK(bfhip_engine_set_stream(s.eng, s.delay_steps > 0 ? s.stream : n->stream));
         ECHK(bfhip_engine_set_status_dev(s.eng, n->d_status));
         NCHK(bfhip_internal_dev_alloc((void **)&s.d_out, (size_t)s.L * n->n_out * n->rs));
+        if (n->can_switch) {
+            NCHK(bfhip_internal_dev_alloc((void **)&s.d_out2, (size_t)s.L * n->n_out * n->rs));
+            // n_out spectra of L complex numbers (rounded up to the MAC's output groups)
+            NCHK(bfhip_internal_dev_alloc((void **)&s.d_z, (size_t)((n->n_out + 7) / 8 * 8) * s.L * 2 * n->rs));
+        }
     }
     n->finalized = true;
     return BFHIP_OK;
@@ -360,16 +459,83 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
 
 namespace {
 
-int nupc_accumulate(bfhip_nupc *n, const Seg &s, unsigned long long pos) {
+int nupc_accumulate(bfhip_nupc *n, const Seg &s, unsigned long long pos, void *acc, void *acc2) {
     const size_t cnt = (size_t)s.L * n->n_out;
     if (n->rs == 4)
         hipLaunchKernelGGL(nupc_accumulate_kernel<float>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->stream,
-                           (float *)n->d_acc, (const float *)s.d_out, pos, n->A, n->n_out, s.L);
+                           (float *)acc, (const float *)s.d_out, (float *)acc2, (const float *)s.d_out2, pos, n->A, n->n_out, s.L);
     else
         hipLaunchKernelGGL(nupc_accumulate_kernel<double>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->stream,
-                           (double *)n->d_acc, (const double *)s.d_out, pos, n->A, n->n_out, s.L);
+                           (double *)acc, (const double *)s.d_out, (double *)acc2, (const double *)s.d_out2, pos, n->A, n->n_out, s.L);
     NCHK(hipGetLastError());
     return BFHIP_OK;
+}
+
+// point a segment engine's filters at an assignment (a plan rebuild at its next call if any moved)
+int seg_assign(Seg &s, const bfhip_nupc *n, const std::vector<int> &asg) {
+    for (size_t f = 0; f < asg.size(); f++) {
+        if (s.eng_set[f] == asg[f]) continue;
+        ECHK(bfhip_engine_set_coeff(s.eng, (int)f, n->coeff[f][asg[f]]));
+        s.eng_set[f] = asg[f];
+    }
+    return BFHIP_OK;
+}
+
+// one block of a segment: under one assignment into d_out, or (dual) the input transform once and
+// the MAC + inverse transform under the old assignment into d_out and under the new one into
+// d_out2.  The engine keeps whichever assignment it ran last, so a run of dual blocks costs one
+// plan rebuild each, not two.
+int seg_run(bfhip_nupc *n, Seg &s, const uint8_t *in, int mode /* 0 old, 1 new, 2 both */) {
+    const std::vector<int> &old_asg = n->sw ? n->sw_old : n->live;
+    if (mode != 2) {
+        { const int r = seg_assign(s, n, mode == 0 ? old_asg : n->live); if (r < 0) return r; }
+        ECHK(bfhip_engine_block_dev(s.eng, in, s.d_out));
+        return BFHIP_OK;
+    }
+    const bool new_first = s.eng_set == n->live;
+    ECHK(bfhip_engine_inputs_dev(s.eng, in));
+    for (int k = 0; k < 2; k++) {
+        const bool is_new = (k == 0) == new_first;
+        { const int r = seg_assign(s, n, is_new ? n->live : old_asg); if (r < 0) return r; }
+        ECHK(bfhip_engine_mac_dev(s.eng, s.d_z));
+        ECHK(bfhip_engine_outputs_dev(s.eng, s.d_z, 0, n->n_out, is_new ? s.d_out2 : s.d_out));
+    }
+    ECHK(bfhip_engine_advance(s.eng));
+    return BFHIP_OK;
+}
+
+// the queued requests become one switch whose first output block is the one starting at t_req
+void nupc_commit(bfhip_nupc *n, unsigned long long t_req) {
+    std::vector<int> asg = n->live;
+    for (size_t f = 0; f < asg.size(); f++) if (n->queued[f] >= 0) asg[f] = n->queued[f];
+    std::fill(n->queued.begin(), n->queued.end(), -1);
+    if (asg == n->live) return;                                   // nothing changes
+    const unsigned long long L0 = (unsigned long long)n->seg[0].L;
+    long long t_sw = (long long)t_req;
+    for (const Seg &s : n->seg) {
+        // segment k's first block launched from now on computes frames from e_k - L_k + off_k on
+        const unsigned long long L = (unsigned long long)s.L;
+        const unsigned long long e = (t_req + L0 + L - 1) / L * L;
+        t_sw = std::max(t_sw, (long long)(e - L) + s.off);
+    }
+    n->sw_old = n->live;
+    n->live = asg;
+    n->sw = true;
+    n->t_sw = t_sw;
+    n->sw_F = n->crossfade;
+    n->old_hi = t_sw;          // what was launched before wrote frames < t_sw only
+}
+
+// after the block call that emitted frames up to `end`: is old-assignment work or fade left?
+bool nupc_switch_left(const bfhip_nupc *n, unsigned long long end) {
+    const long long old_end = n->t_sw + n->sw_F;                  // old output is needed below this frame
+    if ((long long)end < std::max(n->old_hi, old_end)) return true;
+    for (const Seg &s : n->seg) {
+        const unsigned long long L = (unsigned long long)s.L;
+        const unsigned long long next = (end / L + 1) * L;
+        if ((long long)(next - L) + s.off < old_end) return true;
+    }
+    return false;
 }
 
 }  // namespace
@@ -388,45 +554,76 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     const size_t wpos = (size_t)((end - L0) % (unsigned long long)n->in_frames);
     if ((const uint8_t *)rawin_dev != n->d_in + wpos * n->frame_bytes[0])     // block() uploads straight into the slot
         NCHK(hipMemcpyAsync(n->d_in + wpos * n->frame_bytes[0], rawin_dev, (size_t)L0 * n->frame_bytes[0], hipMemcpyDeviceToDevice, n->stream));
+    if (n->gain_dirty) {
+        // output gains set since the last block: in force from this block's first frame
+        NCHK(hipEventSynchronize(n->ev_gain));                    // the previous upload has read h_inv
+        for (int ch = 0; ch < n->n_out; ch++) n->h_inv[ch] = 1.0 / n->fmt[1][ch].scale * n->gain[ch];
+        NCHK(hipMemcpyAsync(n->d_inv_scale, n->h_inv, (size_t)n->n_out * sizeof(double), hipMemcpyHostToDevice, n->stream));
+        NCHK(hipEventRecord(n->ev_gain, n->stream));
+        n->gain_dirty = false;
+    }
+    if (!n->sw) nupc_commit(n, end - L0);
+    const long long old_end = n->t_sw + n->sw_F;
     bool ev_in_recorded = false;
     for (auto &s : n->seg) {
         if (end % (unsigned long long)s.L != 0) continue;
         const size_t rpos = (size_t)((end - s.L) % (unsigned long long)n->in_frames);
         const unsigned long long pos = end - s.L + (unsigned long long)s.off;
+        // which assignment(s) this block's frames [pos, pos + L) need, and into which ring
+        int mode = 1;
+        void *acc = n->ring(n->cur), *acc2 = nullptr;
+        if (n->sw) {
+            const bool need_old = (long long)pos < old_end, need_new = (long long)(pos + s.L) > n->t_sw;
+            mode = need_old && need_new ? 2 : need_old ? 0 : 1;
+            if (mode == 1) acc = n->ring(1 - n->cur);
+            if (mode == 2) acc2 = n->ring(1 - n->cur);
+            if (need_old) n->old_hi = std::max(n->old_hi, (long long)(pos + s.L));
+        }
+        const uint8_t *in = n->d_in + rpos * n->frame_bytes[0];
         if (s.delay_steps == 0) {
-            ECHK(bfhip_engine_block_dev(s.eng, n->d_in + rpos * n->frame_bytes[0], s.d_out));
-            { const int r = nupc_accumulate(n, s, pos); if (r < 0) return r; }
+            { const int r = seg_run(n, s, in, mode); if (r < 0) return r; }
+            { const int r = nupc_accumulate(n, s, pos, acc, acc2); if (r < 0) return r; }
             continue;
         }
         if (s.pending) return nfail(BFHIP_ESTATE, "nupc: a background segment block was never collected");
         if (!ev_in_recorded) { NCHK(hipEventRecord(n->ev_in, n->stream)); ev_in_recorded = true; }
         NCHK(hipStreamWaitEvent(s.stream, n->ev_in, 0));
         if (s.consumed_once) NCHK(hipStreamWaitEvent(s.stream, s.ev_consumed, 0));   // d_out is free again
-        ECHK(bfhip_engine_block_dev(s.eng, n->d_in + rpos * n->frame_bytes[0], s.d_out));
+        { const int r = seg_run(n, s, in, mode); if (r < 0) return r; }
         NCHK(hipEventRecord(s.ev_done, s.stream));
         s.pending = true;
         s.pending_pos = pos;
+        s.pending_acc[0] = acc;
+        s.pending_acc[1] = acc2;
         s.due_block = n->block + (unsigned long long)s.delay_steps;
     }
     for (auto &s : n->seg) {
         if (!s.pending || s.due_block != n->block) continue;
         NCHK(hipStreamWaitEvent(n->stream, s.ev_done, 0));
-        { const int r = nupc_accumulate(n, s, s.pending_pos); if (r < 0) return r; }
+        { const int r = nupc_accumulate(n, s, s.pending_pos, s.pending_acc[0], s.pending_acc[1]); if (r < 0) return r; }
         NCHK(hipEventRecord(s.ev_consumed, n->stream));
         s.pending = false;
         s.consumed_once = true;
     }
     const unsigned long long opos = end - L0;
+    // inside a switch window the old assignment's ring is read beside the new one's
+    void *acc_old = n->ring(n->cur), *acc_new = n->sw ? n->ring(1 - n->cur) : nullptr;
+    const long long rel0 = n->sw ? (long long)opos - n->t_sw : 0;
     if (n->rs == 4)
-        hipLaunchKernelGGL(nupc_emit_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)n->d_acc, opos, n->A, n->n_out, L0,
-                           n->d_fmt_out, n->d_inv_scale, n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status,
-                           n->d_arrive, n->h_status);
+        hipLaunchKernelGGL(nupc_emit_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)acc_old, (float *)acc_new,
+                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
+                           (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);
     else
-        hipLaunchKernelGGL(nupc_emit_kernel<double>, dim3(n->n_out), dim3(256), 0, n->stream, (double *)n->d_acc, opos, n->A, n->n_out, L0,
-                           n->d_fmt_out, n->d_inv_scale, n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status,
-                           n->d_arrive, n->h_status);
+        hipLaunchKernelGGL(nupc_emit_kernel<double>, dim3(n->n_out), dim3(256), 0, n->stream, (double *)acc_old, (double *)acc_new,
+                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
+                           (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);
     NCHK(hipGetLastError());
     n->block++;
+    if (n->sw && !nupc_switch_left(n, end)) {
+        // the old ring has been emitted and cleared down to its last written frame: it is the spare now
+        n->sw = false;
+        n->cur = 1 - n->cur;
+    }
     return BFHIP_OK;
 }
 
@@ -476,6 +673,77 @@ int bfhip_nupc_get_overflow(bfhip_nupc *n, int ch, bfhip_overflow *of) {
     NCHK(hipSetDevice(n->device));
     NCHK(hipStreamSynchronize(n->stream));
     NCHK(hipMemcpy(of, n->d_over + ch, sizeof(DevOverflow), hipMemcpyDeviceToHost));
+    return BFHIP_OK;
+}
+
+// ---- run-time control: coefficient switches and output gain --------------------------------
+
+int bfhip_nupc_set_crossfade(bfhip_nupc *n, int frames) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (frames < 0 || frames == 1 || frames > 1048576) return nfail(BFHIP_EINVAL, "nupc_set_crossfade: 0 (hard switch) or 2 .. 1048576 frames");
+    n->crossfade = frames;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size())
+        return nfail(BFHIP_EINVAL, "nupc_set_coeff: bad filter or set");
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_coeff before finalize");
+    if (n->sw) return nfail(BFHIP_ESTATE, "nupc_set_coeff: the previous switch is still in flight (bfhip_nupc_switch_busy)");
+    n->queued[filter] = coeff;
+    return BFHIP_OK;
+}
+
+long bfhip_nupc_switch_frame(const bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_ESTATE, "null");                 // not BFHIP_EINVAL: -1 means "no switch yet"
+    return n->t_sw;
+}
+
+int bfhip_nupc_switch_busy(const bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    return n->sw ? 1 : 0;
+}
+
+// rewrite every partition of an idle set in every segment engine
+int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size() ||
+        !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff: bad argument");
+    if (coeff == n->live[filter] || coeff == n->queued[filter] || (n->sw && coeff == n->sw_old[filter]))
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff: the set is live or part of a queued / in-flight switch");
+    OWNER(n);
+    // set 0 keeps the partitions add_filter gave it: taps past them must be zero
+    const unsigned char *t = (const unsigned char *)taps;
+    auto nonzero = [&](long from, long to) {
+        for (long i = from; i < to; i++)
+            if (n->rs == 4 ? ((const float *)t)[i] != 0.0f : ((const double *)t)[i] != 0.0) return true;
+        return false;
+    };
+    for (const Seg &s : n->seg) {
+        const long covered = s.off + (long)s.n_blocks[filter][coeff] * s.L;
+        if (nonzero(std::min(covered, n_taps), std::min(s.off + (long)s.L * s.N, n_taps)))
+            return nfail(BFHIP_EINVAL, "nupc_update_coeff: set 0 of this filter is shorter than these taps (add_filter's length)");
+    }
+    NCHK(hipSetDevice(n->device));
+    for (Seg &s : n->seg) {
+        std::vector<unsigned char> part((size_t)s.L * n->rs);
+        for (int p = 0; p < s.n_blocks[filter][coeff]; p++) {
+            const long first = s.off + (long)p * s.L;
+            const long take = std::max(0L, std::min((long)s.L, n_taps - first));
+            std::fill(part.begin(), part.end(), 0);
+            if (take > 0) memcpy(part.data(), t + (size_t)first * n->rs, (size_t)take * n->rs);
+            ECHK(bfhip_engine_update_coeff_block(s.eng, n->coeff[filter][coeff], p, part.data()));
+        }
+    }
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (out_ch < 0 || out_ch >= n->n_out || !std::isfinite(gain)) return nfail(BFHIP_EINVAL, "nupc_set_output_gain: bad argument");
+    if (n->gain[out_ch] != gain) { n->gain[out_ch] = gain; n->gain_dirty = true; }
     return BFHIP_OK;
 }
 

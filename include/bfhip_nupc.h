@@ -52,6 +52,54 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
 int bfhip_nupc_sync(bfhip_nupc *n);
 int bfhip_nupc_get_overflow(bfhip_nupc *n, int out_channel, bfhip_overflow *of);
 
+/* ---- run-time control: coefficient switches (cfc) and output gain (cfoa) ------------------
+ * Filters are numbered 0, 1, ... in add_filter order.  Each filter can hold several impulse
+ * responses ("sets"); set 0 is add_filter's taps.  A switch changes which set filters run.
+ *
+ * Switch frame.  Output frames are counted from the convolver's first output frame: block call
+ * b emits frames [b*L0, (b+1)*L0).  Requests queued by bfhip_nupc_set_coeff are committed by the
+ * next block call; t_req is that call's first output frame.  Segment k (length L_k, first tap
+ * off_k) computes, when launched, frames up to off_k ahead of the output, so part of the future
+ * is already fixed under the old sets.  The switch takes effect at
+ *     t_sw = max(t_req, max_k (e_k - L_k + off_k)),  e_k = first multiple of L_k >= t_req + L0,
+ * the first frame all of whose contributions are launched after the request:
+ * t_req <= t_sw <= t_req + max_k off_k.
+ *
+ * Output.  y_old / y_new are the full-history convolutions of the input under the old and the
+ * new assignment (filter in/out scales included), F the cross-fade length, w(j) = j / (F - 1):
+ *     t < t_sw              y_old(t)
+ *     t_sw <= t < t_sw + F  (1 - w(t - t_sw)) y_old(t) + w(t - t_sw) y_new(t)
+ *     t >= t_sw + F         y_new(t)
+ * then the output gain, then the output format's 1/scale, then quantisation.  Old weight 1 at
+ * the first frame of the ramp, new weight 1 at its last, like the reference's cross-fade.
+ * Between t_req and the end of the window the segment blocks that need both assignments run
+ * their input transform once and the MAC + inverse transform twice, into two accumulators.
+ * Outside a window the cost and the output bits are those of a convolver without sets.
+ */
+/* another impulse response for `filter` (before finalize).  n_taps <= bfhip_nupc_taps(); shorter
+   sets are zero-padded.  Returns the set index (>= 1). */
+int bfhip_nupc_add_coeff(bfhip_nupc *n, int filter, const void *taps, long n_taps);
+/* cross-fade length in frames for the switches committed from now on: 0 = hard switch, >= 2 =
+   linear ramp; default L0 (the reference's one-block fade); 1 or > 1048576: BFHIP_EINVAL */
+int bfhip_nupc_set_crossfade(bfhip_nupc *n, int frames);
+/* queue filter -> set (after finalize); every call made before the next block call forms ONE
+   switch (a preset).  BFHIP_ESTATE while the previous switch is still in flight
+   (bfhip_nupc_switch_busy), and nothing changes.  A group that changes no filter's set commits
+   no switch. */
+int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff);
+/* t_sw of the last committed switch; -1 if none yet (a NULL handle: BFHIP_ESTATE) */
+long bfhip_nupc_switch_frame(const bfhip_nupc *n);
+/* 1 while a committed switch has old-coefficient work or fade frames left, else 0 */
+int bfhip_nupc_switch_busy(const bfhip_nupc *n);
+/* rewrite a set that is neither live nor part of a queued / in-flight switch (BFHIP_ESTATE
+   otherwise), at run time (bflogic_eq's "render into the inactive set, then switch").  Sets added
+   by add_coeff cover the whole schedule; set 0 keeps add_filter's length, and taps past it must
+   be zero (BFHIP_EINVAL).  Synchronous: waits for the segment engines' pending blocks. */
+int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps);
+/* per-output gain applied at the emit step, exact from the first frame of the next block call's
+   output; 0.0 mutes; default 1.0 (folded into the 1/scale factor: exact) */
+int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);
+
 #ifdef __cplusplus
 }
 #endif
