@@ -151,10 +151,12 @@ struct Filter {
 };
 
 constexpr int MAX_TIMED = 4096;
-// event pairs of a timed block: 0 K1 (input transforms), 1 K2 (MAC), 2 K3 (output pass, everything
-// of it), 3 the part of the output pass behind the inverse transforms (dither, N:1 mix, sub-sample
-// delay), 4 the per-filter level kernels in front of the MAC (N-way input mixes, cascades, cross-fades)
-constexpr int EV_PAIRS = 5, EV_PER_BLOCK = 2 * EV_PAIRS;
+// event pairs of a timed block: T_IN K1 (input transforms), T_MAC K2 (MAC), T_OUT K3 (output pass,
+// everything of it), T_POST the part of the output pass behind the inverse transforms (dither, N:1
+// mix, sub-sample delay), T_LEVELS the per-filter level kernels in front of the MAC (N-way input
+// mixes, cascades, cross-fades)
+enum { T_IN, T_MAC, T_OUT, T_POST, T_LEVELS, EV_PAIRS };
+constexpr int EV_PER_BLOCK = 2 * EV_PAIRS;
 
 // Host mirror of the reference's integer delay buffer (delay.c:29-45, 229-340, 346-411): same
 // state variables, same decisions; the byte moves themselves are emitted as ByteOps that a
@@ -304,35 +306,31 @@ struct bfhip_engine {
     hipStream_t stream = nullptr;      // main stream: per-filter kernels and the crossbar MAC
     bool own_stream = false;
     hipStream_t ls = nullptr;          // stream the next launch goes to
-    // Pipelined block (bfhip_engine_block[_dev]): the input FFT of block t+1 and the inverse
-    // FFT / requantiser of block t-1 run on their own streams beside the HBM-bound MAC of
-    // block t, the way the reference overlaps its input, filter and output processes
-    // (bfrun.c:2312-2616).  Needs one spare ring slot (R = N + 1) and two Zp buffers.
-    bool pipelined = false;            // decided at finalize (or BFHIP_OVERLAP=0/1)
+    // How bfhip_engine_block[_dev] schedules a block (BFHIP_MODE_*, choose_mode at finalize):
+    //  - PIPELINED: the input FFT of block t+1 and the inverse FFT / requantiser of block t-1 run on
+    //    their own streams beside the HBM-bound MAC of block t, the way the reference overlaps its
+    //    input, filter and output processes (bfrun.c:2312-2616).  Needs one spare ring slot (R = N + 1).
+    //  - DEFERRED (large crossbars on one stream): the inverse transforms of block t run in ONE launch
+    //    with the forward transforms of block t+1 (io_wave_kernel) -- both are a handful of workgroups
+    //    that would otherwise run back to back, each alone on the chip, in front of and behind the
+    //    millisecond MAC.  The output of a block is therefore written during the NEXT
+    //    bfhip_engine_block_dev call, or by bfhip_engine_sync (which flushes it).
+    //  - PINGPONG (small crossbars with the wave FFT): [K3 of t-2 | K1 of t] in one launch on the side
+    //    stream s_in while the MAC of t-1 runs on the main stream; the MAC of t waits for that launch.
+    //    Two launches and four event calls per block instead of three launches and seven, and the two
+    //    transforms run side by side.  Outputs are owed for two calls.
+    int mode = BFHIP_MODE_SEQUENTIAL;
     int overlap_mode = -1;             // -1 auto, 0 off, 1 on (bfhip_engine_set_overlap)
     hipStream_t s_in = nullptr, s_out = nullptr;
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_mac[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    int R = 0;                         // depth of the input rings
-    void *d_Zp2 = nullptr;             // second partial-spectra buffer
-    // Deferred output (large crossbars on one stream): the inverse transforms of block t run in
-    // ONE launch with the forward transforms of block t+1 (io_wave_kernel) -- both are a handful
-    // of workgroups that would otherwise run back to back, each alone on the chip, in front of
-    // and behind the millisecond MAC.  The output of a block is therefore written during the
-    // NEXT bfhip_engine_block_dev call, or by bfhip_engine_sync (which flushes it).
-    bool defer_out = false;            // decided at finalize (BFHIP_DEFER=0/1 forces)
-    // Two-stream ping-pong (small crossbars with the wave FFT): [K3 of t-2 | K1 of t] in one launch
-    // on the side stream s_in while the MAC of t-1 runs on the main stream; the MAC of t waits for
-    // that launch.  Two launches and four event calls per block instead of three launches and
-    // seven, and the two transforms run side by side.  Outputs are owed for two calls.
-    bool pipe2 = false;                // decided at finalize (BFHIP_PIPE2=0 keeps the three-stream schedule)
-    void *d_Zp3 = nullptr;
     hipEvent_t ev_io[2] = {nullptr, nullptr}, ev_mac3[3] = {nullptr, nullptr, nullptr};
+    int R = 0;                         // depth of the input rings
     struct Pending {
         void *Zp = nullptr; size_t chunk_stride = 0; int n_chunks = 0;
         void *rawout = nullptr; hipEvent_t out_done = nullptr;
-        hipEvent_t mac_done = nullptr;     // pipe2: the side stream waits for it before the inverse transforms
+        hipEvent_t mac_done = nullptr;     // ping-pong: the side stream waits for it before the inverse transforms
     };
-    std::deque<Pending> pendq;         // outputs owed, oldest first (deferred: at most 1, pipe2: at most 2)
+    std::deque<Pending> pendq;         // outputs owed, oldest first (at most output_lag of them)
 
     // partition lengths above the LDS limit (bigfft.h): global scratch for [transform][L] complex
     bool big = false;
@@ -353,7 +351,10 @@ struct bfhip_engine {
     int *d_status = nullptr;
     int *d_status_own = nullptr;   // the engine's allocation while d_status points at a caller's word
     int *d_bad = nullptr;
-    void *d_Zp = nullptr;          // [n_chunks][n_out_padded][L] complex
+    // partial-sum ring, [n_chunks][n_out_padded][L] complex each: a schedule's block t writes
+    // d_Zp[t % zp_depth(e)]; zp_last is the buffer the last MAC (or paired MAC) wrote
+    void *d_Zp[3] = {nullptr, nullptr, nullptr};
+    int zp_last = 0;
     size_t zp_bytes = 0;
     void *d_entries = nullptr;
     size_t entries_cap = 0;
@@ -487,6 +488,23 @@ int sync_all(bfhip_engine *e) {
     if (e->stream) HIPCHK(hipStreamSynchronize(e->stream));
     if (e->s_out) HIPCHK(hipStreamSynchronize(e->s_out));
     return BFHIP_OK;
+}
+
+// the streams a block's input and output passes go to, and how many calls its output is owed for
+hipStream_t in_stream(const bfhip_engine *e) {
+    return e->mode == BFHIP_MODE_PIPELINED || e->mode == BFHIP_MODE_PINGPONG ? e->s_in : e->stream;
+}
+hipStream_t out_stream(const bfhip_engine *e) {
+    return e->mode == BFHIP_MODE_PIPELINED ? e->s_out : e->mode == BFHIP_MODE_PINGPONG ? e->s_in : e->stream;
+}
+int output_lag(const bfhip_engine *e) {
+    return e->mode == BFHIP_MODE_PINGPONG ? 2 : e->mode == BFHIP_MODE_DEFERRED ? 1 : 0;
+}
+// partial-sum buffers a schedule cycles through: the MAC of block t writes one while the output passes
+// of the blocks before it still read the others (a pair writes two at once)
+int zp_depth(const bfhip_engine *e) {
+    const int d = e->mode == BFHIP_MODE_PINGPONG ? 3 : e->mode == BFHIP_MODE_SEQUENTIAL ? 1 : 2;
+    return e->pairs ? std::max(d, 2) : d;
 }
 
 // ---------------------------------------------------------------- coefficient memory
@@ -1510,14 +1528,10 @@ int build_plan_t(bfhip_engine *e) {
     }
     const size_t zb = (size_t)S * e->n_out_padded * L * sizeof(c2<T>);
     if (zb > e->zp_bytes) {
-        if (e->d_Zp) (void)hipFree(e->d_Zp);
-        if (e->d_Zp2) (void)hipFree(e->d_Zp2);
-        if (e->d_Zp3) (void)hipFree(e->d_Zp3);
-        e->d_Zp2 = nullptr; e->d_Zp3 = nullptr;
-        HIPCHK(dev_alloc(&e->d_Zp, zb));
-        if (e->pipelined || e->defer_out || e->pairs) HIPCHK(dev_alloc(&e->d_Zp2, zb));
-        if (e->pipe2) HIPCHK(dev_alloc(&e->d_Zp3, zb));
+        for (void *&z : e->d_Zp) { if (z) (void)hipFree(z); z = nullptr; }
+        for (int i = 0; i < zp_depth(e); i++) HIPCHK(dev_alloc(&e->d_Zp[i], zb));
         e->zp_bytes = zb;
+        e->zp_last = 0;
     }
 
     // algorithmic bytes per block, SURVEY 8(d): C*(F*P + U*P + U + O) + (I+O)*L*s_raw
@@ -1604,13 +1618,15 @@ int check_format(const bfhip_format *f) {
     return f->sample_spacing >= 1 && f->byte_offset >= 0;
 }
 
-int record(bfhip_engine *e, int idx) {
+int record(bfhip_engine *e, int stage, bool end) {
     if (!e->timed_now) return BFHIP_OK;
     if (e->bs_arg != nullptr) return BFHIP_OK;           // a graph is being captured: replayed blocks are not timed
-    HIPCHK(hipEventRecord(e->ev[(size_t)e->ev_used * EV_PER_BLOCK + idx], e->ls));
-    if (idx & 1) e->timed_mask |= 1 << (idx >> 1);
+    HIPCHK(hipEventRecord(e->ev[(size_t)e->ev_used * EV_PER_BLOCK + 2 * stage + end], e->ls));
+    if (end) e->timed_mask |= 1 << stage;
     return BFHIP_OK;
 }
+int record_begin(bfhip_engine *e, int stage) { return record(e, stage, false); }
+int record_end(bfhip_engine *e, int stage) { return record(e, stage, true); }
 
 // is the block in progress one of the timed ones?  Decided once per block, by whichever entry
 // point touches it first (block_dev, or the phase calls of a multi-GPU host).
@@ -1637,14 +1653,14 @@ struct LsGuard {
 // schedule: up to two), oldest first, each as a launch of its own
 int flush_pending(bfhip_engine *e) {
     LsGuard guard{e};                  // every return path leaves the launch stream on the main stream
-    const bool side = e->pipe2 && !e->pendq.empty();
+    const bool side = e->mode == BFHIP_MODE_PINGPONG && !e->pendq.empty();
     while (!e->pendq.empty()) {
         // (popped only once its launch is in the stream: a failed launch leaves the owed output
         // queued -- the caller sees the error, and the entry's event is never silently dropped)
         const bfhip_engine::Pending p = e->pendq.front();
         // the ping-pong schedule keeps every output pass on the side stream (their overflow state
         // and the dither chains are sequential), behind the MAC that produced the spectra
-        e->ls = e->pipe2 ? e->s_in : e->stream;
+        e->ls = out_stream(e);
         if (p.mac_done) HIPCHK(hipStreamWaitEvent(e->ls, p.mac_done, 0));
         const int r = do_outputs(e, p.Zp, p.chunk_stride, p.n_chunks, 0, e->n_ch[1], p.rawout);
         if (r != BFHIP_OK) return r;
@@ -1890,7 +1906,7 @@ int do_levels(bfhip_engine *e) {
     for (auto &lj : e->level_jobs) any = any || lj.n_fill || lj.n_filt || lj.n_fade;
     if (!any) return BFHIP_OK;
     hipError_t err = hipSuccess;
-    { const int rr = record(e, 8); if (rr != BFHIP_OK) return rr; }
+    { const int rr = record_begin(e, T_LEVELS); if (rr != BFHIP_OK) return rr; }
     if (e->big) {
         size_t need = 1;
         for (auto &lj : e->level_jobs) need = std::max(need, std::max((size_t)lj.n_fill, (size_t)2 * lj.n_fade));
@@ -1900,7 +1916,7 @@ int do_levels(bfhip_engine *e) {
     if (e->big) DISPATCH_BIG(launch_levels_big, e, &err);
     else DISPATCH(launch_levels, e, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "level kernels: %s", hipGetErrorString(err));
-    return record(e, 9);
+    return record_end(e, T_LEVELS);
 }
 
 int do_mac(bfhip_engine *e, void *Zp) {
@@ -1908,6 +1924,14 @@ int do_mac(bfhip_engine *e, void *Zp) {
     e->zp_is_sum = false;
     if (e->rs == 4) launch_mac<float>(e, Zp, &err); else launch_mac<double>(e, Zp, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "mac launch: %s", hipGetErrorString(err));
+    return BFHIP_OK;
+}
+
+// the sum over the chunks of Zp into Z (Z == Zp: in place, into chunk 0)
+int sum_chunks(bfhip_engine *e, const void *Zp, void *Z) {
+    hipError_t err = hipSuccess;
+    if (e->rs == 4) launch_sum<float>(e, Zp, Z, &err); else launch_sum<double>(e, Zp, Z, &err);
+    if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
     return BFHIP_OK;
 }
 
@@ -1922,9 +1946,7 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
         // many partials (few long filters): the one-workgroup-per-channel output pass would walk
         // them one dependent load after the other; add them up with the whole chip first
         // (in place, same order) and hand over a single spectrum per channel
-        if (e->rs == 4) launch_sum<float>(e, Zp, const_cast<void *>(Zp), &err);
-        else launch_sum<double>(e, Zp, const_cast<void *>(Zp), &err);
-        if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
+        { const int rr = sum_chunks(e, Zp, const_cast<void *>(Zp)); if (rr != BFHIP_OK) return rr; }
         n_chunks = 1;
     }
     void *const user_out = rawout_dev;
@@ -1937,14 +1959,57 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
     else if (e->wave) { DISPATCH_WAVE(launch_ifft_out_wave, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err) }
     else DISPATCH(launch_ifft_out, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "ifft_out launch: %s", hipGetErrorString(err));
-    if (post) { const int rr = record(e, 6); if (rr != BFHIP_OK) return rr; }
+    if (post) { const int rr = record_begin(e, T_POST); if (rr != BFHIP_OK) return rr; }
     if (e->rs == 4) launch_dither<float>(e, first, count, (uint8_t *)rawout_dev, &err);
     else launch_dither<double>(e, first, count, (uint8_t *)rawout_dev, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "dither launch: %s", hipGetErrorString(err));
     { int rv = do_subdelay(e, 1, nullptr); if (rv != BFHIP_OK) return rv; }
     { int rv = do_vout(e, rawout_dev); if (rv != BFHIP_OK) return rv; }
     { int rv = post_outputs(e, user_out, first, count); if (rv != BFHIP_OK) return rv; }
-    return post ? record(e, 7) : BFHIP_OK;
+    return post ? record_end(e, T_POST) : BFHIP_OK;
+}
+
+// [K3 of an owed block | K1 of this block] in one launch, with the transposes of wide sides around it
+int fused_outputs_inputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first, int count,
+                         void *rawout_dev, const void *rawin_dev) {
+    int r;
+    if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    hipError_t err = hipSuccess;
+    const int slot = (int)(e->blockcounter % (unsigned int)e->R);
+    if (e->wave) { DISPATCH_WAVE(launch_io_wave, e, Zp, chunk_stride, n_chunks, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err) }
+    else DISPATCH(launch_io, e, Zp, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err);   // (one chunk)
+    if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
+    return post_outputs(e, rawout_dev, first, count);
+}
+
+// The three passes of a block with their timing records, each on e->ls: a schedule switches streams
+// and adds its waits and event records between them.
+int block_inputs(bfhip_engine *e, const void *rawin_dev) {
+    int r;
+    if ((r = record_begin(e, T_IN)) != BFHIP_OK) return r;
+    if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    return record_end(e, T_IN);
+}
+int block_mac(bfhip_engine *e, int zi) {
+    int r;
+    if ((r = do_levels(e)) != BFHIP_OK) return r;
+    if ((r = record_begin(e, T_MAC)) != BFHIP_OK) return r;
+    if ((r = do_mac(e, e->d_Zp[zi])) != BFHIP_OK) return r;
+    e->zp_last = zi;
+    return record_end(e, T_MAC);
+}
+int block_outputs(bfhip_engine *e, int zi, void *rawout_dev) {
+    int r;
+    if ((r = record_begin(e, T_OUT)) != BFHIP_OK) return r;
+    if ((r = do_outputs(e, e->d_Zp[zi], (size_t)e->n_out_padded * e->L, e->n_chunks, 0, e->n_ch[1], rawout_dev)) != BFHIP_OK) return r;
+    return record_end(e, T_OUT);
+}
+// inputs -> levels -> MAC -> outputs of one block, in order on e->ls
+int block_in_order(bfhip_engine *e, const void *rawin_dev, int zi, void *rawout_dev) {
+    int r;
+    if ((r = block_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    if ((r = block_mac(e, zi)) != BFHIP_OK) return r;
+    return block_outputs(e, zi, rawout_dev);
 }
 
 void advance(bfhip_engine *e) {
@@ -2028,16 +2093,7 @@ int rt_enqueue_overlap(bfhip_engine *e, int p) {
     HIPCHK(hipEventRecord(rt.ev_h2d[p], rt.s_h2d));
     e->ls = e->stream;
     HIPCHK(hipStreamWaitEvent(e->stream, rt.ev_h2d[p], 0));
-    if ((r = record(e, 0)) != BFHIP_OK) return r;
-    if ((r = do_inputs(e, rt.d_in[p])) != BFHIP_OK) return r;
-    if ((r = record(e, 1)) != BFHIP_OK) return r;
-    if ((r = do_levels(e)) != BFHIP_OK) return r;
-    if ((r = record(e, 2)) != BFHIP_OK) return r;
-    if ((r = do_mac(e, e->d_Zp)) != BFHIP_OK) return r;
-    if ((r = record(e, 3)) != BFHIP_OK) return r;
-    if ((r = record(e, 4)) != BFHIP_OK) return r;
-    if ((r = do_outputs(e, e->d_Zp, (size_t)e->n_out_padded * e->L, e->n_chunks, 0, e->n_ch[1], rt.d_out[p])) != BFHIP_OK) return r;
-    if ((r = record(e, 5)) != BFHIP_OK) return r;
+    if ((r = block_in_order(e, rt.d_in[p], 0, rt.d_out[p])) != BFHIP_OK) return r;
     RtCopy none;
     none.dst = nullptr; none.src = nullptr; none.n16 = 0; none.pad = 0;
     hipLaunchKernelGGL(rt_tail_kernel<0>, dim3(1), dim3(256), 0, e->stream, none, e->d_bs, e->N,
@@ -2070,16 +2126,7 @@ int rt_enqueue(bfhip_engine *e, int p) {
     }
     // (plain launches of a timed engine -- bfhip_engine_enable_timing; `benchmark: true` hosts ask for
     // BFHIP_RT_NO_GRAPH -- are bracketed by events like bfhip_engine_block_dev's; captured ones are not)
-    if ((r = record(e, 0)) != BFHIP_OK) return r;
-    if ((r = do_inputs(e, e->d_rawin)) != BFHIP_OK) return r;
-    if ((r = record(e, 1)) != BFHIP_OK) return r;
-    if ((r = do_levels(e)) != BFHIP_OK) return r;
-    if ((r = record(e, 2)) != BFHIP_OK) return r;
-    if ((r = do_mac(e, e->d_Zp)) != BFHIP_OK) return r;
-    if ((r = record(e, 3)) != BFHIP_OK) return r;
-    if ((r = record(e, 4)) != BFHIP_OK) return r;
-    if ((r = do_outputs(e, e->d_Zp, (size_t)e->n_out_padded * e->L, e->n_chunks, 0, e->n_ch[1], e->d_rawout)) != BFHIP_OK) return r;
-    if ((r = record(e, 5)) != BFHIP_OK) return r;
+    if ((r = block_in_order(e, e->d_rawin, 0, e->d_rawout)) != BFHIP_OK) return r;
     if (nodes) HIPCHK(hipMemcpyAsync(rt.h_out[p], e->d_rawout, e->raw_bytes[1], hipMemcpyDeviceToHost, e->stream));
     hipLaunchKernelGGL(rt_tail_kernel<0>, dim3(nodes ? 1u : (cout.n16 + 255) / 256), dim3(256), 0, e->stream, cout,
                        e->d_bs, e->N, (const DevOverflow *)e->d_over, rt.h_over[p], e->n_ch[1], e->d_status,
@@ -2295,7 +2342,7 @@ void bfhip_engine_destroy(bfhip_engine *e) {
     rt_release(e);
     if (e->d_vjobs) (void)hipFree(e->d_vjobs);
     e->st_vin.release(); e->st_vout.release(); e->st_sd[0].release(); e->st_sd[1].release();
-    if (e->d_Zp2) (void)hipFree(e->d_Zp2);
+    for (void *z : e->d_Zp) if (z) (void)hipFree(z);
     for (int i = 0; i < 2; i++) {
         if (e->ev_in[i]) (void)hipEventDestroy(e->ev_in[i]);
         if (e->ev_mac[i]) (void)hipEventDestroy(e->ev_mac[i]);
@@ -2303,12 +2350,11 @@ void bfhip_engine_destroy(bfhip_engine *e) {
         if (e->ev_io[i]) (void)hipEventDestroy(e->ev_io[i]);
     }
     for (int i = 0; i < 3; i++) if (e->ev_mac3[i]) (void)hipEventDestroy(e->ev_mac3[i]);
-    if (e->d_Zp3) (void)hipFree(e->d_Zp3);
     if (e->s_in) (void)hipStreamDestroy(e->s_in);
     if (e->s_out) (void)hipStreamDestroy(e->s_out);
     if (e->d_status_own) e->d_status = e->d_status_own;
     void *ptrs[] = {e->d_tw, e->d_prev, e->d_ring, e->d_fmt[0], e->d_fmt[1], e->d_over, e->d_status,
-                    e->d_bad, e->d_Zp, e->d_entries, e->d_chunks, e->d_rawin, e->d_rawout, e->d_taps,
+                    e->d_bad, e->d_entries, e->d_chunks, e->d_rawin, e->d_rawout, e->d_taps,
                     e->d_fring, e->d_Y, e->d_Yold, e->d_evalprev, e->d_jobs,
                     e->d_dither_ch, e->d_dither_state, e->d_dither_table, e->d_randmap, e->d_skip_quant, e->d_timeout,
                     e->d_big[0], e->d_big[1], e->d_big[2], e->d_tw13, e->d_tww,
@@ -2893,51 +2939,53 @@ static void copy_owned_overflow(const bfhip_engine *e, bfhip_overflow dst[], con
         if (!e->sharded || e->out_active[o]) memcpy(&dst[o], &s[o], sizeof(DevOverflow));
 }
 
+// the block schedule (BFHIP_MODE_*), decided once at finalize
+static int choose_mode(const bfhip_engine *e) {
+    // Run the FFT kernels of neighbouring blocks beside the MAC?  Pays when the MAC is short
+    // (small crossbars: config B 84 -> 58 us per block) and costs when it streams for a
+    // millisecond (config C 1.40 -> 1.77 ms): decide from the coefficient bytes per block.
+    double bytes = 0;
+    for (auto &f : e->filters) {
+        if (f.coeff < 0) continue;
+        const int d = clamp_delay(e, f.delayblocks);
+        bytes += (double)cblocks_of(e, f.coeff, d) * (double)e->L * (double)e->csize() * (double)std::max<size_t>(1, f.out_ch.size());
+    }
+    // ... and only while the transforms leave most CUs to the MAC: with hundreds of channels the
+    // FFT workgroups fill the chip themselves (config D, 256 + 256: 0.178 ms piped, 0.168 plain)
+    bool pipe = bytes / 6.4e12 < 100e-6 && e->n_ch[0] + e->n_ch[1] <= 128;
+    // (Beside a long MAC the transforms only get in the way: a MAC workgroup takes 320 of a SIMD's
+    // 512 registers per lane, no transform workgroup fits on the same CU, and on a side stream
+    // they either wait for the MAC's tail or push its workgroups together on fewer CUs --
+    // config C 1.40 -> 1.74 ms.  A 256-thread variant that did fit next to round 1's MAC hid
+    // them but slowed the MAC by as much)
+    if (e->overlap_mode >= 0) pipe = e->overlap_mode != 0;
+    // (the environment only moves the AUTOMATIC choice: an explicit bfhip_engine_set_overlap wins --
+    // the non-uniform convolver depends on its segment engines running strictly in order)
+    if (const char *env = e->overlap_mode < 0 ? getenv("BFHIP_OVERLAP") : nullptr) pipe = atoi(env) != 0;
+    bool one_to_one = true;
+    for (int io = 0; io < 2; io++) for (int c : e->n_vpp[io]) if (c > 1) one_to_one = false;
+    if (!one_to_one || e->big) pipe = false;   // one job table per side; one FFT scratch
+    // the fused [K3 | K1] launch of deferred output and ping-pong needs the plain 1:1 raw path
+    const bool plain = e->wave && !e->big && e->sdf_length <= 0 && e->dither_channels.empty() && one_to_one;
+    // one stream and a MAC that fills the chip for a long time: deferred output.  (An explicit
+    // bfhip_engine_set_overlap(e, 0) -- "strictly in order" -- beats the environment.)
+    bool defer = !pipe && plain && e->overlap_mode != 0;
+    if (const char *env = getenv("BFHIP_DEFER")) defer = defer && atoi(env) != 0;
+    if (e->pairs) pipe = false;                // block pairs run on the one main stream
+    // small MACs with the wave FFT: the two-stream ping-pong instead of three streams
+    if (pipe) return plain ? BFHIP_MODE_PINGPONG : BFHIP_MODE_PIPELINED;
+    return defer ? BFHIP_MODE_DEFERRED : BFHIP_MODE_SEQUENTIAL;
+}
+
 static int finalize_impl(bfhip_engine *e) {
     { const int ro = check_owner(e); if (ro != BFHIP_OK) return ro; }
     { const int rsh = resolve_shard(e); if (rsh != BFHIP_OK) return rsh; }
     HIPCHK(hipSetDevice(e->device));
     const size_t L = e->L;
     const size_t prev_b = (size_t)e->n_ch[0] * L * e->rs;
-    // Run the FFT kernels of neighbouring blocks beside the MAC?  Pays when the MAC is short
-    // (small crossbars: config B 84 -> 58 us per block) and costs when it streams for a
-    // millisecond (config C 1.40 -> 1.77 ms): decide from the coefficient bytes per block.
-    {
-        double bytes = 0;
-        for (auto &f : e->filters) {
-            if (f.coeff < 0) continue;
-            const int d = clamp_delay(e, f.delayblocks);
-            bytes += (double)cblocks_of(e, f.coeff, d) * (double)e->L * (double)e->csize() * (double)std::max<size_t>(1, f.out_ch.size());
-        }
-        // ... and only while the transforms leave most CUs to the MAC: with hundreds of channels the
-        // FFT workgroups fill the chip themselves (config D, 256 + 256: 0.178 ms piped, 0.168 plain)
-        e->pipelined = bytes / 6.4e12 < 100e-6 && e->n_ch[0] + e->n_ch[1] <= 128;
-        // (Beside a long MAC the transforms only get in the way: a MAC workgroup takes 320 of a SIMD's
-        // 512 registers per lane, no transform workgroup fits on the same CU, and on a side stream
-        // they either wait for the MAC's tail or push its workgroups together on fewer CUs --
-        // config C 1.40 -> 1.74 ms.  A 256-thread variant that did fit next to round 1's MAC hid
-        // them but slowed the MAC by as much)
-        if (e->overlap_mode >= 0) e->pipelined = e->overlap_mode != 0;
-        // (the environment only moves the AUTOMATIC choice: an explicit bfhip_engine_set_overlap wins --
-        // the non-uniform convolver depends on its segment engines running strictly in order)
-        if (const char *env = e->overlap_mode < 0 ? getenv("BFHIP_OVERLAP") : nullptr) e->pipelined = atoi(env) != 0;
-        for (int io = 0; io < 2; io++) for (int c : e->n_vpp[io]) if (c > 1) e->pipelined = false;   // one job table per side
-        if (e->big) e->pipelined = false;          // one FFT scratch
-        // one stream and a MAC that fills the chip for a long time: fuse the output pass of a block
-        // with the input pass of the next one (deferred output).  Needs the plain 1:1 raw path.
-        bool plain = e->wave && !e->big && e->sdf_length <= 0 && e->dither_channels.empty();
-        for (int io = 0; io < 2; io++) for (int c : e->n_vpp[io]) if (c > 1) plain = false;
-        e->defer_out = !e->pipelined && plain && e->overlap_mode != 0;
-        // (an explicit bfhip_engine_set_overlap(e, 0) -- "strictly in order" -- beats the environment:
-        // the non-uniform convolver relies on it for its segment engines)
-        if (const char *env = getenv("BFHIP_DEFER")) e->defer_out = atoi(env) != 0 && !e->pipelined && plain && e->overlap_mode != 0;
-        // small MACs with the wave FFT: the two-stream ping-pong instead of three streams
-        e->pipe2 = e->pipelined && plain;
-        if (const char *env = getenv("BFHIP_PIPE2")) e->pipe2 = e->pipe2 && atoi(env) != 0;
-    }
-    if (e->pairs) { e->pipelined = false; e->pipe2 = false; }       // block pairs run on the one main stream
+    e->mode = choose_mode(e);
     // (a pair needs the spare ring slot too: block t + 1 is transformed before the MAC reads block t - N + 1)
-    e->R = (e->pipelined || e->pairs) ? e->N + 1 : e->N;
+    e->R = (e->mode == BFHIP_MODE_PIPELINED || e->mode == BFHIP_MODE_PINGPONG || e->pairs) ? e->N + 1 : e->N;
     {
         // the shared rings are R deep, the private ones N: the counter wraps by a multiple of both
         const unsigned long long period = e->R == e->N ? (unsigned long long)e->N : (unsigned long long)e->N * e->R;
@@ -3158,7 +3206,7 @@ static int finalize_impl(bfhip_engine *e) {
         if ((r = zalloc(&e->d_evalprev, (size_t)e->n_sinks * L * e->rs)) != BFHIP_OK) return r;
     }
     if ((r = dither_upload(e)) != BFHIP_OK) return r;
-    if (e->pipelined) {
+    if (e->mode == BFHIP_MODE_PIPELINED || e->mode == BFHIP_MODE_PINGPONG) {
         HIPCHK(hipStreamCreateWithFlags(&e->s_in, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&e->s_out, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) {
@@ -3264,9 +3312,7 @@ int bfhip_engine_inputs_dev(bfhip_engine *e, const void *rawin_dev) {
     if ((r = flush_pending(e)) != BFHIP_OK) return r;
     e->ls = e->stream;
     timing_begin(e);
-    if ((r = record(e, 0)) != BFHIP_OK) return r;
-    if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-    return record(e, 1);
+    return block_inputs(e, rawin_dev);
 }
 
 int bfhip_engine_mac_dev(bfhip_engine *e, void *z_dev) {
@@ -3277,18 +3323,12 @@ int bfhip_engine_mac_dev(bfhip_engine *e, void *z_dev) {
     e->ls = e->stream;
     timing_begin(e);
     if ((r = do_levels(e)) != BFHIP_OK) return r;
-    if ((r = record(e, 2)) != BFHIP_OK) return r;
-    if (e->n_chunks == 1 && e->n_out_padded == e->n_ch[1]) {
-        if ((r = do_mac(e, z_dev)) != BFHIP_OK) return r;
-        return record(e, 3);
-    }
-    r = do_mac(e, e->d_Zp);
-    if (r != BFHIP_OK) return r;
-    if ((r = record(e, 3)) != BFHIP_OK) return r;
-    hipError_t err = hipSuccess;
-    if (e->rs == 4) launch_sum<float>(e, e->d_Zp, z_dev, &err); else launch_sum<double>(e, e->d_Zp, z_dev, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
-    return BFHIP_OK;
+    if ((r = record_begin(e, T_MAC)) != BFHIP_OK) return r;
+    const bool direct = e->n_chunks == 1 && e->n_out_padded == e->n_ch[1];
+    if ((r = do_mac(e, direct ? z_dev : e->d_Zp[0])) != BFHIP_OK) return r;
+    e->zp_last = 0;
+    if ((r = record_end(e, T_MAC)) != BFHIP_OK) return r;
+    return direct ? BFHIP_OK : sum_chunks(e, e->d_Zp[0], z_dev);
 }
 
 int bfhip_engine_outputs_dev(bfhip_engine *e, const void *z_dev, int first, int count, void *rawout_dev) {
@@ -3299,9 +3339,9 @@ int bfhip_engine_outputs_dev(bfhip_engine *e, const void *z_dev, int first, int 
     if (!z_dev || !rawout_dev) return fail(BFHIP_EINVAL, "outputs: null buffer");
     e->ls = e->stream;
     timing_begin(e);
-    if ((r = record(e, 4)) != BFHIP_OK) return r;
+    if ((r = record_begin(e, T_OUT)) != BFHIP_OK) return r;
     if ((r = do_outputs(e, z_dev, 0, 1, first, count, rawout_dev)) != BFHIP_OK) return r;
-    return record(e, 5);
+    return record_end(e, T_OUT);
 }
 
 int bfhip_engine_outputs_inputs_dev(bfhip_engine *e, const void *z_dev, int first, int count,
@@ -3318,15 +3358,9 @@ int bfhip_engine_outputs_inputs_dev(bfhip_engine *e, const void *z_dev, int firs
     }
     e->ls = e->stream;
     timing_begin(e);
-    if ((r = record(e, 0)) != BFHIP_OK) return r;      // the fused launch is timed in the input slot
-    hipError_t err = hipSuccess;
-    const int slot = (int)(e->blockcounter % (unsigned int)e->R);
-    if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-    if (e->wave) { DISPATCH_WAVE(launch_io_wave, e, z_dev, (size_t)0, 1, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err) }
-    else DISPATCH(launch_io, e, z_dev, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
-    if ((r = post_outputs(e, rawout_dev, first, count)) != BFHIP_OK) return r;
-    return record(e, 1);
+    if ((r = record_begin(e, T_IN)) != BFHIP_OK) return r;      // the fused launch is timed in the input slot
+    if ((r = fused_outputs_inputs(e, z_dev, 0, 1, first, count, rawout_dev, rawin_dev)) != BFHIP_OK) return r;
+    return record_end(e, T_IN);
 }
 
 int bfhip_engine_advance(bfhip_engine *e) {
@@ -3335,8 +3369,106 @@ int bfhip_engine_advance(bfhip_engine *e) {
     return BFHIP_OK;
 }
 
+// PIPELINED: the same passes on three streams
+static int block_three_streams(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
+                               hipEvent_t in_ready, hipEvent_t out_done) {
+    int r;
+    const int buf = (int)(e->blocks_done & 1);
+    // K1 on the input stream.  It overwrites the ring slot of block t-R, last read by the MAC
+    // of block t-2 (the MAC of t-1 reaches back only N = R-1 blocks).
+    e->ls = e->s_in;
+    if (e->blocks_done >= 2) HIPCHK(hipStreamWaitEvent(e->s_in, e->ev_mac[buf], 0));
+    if (in_ready) HIPCHK(hipStreamWaitEvent(e->s_in, in_ready, 0));
+    if ((r = block_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    HIPCHK(hipEventRecord(e->ev_in[buf], e->s_in));
+
+    // per-filter kernels and the crossbar MAC on the main stream; Zp[buf] is free once the
+    // output pass of block t-2 has read it
+    e->ls = e->stream;
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_in[buf], 0));
+    if (e->blocks_done >= 2) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_out[buf], 0));
+    if ((r = block_mac(e, buf)) != BFHIP_OK) return r;
+    HIPCHK(hipEventRecord(e->ev_mac[buf], e->stream));
+
+    // K3 (+ dither pass) on the output stream
+    e->ls = e->s_out;
+    HIPCHK(hipStreamWaitEvent(e->s_out, e->ev_mac[buf], 0));
+    if ((r = block_outputs(e, buf, rawout_dev)) != BFHIP_OK) return r;
+    HIPCHK(hipEventRecord(e->ev_out[buf], e->s_out));
+    if (out_done) HIPCHK(hipEventRecord(out_done, e->s_out));
+    return BFHIP_OK;
+}
+
+// DEFERRED (lag 1, main stream) and PINGPONG (lag 2, side stream): [K3 of block t-lag | K1 of block t]
+// in one launch, then the MAC of block t on the main stream; K3 of block t is owed to a later call (or
+// to flush / sync).  Same kernels, same order per channel: same bits.  With ping-pong the MAC of t-1
+// (main) and the fused launch (side) overlap: K1 fills the spare ring slot, K3 reads the third Zp buffer.
+static int block_owed(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
+                      hipEvent_t in_ready, hipEvent_t out_done) {
+    int r;
+    const bool side = e->mode == BFHIP_MODE_PINGPONG;
+    const int zi = (int)(e->blocks_done % (unsigned)zp_depth(e));
+    e->ls = in_stream(e);
+    if (in_ready) HIPCHK(hipStreamWaitEvent(e->ls, in_ready, 0));
+    if ((r = record_begin(e, T_IN)) != BFHIP_OK) return r;
+    if (e->pendq.size() >= (size_t)output_lag(e)) {
+        const bfhip_engine::Pending p = e->pendq.front();     // popped once its launch is in the stream
+        if (p.mac_done) HIPCHK(hipStreamWaitEvent(e->ls, p.mac_done, 0));
+        if ((r = fused_outputs_inputs(e, p.Zp, p.chunk_stride, p.n_chunks, 0, e->n_ch[1], p.rawout, rawin_dev)) != BFHIP_OK) return r;
+        e->pendq.pop_front();
+        if (p.out_done) HIPCHK(hipEventRecord(p.out_done, e->ls));
+    } else {
+        if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    }
+    if ((r = record_end(e, T_IN)) != BFHIP_OK) return r;
+    if (side) {
+        const int par = (int)(e->blocks_done & 1ull);
+        HIPCHK(hipEventRecord(e->ev_io[par], e->s_in));
+        e->ls = e->stream;
+        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_io[par], 0));
+    }
+    if ((r = block_mac(e, zi)) != BFHIP_OK) return r;
+    bfhip_engine::Pending np;
+    np.Zp = e->d_Zp[zi]; np.chunk_stride = (size_t)e->n_out_padded * e->L; np.n_chunks = e->n_chunks;
+    if (e->n_chunks > 2) {
+        // many partials (few outputs, many inputs: an output-sharded rank; few long filters): add them
+        // up with the whole chip here, in place, same order -- the fused launch that owes this block's
+        // output then reads one spectrum per channel (and exists: it takes at most two)
+        if ((r = sum_chunks(e, np.Zp, np.Zp)) != BFHIP_OK) return r;
+        np.n_chunks = 1;
+    }
+    if (side) {
+        HIPCHK(hipEventRecord(e->ev_mac3[zi], e->stream));
+        np.mac_done = e->ev_mac3[zi];
+    }
+    np.rawout = rawout_dev; np.out_done = out_done;
+    e->pendq.push_back(np);
+    return BFHIP_OK;
+}
+
 static int block_dev_impl(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
-                          hipEvent_t in_ready, hipEvent_t out_done);
+                          hipEvent_t in_ready, hipEvent_t out_done) {
+    int r = ensure_ready(e);
+    if (r != BFHIP_OK) return r;
+    if (!rawin_dev || !rawout_dev) return fail(BFHIP_EINVAL, "block_dev: null buffer");
+    timing_begin(e);
+    LsGuard guard{e};
+    switch (e->mode) {
+    case BFHIP_MODE_PIPELINED: r = block_three_streams(e, rawin_dev, rawout_dev, in_ready, out_done); break;
+    case BFHIP_MODE_DEFERRED:
+    case BFHIP_MODE_PINGPONG: r = block_owed(e, rawin_dev, rawout_dev, in_ready, out_done); break;
+    default:                           // the three passes in order on the main stream
+        e->ls = e->stream;
+        // the caller's producer of rawin_dev (any stream): K1 must not start before it is done
+        if (in_ready) HIPCHK(hipStreamWaitEvent(e->stream, in_ready, 0));
+        r = block_in_order(e, rawin_dev, (int)(e->blocks_done % (unsigned)zp_depth(e)), rawout_dev);
+        // rawout_dev of THIS block is complete (and rawin_dev no longer needed) once this fires
+        if (r == BFHIP_OK && out_done) HIPCHK(hipEventRecord(out_done, e->stream));
+    }
+    if (r != BFHIP_OK) return r;
+    advance(e);
+    return BFHIP_OK;
+}
 
 int bfhip_engine_block_dev(bfhip_engine *e, const void *rawin_dev, void *rawout_dev) {
     return block_dev_impl(e, rawin_dev, rawout_dev, nullptr, nullptr);
@@ -3345,153 +3477,6 @@ int bfhip_engine_block_dev(bfhip_engine *e, const void *rawin_dev, void *rawout_
 int bfhip_engine_block_dev_ev(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
                               void *in_ready_event, void *out_done_event) {
     return block_dev_impl(e, rawin_dev, rawout_dev, (hipEvent_t)in_ready_event, (hipEvent_t)out_done_event);
-}
-
-static int block_dev_impl(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
-                          hipEvent_t in_ready, hipEvent_t out_done) {
-    int r = ensure_ready(e);
-    if (r != BFHIP_OK) return r;
-    if (!rawin_dev || !rawout_dev) return fail(BFHIP_EINVAL, "block_dev: null buffer");
-    const bool pipe = e->pipelined;
-    const int buf = (int)(e->blocks_done & 1);
-    void *Zp = ((pipe || e->defer_out) && buf) ? e->d_Zp2 : e->d_Zp;
-    timing_begin(e);
-    LsGuard guard{e};
-
-    if (e->pipe2) {
-        // side stream: [K3 of block t-2 | K1 of block t]; main stream: MAC of block t behind it.  The
-        // MAC of t-1 (main) and this launch (side) overlap: K1 fills the spare ring slot, K3 reads the
-        // third Zp buffer.
-        const int zi = (int)(e->blocks_done % 3ull), par = (int)(e->blocks_done & 1ull);
-        void *Zq = zi == 0 ? e->d_Zp : (zi == 1 ? e->d_Zp2 : e->d_Zp3);
-        e->ls = e->s_in;
-        if (in_ready) HIPCHK(hipStreamWaitEvent(e->s_in, in_ready, 0));
-        if ((r = record(e, 0)) != BFHIP_OK) return r;
-        if (e->pendq.size() >= 2) {
-            const bfhip_engine::Pending p = e->pendq.front();     // popped once its launch is in the stream
-            HIPCHK(hipStreamWaitEvent(e->s_in, p.mac_done, 0));
-            if (p.n_chunks <= 2) {
-                hipError_t err = hipSuccess;
-                const int slot = (int)(e->blockcounter % (unsigned int)e->R);
-                if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-                DISPATCH_WAVE(launch_io_wave, e, p.Zp, p.chunk_stride, p.n_chunks, 0, e->n_ch[1],
-                              k3_target(e, p.rawout), (const uint8_t *)rawin_dev, slot, &err)
-                if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
-                e->pendq.pop_front();
-                if ((r = post_outputs(e, p.rawout, 0, e->n_ch[1])) != BFHIP_OK) return r;
-            } else {
-                if ((r = do_outputs(e, p.Zp, p.chunk_stride, p.n_chunks, 0, e->n_ch[1], p.rawout)) != BFHIP_OK) return r;
-                e->pendq.pop_front();
-                if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-            }
-            if (p.out_done) HIPCHK(hipEventRecord(p.out_done, e->s_in));
-        } else {
-            if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-        }
-        if ((r = record(e, 1)) != BFHIP_OK) return r;
-        HIPCHK(hipEventRecord(e->ev_io[par], e->s_in));
-        e->ls = e->stream;
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_io[par], 0));
-        if ((r = do_levels(e)) != BFHIP_OK) return r;
-        if ((r = record(e, 2)) != BFHIP_OK) return r;
-        if ((r = do_mac(e, Zq)) != BFHIP_OK) return r;
-        if ((r = record(e, 3)) != BFHIP_OK) return r;
-        bfhip_engine::Pending np;
-        np.Zp = Zq; np.chunk_stride = (size_t)e->n_out_padded * e->L; np.n_chunks = e->n_chunks;
-        if (e->n_chunks > 2) {
-            // many partials (few long filters): add them up with the whole chip here, in place, so that
-            // the fused transform launch reads one spectrum per channel
-            hipError_t err = hipSuccess;
-            if (e->rs == 4) launch_sum<float>(e, Zq, Zq, &err); else launch_sum<double>(e, Zq, Zq, &err);
-            if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
-            np.n_chunks = 1;
-        }
-        HIPCHK(hipEventRecord(e->ev_mac3[zi], e->stream));
-        np.rawout = rawout_dev; np.out_done = out_done; np.mac_done = e->ev_mac3[zi];
-        e->pendq.push_back(np);
-        advance(e);
-        return BFHIP_OK;
-    }
-
-    if (e->defer_out && !pipe) {
-        // [K3 of block t-1 | K1 of block t] in one launch, then the MAC of block t; K3 of block t is
-        // owed to the next call (or to sync).  Same kernels, same order per channel: same bits.
-        e->ls = e->stream;
-        if (in_ready) HIPCHK(hipStreamWaitEvent(e->stream, in_ready, 0));
-        if ((r = record(e, 0)) != BFHIP_OK) return r;
-        if (!e->pendq.empty() && e->pendq.front().n_chunks <= 2) {
-            const bfhip_engine::Pending p = e->pendq.front();     // popped once its launch is in the stream
-            hipError_t err = hipSuccess;
-            const int slot = (int)(e->blockcounter % (unsigned int)e->R);
-            if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-            DISPATCH_WAVE(launch_io_wave, e, p.Zp, p.chunk_stride, p.n_chunks, 0, e->n_ch[1],
-                          k3_target(e, p.rawout), (const uint8_t *)rawin_dev, slot, &err)
-            if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
-            e->pendq.pop_front();
-            if ((r = post_outputs(e, p.rawout, 0, e->n_ch[1])) != BFHIP_OK) return r;
-            if (p.out_done) HIPCHK(hipEventRecord(p.out_done, e->stream));
-        } else {
-            if ((r = flush_pending(e)) != BFHIP_OK) return r;
-            if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-        }
-        if ((r = record(e, 1)) != BFHIP_OK) return r;
-        if ((r = do_levels(e)) != BFHIP_OK) return r;
-        if ((r = record(e, 2)) != BFHIP_OK) return r;
-        if ((r = do_mac(e, Zp)) != BFHIP_OK) return r;
-        if ((r = record(e, 3)) != BFHIP_OK) return r;
-        bfhip_engine::Pending np;
-        np.Zp = Zp; np.chunk_stride = (size_t)e->n_out_padded * e->L; np.n_chunks = e->n_chunks;
-        if (e->n_chunks > 2) {
-            // many partials (few outputs, many inputs: an output-sharded rank): add them up with the
-            // whole chip here, in place, same order -- the next call's fused [K3 | K1] launch then
-            // reads one spectrum per channel (and exists: it takes at most two)
-            hipError_t err = hipSuccess;
-            if (e->rs == 4) launch_sum<float>(e, Zp, Zp, &err); else launch_sum<double>(e, Zp, Zp, &err);
-            if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
-            np.n_chunks = 1;
-        }
-        np.rawout = rawout_dev; np.out_done = out_done; np.mac_done = nullptr;
-        e->pendq.push_back(np);
-        advance(e);
-        return BFHIP_OK;
-    }
-
-    // K1 on the input stream.  It overwrites the ring slot of block t-R, last read by the MAC
-    // of block t-2 (the MAC of t-1 reaches back only N = R-1 blocks).
-    e->ls = pipe ? e->s_in : e->stream;
-    if (pipe && e->blocks_done >= 2) HIPCHK(hipStreamWaitEvent(e->s_in, e->ev_mac[buf], 0));
-    // the caller's producer of rawin_dev (any stream): K1 must not start before it is done
-    if (in_ready) HIPCHK(hipStreamWaitEvent(e->ls, in_ready, 0));
-    if ((r = record(e, 0)) != BFHIP_OK) return r;
-    if ((r = do_inputs(e, rawin_dev)) != BFHIP_OK) return r;
-    if ((r = record(e, 1)) != BFHIP_OK) return r;
-    if (pipe) HIPCHK(hipEventRecord(e->ev_in[buf], e->s_in));
-
-    // per-filter kernels and the crossbar MAC on the main stream; Zp[buf] is free once the
-    // output pass of block t-2 has read it
-    e->ls = e->stream;
-    if (pipe) {
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_in[buf], 0));
-        if (e->blocks_done >= 2) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_out[buf], 0));
-    }
-    if ((r = do_levels(e)) != BFHIP_OK) return r;
-    if ((r = record(e, 2)) != BFHIP_OK) return r;
-    if ((r = do_mac(e, Zp)) != BFHIP_OK) return r;
-    if ((r = record(e, 3)) != BFHIP_OK) return r;
-    if (pipe) HIPCHK(hipEventRecord(e->ev_mac[buf], e->stream));
-
-    // K3 (+ dither pass) on the output stream
-    e->ls = pipe ? e->s_out : e->stream;
-    if (pipe) HIPCHK(hipStreamWaitEvent(e->s_out, e->ev_mac[buf], 0));
-    if ((r = record(e, 4)) != BFHIP_OK) return r;
-    if ((r = do_outputs(e, Zp, (size_t)e->n_out_padded * e->L, e->n_chunks, 0, e->n_ch[1], rawout_dev)) != BFHIP_OK) return r;
-    if ((r = record(e, 5)) != BFHIP_OK) return r;
-    if (pipe) HIPCHK(hipEventRecord(e->ev_out[buf], e->s_out));
-    // rawout_dev of THIS block is complete (and rawin_dev no longer needed) once this fires
-    if (out_done) HIPCHK(hipEventRecord(out_done, e->ls));
-    e->ls = e->stream;
-    advance(e);
-    return BFHIP_OK;
 }
 
 int bfhip_engine_enable_pairs(bfhip_engine *e, int on) {
@@ -3510,7 +3495,7 @@ int bfhip_engine_block_pair_dev(bfhip_engine *e, const void *rawin0_dev, void *r
     if (r != BFHIP_OK) return r;
     if (!rawin0_dev || !rawout0_dev || !rawin1_dev || !rawout1_dev) return fail(BFHIP_EINVAL, "block_pair_dev: null buffer");
     bool plain = e->pairs && e->all_dense && !e->mac_diag && e->mac_nt && e->mac_unroll == 0 && !e->any_fading &&
-                 !e->has_vchan && !e->big && !e->rt.on && e->d_Zp2 != nullptr && e->blocks_done >= (unsigned long long)e->N;
+                 !e->has_vchan && !e->big && !e->rt.on && e->d_Zp[1] != nullptr && e->blocks_done >= (unsigned long long)e->N;
     for (auto &lj : e->level_jobs) plain = plain && !lj.n_fill && !lj.n_filt && !lj.n_fade;
     if (!plain) {
         if ((r = bfhip_engine_block_dev(e, rawin0_dev, rawout0_dev)) != BFHIP_OK) return r;
@@ -3520,20 +3505,21 @@ int bfhip_engine_block_pair_dev(bfhip_engine *e, const void *rawin0_dev, void *r
     LsGuard guard{e};
     e->ls = e->stream;
     timing_begin(e);
-    if ((r = record(e, 0)) != BFHIP_OK) return r;
+    if ((r = record_begin(e, T_IN)) != BFHIP_OK) return r;
     if ((r = do_inputs(e, rawin0_dev, 0u)) != BFHIP_OK) return r;
     if ((r = do_inputs(e, rawin1_dev, 1u)) != BFHIP_OK) return r;
-    if ((r = record(e, 1)) != BFHIP_OK) return r;
-    if ((r = record(e, 2)) != BFHIP_OK) return r;
+    if ((r = record_end(e, T_IN)) != BFHIP_OK) return r;
+    if ((r = record_begin(e, T_MAC)) != BFHIP_OK) return r;
     hipError_t err = hipSuccess;
-    if (e->rs == 4) launch_mac2<float>(e, e->d_Zp, e->d_Zp2, &err); else launch_mac2<double>(e, e->d_Zp, e->d_Zp2, &err);
+    if (e->rs == 4) launch_mac2<float>(e, e->d_Zp[0], e->d_Zp[1], &err); else launch_mac2<double>(e, e->d_Zp[0], e->d_Zp[1], &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "mac2 launch: %s", hipGetErrorString(err));
-    if ((r = record(e, 3)) != BFHIP_OK) return r;
-    if ((r = record(e, 4)) != BFHIP_OK) return r;
+    e->zp_last = 1;
+    if ((r = record_end(e, T_MAC)) != BFHIP_OK) return r;
+    if ((r = record_begin(e, T_OUT)) != BFHIP_OK) return r;
     const size_t stride = (size_t)e->n_out_padded * e->L;
-    if ((r = do_outputs(e, e->d_Zp, stride, e->n_chunks, 0, e->n_ch[1], rawout0_dev)) != BFHIP_OK) return r;
-    if ((r = do_outputs(e, e->d_Zp2, stride, e->n_chunks, 0, e->n_ch[1], rawout1_dev)) != BFHIP_OK) return r;
-    if ((r = record(e, 5)) != BFHIP_OK) return r;
+    if ((r = do_outputs(e, e->d_Zp[0], stride, e->n_chunks, 0, e->n_ch[1], rawout0_dev)) != BFHIP_OK) return r;
+    if ((r = do_outputs(e, e->d_Zp[1], stride, e->n_chunks, 0, e->n_ch[1], rawout1_dev)) != BFHIP_OK) return r;
+    if ((r = record_end(e, T_OUT)) != BFHIP_OK) return r;
     e->n_pair_launches++;
     advance(e);
     advance(e);
@@ -3551,7 +3537,7 @@ int bfhip_engine_flush(bfhip_engine *e) {
 
 int bfhip_engine_output_lag(const bfhip_engine *e) {
     if (!e || !e->finalized) return 0;
-    return e->pipe2 ? 2 : ((e->defer_out && !e->pipelined) ? 1 : 0);
+    return output_lag(e);
 }
 
 int bfhip_engine_sync(bfhip_engine *e) {
@@ -3571,8 +3557,7 @@ int bfhip_engine_block(bfhip_engine *e, const void *rawin, void *rawout, bfhip_o
     if (r != BFHIP_OK) return r;
     if (!rawin || !rawout) return fail(BFHIP_EINVAL, "block: null buffer");
     static_assert(sizeof(bfhip_overflow) == sizeof(DevOverflow), "overflow struct layout");
-    hipStream_t sin = e->pipelined ? e->s_in : e->stream, sout = e->pipelined ? e->s_out : e->stream;
-    if (e->pipe2) sout = e->s_in;              // the ping-pong schedule keeps the output passes on the side stream
+    const hipStream_t sin = in_stream(e), sout = out_stream(e);
     if (overflow) HIPCHK(hipMemcpyAsync(e->d_over, overflow, e->n_ch[1] * sizeof(DevOverflow), hipMemcpyHostToDevice, sout));
     HIPCHK(hipMemcpyAsync(e->d_rawin, rawin, e->raw_bytes[0], hipMemcpyHostToDevice, sin));
     if ((r = bfhip_engine_block_dev(e, e->d_rawin, e->d_rawout)) != BFHIP_OK) return r;
@@ -3600,8 +3585,8 @@ int bfhip_engine_rt_begin(bfhip_engine *e, int flags) {
     if ((r = flush_pending(e)) != BFHIP_OK) return r;
     if (e->rt.on) return fail(BFHIP_ESTATE, "rt_begin: already in real-time mode");
     if ((r = sync_all(e)) != BFHIP_OK) return r;
-    e->pipelined = false;                      // one stream: a period is needed back as soon as possible
-    e->pipe2 = false;
+    // one stream: a period is needed back as soon as possible (deferred output stays what it was)
+    if (e->mode == BFHIP_MODE_PIPELINED || e->mode == BFHIP_MODE_PINGPONG) e->mode = BFHIP_MODE_SEQUENTIAL;
     auto &rt = e->rt;
     rt.flags = flags;
     for (int p = 0; p < 2; p++) {
@@ -3868,8 +3853,7 @@ int bfhip_engine_reset_overflow(bfhip_engine *e) {
 unsigned int bfhip_engine_blockcounter(const bfhip_engine *e) { return e ? e->blockcounter : 0; }
 int bfhip_engine_block_mode(const bfhip_engine *e) {
     if (!e || !e->finalized) return -1;
-    if (e->pipe2) return BFHIP_MODE_PINGPONG;
-    return e->pipelined ? BFHIP_MODE_PIPELINED : (e->defer_out ? BFHIP_MODE_DEFERRED : BFHIP_MODE_SEQUENTIAL);
+    return e->mode;
 }
 int bfhip_engine_uses_wave_fft(const bfhip_engine *e) { return e && e->wave ? 1 : 0; }
 int bfhip_engine_uses_stream_layout(const bfhip_engine *e) { return e && e->hstream.base ? 1 : 0; }
@@ -3899,10 +3883,10 @@ int bfhip_engine_get_timing(bfhip_engine *e, double ms[4]) {
     { const int ro = check_owner(e); if (ro != BFHIP_OK) return ro; }
     HIPCHK(hipSetDevice(e->device));
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    ms[0] = ms[1] = ms[2] = ms[3] = 0;
+    ms[0] = ms[1] = ms[2] = ms[3] = 0;                      // T_IN, T_MAC, T_OUT, blocks with a MAC
     int cnt[3] = {0, 0, 0};
     for (int i = 0; i < e->ev_used; i++) {
-        for (int k = 0; k < 3; k++) {
+        for (int k = T_IN; k <= T_OUT; k++) {
             if (!(e->ev_mask[i] & (1 << k))) continue;      // phase not launched through a timed entry point
             float t = 0;
             HIPCHK(hipEventElapsedTime(&t, e->ev[(size_t)i * EV_PER_BLOCK + 2 * k], e->ev[(size_t)i * EV_PER_BLOCK + 2 * k + 1]));
@@ -3910,8 +3894,8 @@ int bfhip_engine_get_timing(bfhip_engine *e, double ms[4]) {
             cnt[k]++;
         }
     }
-    for (int k = 0; k < 3; k++) if (cnt[k] > 0) ms[k] /= cnt[k];
-    ms[3] = cnt[1];
+    for (int k = T_IN; k <= T_OUT; k++) if (cnt[k] > 0) ms[k] /= cnt[k];
+    ms[3] = cnt[T_MAC];
     e->ev_used = 0;
     return BFHIP_OK;
 }
@@ -3926,7 +3910,7 @@ int bfhip_engine_stage_times(bfhip_engine *e, double ms[8]) {
     double sum[EV_PAIRS] = {0, 0, 0, 0, 0};
     int n_blocks = 0;
     for (int i = 0; i < e->ev_used; i++) {
-        if (!(e->ev_mask[i] & 2)) continue;                 // no MAC timed: not a whole block
+        if (!(e->ev_mask[i] & (1 << T_MAC))) continue;      // no MAC timed: not a whole block
         n_blocks++;
         for (int k = 0; k < EV_PAIRS; k++) {
             if (!(e->ev_mask[i] & (1 << k))) continue;
@@ -3937,10 +3921,10 @@ int bfhip_engine_stage_times(bfhip_engine *e, double ms[8]) {
     }
     e->ev_used = 0;
     if (n_blocks == 0) return 0;
-    const double post = sum[3] / n_blocks, out = sum[2] / n_blocks;
-    ms[1] = sum[0] / n_blocks;                              // time2freq (+ raw2real, fused)
-    ms[2] = sum[4] / n_blocks;                              // mixscale1: the per-filter input mixes / cascades
-    ms[3] = sum[1] / n_blocks;                              // convolve (+ mixscale1 of plain filters, mixscale2: fused)
+    const double post = sum[T_POST] / n_blocks, out = sum[T_OUT] / n_blocks;
+    ms[1] = sum[T_IN] / n_blocks;                           // time2freq (+ raw2real, fused)
+    ms[2] = sum[T_LEVELS] / n_blocks;                       // mixscale1: the per-filter input mixes / cascades
+    ms[3] = sum[T_MAC] / n_blocks;                          // convolve (+ mixscale1 of plain filters, mixscale2: fused)
     ms[5] = out > post ? out - post : 0.0;                  // freq2time (+ real2raw of undithered 1:1 outputs, fused)
     ms[6] = post;                                           // real2raw: dither, N:1 mix, sub-sample delay passes
     ms[7] = ms[1] + ms[2] + ms[3] + ms[5] + ms[6];
@@ -3964,12 +3948,8 @@ int bfhip_engine_read_output_spectrum(bfhip_engine *e, int ch, void *dst) {
     const size_t row = (size_t)e->L * e->csize();
     std::vector<unsigned char> tmp(row);
     memset(dst, 0, row);
+    const unsigned char *zp = (const unsigned char *)e->d_Zp[e->zp_last];
     for (int c = 0; c < (e->zp_is_sum ? 1 : e->n_chunks); c++) {
-        const unsigned char *zp = (const unsigned char *)(((e->pipelined || e->defer_out) && e->d_Zp2 && ((e->blocks_done - 1) & 1)) ? e->d_Zp2 : e->d_Zp);
-        if (e->pipe2) {
-            const int zi = (int)((e->blocks_done - 1) % 3ull);
-            zp = (const unsigned char *)(zi == 0 ? e->d_Zp : (zi == 1 ? e->d_Zp2 : e->d_Zp3));
-        }
         HIPCHK(hipMemcpy(tmp.data(), zp + ((size_t)c * e->n_out_padded + ch) * row, row, hipMemcpyDeviceToHost));
         const size_t n = (size_t)2 * e->L;
         if (e->rs == 4) for (size_t i = 0; i < n; i++) ((float *)dst)[i] += ((float *)tmp.data())[i];

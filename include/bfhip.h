@@ -281,7 +281,7 @@ unsigned long long bfhip_engine_pair_launches(const bfhip_engine *e);
        transforms of a block share one launch with the forward transforms of the next block
        ("deferred output"; bfhip_engine_sync flushes what is owed; bfhip_engine_set_overlap(e, 0)
        or BFHIP_DEFER=0 turn it off); small crossbars on the wave FFT owe their output for TWO calls
-       (ping-pong schedule, BFHIP_MODE_PINGPONG; BFHIP_PIPE2=0 turns it off).
+       (ping-pong schedule, BFHIP_MODE_PINGPONG; bfhip_engine_set_overlap(e, 0) turns it off).
    A caller that produces the input or consumes the output asynchronously uses the variant
    below instead: in_ready_event (hipEvent_t, may be NULL) is an event the caller recorded behind
    its producer of rawin_dev -- the input transform waits for it, nothing else does, so the

@@ -96,6 +96,30 @@ def test_pairs_with_powersave_and_single_blocks_in_between(hip):
         assert np.array_equal(outs[k].cpu().numpy(), np.frombuffer(w.tobytes(), np.float32).reshape(L, O)), k
 
 
+def test_output_spectrum_after_a_pair_is_the_second_block(hip, monkeypatch):
+    """bfhip_engine_read_output_spectrum after a paired MAC reads the spectra of the pair's SECOND
+    block, on an engine whose single blocks all use one partial-sum buffer"""
+    torch = _torch()
+    dev = torch.device("cuda", 0)
+    L, N, I, O = 1024, 5, 8, 16
+    monkeypatch.setenv("BFHIP_COEFF_STREAM", "2")
+    monkeypatch.setenv("BFHIP_MAC_TARGET_WGS", "16")
+    pe, _ = _crossbar(hip.Engine, L, N, 4, I, O, pairs=True)
+    se, _ = _crossbar(hip.Engine, L, N, 4, I, O)
+    assert pe.block_mode == 0                    # sequential: pairs turn the side streams off
+    blocks = cases.raw_blocks(11, N + 2, L, I, "S24_4LE")
+    srcs = [torch.from_numpy(b).to(dev) for b in blocks]
+    outs = [torch.zeros(L, O, dtype=torch.float32, device=dev) for _ in blocks]
+    for k in range(N):
+        pe.block_dev(srcs[k], outs[k])
+    pe.block_pair_dev(srcs[N], outs[N], srcs[N + 1], outs[N + 1])
+    assert pe.sync() == 0 and pe.pair_launches == 1
+    for blk in blocks:
+        se.block(blk)
+    for o in range(O):
+        assert np.array_equal(pe.output_spectrum(o), se.output_spectrum(o)), o
+
+
 def test_pairs_need_the_switch_before_finalize(hip):
     e, _ = _crossbar(hip.Engine, 256, 2, 4, 2, 2)
     with pytest.raises(hip.BfhipError, match="after finalize"):
