@@ -181,6 +181,7 @@ def lib():
     L.bfhip_nupc_switch_busy.argtypes = [vp]
     L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
     L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -615,6 +616,11 @@ class Nupc:
 
     def set_output_gain(self, ch, gain):
         self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))
+
+    def enable_dither(self, channels, sample_rate, max_size=0):
+        """HP-TPDF dither on the listed (integer-format) outputs; before finalize"""
+        self._chk(lib().bfhip_nupc_enable_dither(self.h, _iarr(list(channels)), len(channels),
+                                                 sample_rate, max_size))
 
 
 def device_count():

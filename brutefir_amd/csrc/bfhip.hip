@@ -31,6 +31,7 @@
 #include "../../include/bfhip.h"
 #include "alloc.h"
 #include "conv_shared.h"
+#include "dither_init.h"
 #include "kernels.h"
 #include "bigfft.h"
 
@@ -2459,26 +2460,8 @@ int bfhip_engine_enable_dither(bfhip_engine *e, const int out_channels[], int n,
         if (e->fmt[1][chs[i]].isfloat) return fail(BFHIP_EINVAL, "cannot dither floating point format (output %d)", chs[i]);
     }
     // dither_init (dither.c:75-139): table spacing, Tausworthe bytes
-    int spacing = 10 * sample_rate;
-    const int minspacing = sample_rate > e->L ? sample_rate : e->L;
-    if (spacing < minspacing) spacing = minspacing;
-    if (max_size > 0 && n * spacing > max_size) spacing = max_size / n;
-    if (spacing < minspacing)
-        return fail(BFHIP_EINVAL, "Maximum dither table size %d bytes is too small, must at least be %d bytes.",
-                    max_size, n * sample_rate * minspacing);
-    e->dither_spacing = spacing;
-    e->dither_table.resize((size_t)n * spacing + 1);
-    uint32_t st[3];
-    auto lcg = [](uint32_t v) { return (uint32_t)(69069u * v); };
-    st[0] = lcg(1); st[1] = lcg(st[0]); st[2] = lcg(st[1]);
-    auto taus = [&]() {
-        st[0] = ((st[0] & 4294967294u) << 12) ^ (((st[0] << 13) ^ st[0]) >> 19);
-        st[1] = ((st[1] & 4294967288u) << 4) ^ (((st[1] << 2) ^ st[1]) >> 25);
-        st[2] = ((st[2] & 4294967280u) << 17) ^ (((st[2] << 3) ^ st[2]) >> 11);
-        return st[0] ^ st[1] ^ st[2];
-    };
-    for (int i = 0; i < 6; i++) taus();
-    for (auto &b : e->dither_table) b = (int8_t)(taus() & 0xFF);
+    const std::string msg = dither_make_table(n, sample_rate, max_size, e->L, &e->dither_spacing, &e->dither_table);
+    if (!msg.empty()) return fail(BFHIP_EINVAL, "%s", msg.c_str());
     e->dither_channels = chs;
     return BFHIP_OK;
 }
@@ -2488,29 +2471,9 @@ static int dither_upload(bfhip_engine *e) {
     if (n == 0) return BFHIP_OK;
     HIPCHK(dev_alloc((void **)&e->d_dither_ch, n * sizeof(int)));
     HIPCHK(hipMemcpy(e->d_dither_ch, e->dither_channels.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(dev_alloc((void **)&e->d_dither_table, e->dither_table.size()));
-    HIPCHK(hipMemcpy(e->d_dither_table, e->dither_table.data(), e->dither_table.size(), hipMemcpyHostToDevice));
-    // randmap[d] = 0.5 + (d + 1)/255 for d in -255..253, [-256] = -0.5, [254] = 1.5
-    // (dither.c:115-131).  The reference indexes it with int8 - int8, which can be +255: one
-    // element past its table (undefined there); defined here by continuing the formula.
-    std::vector<unsigned char> map(512 * e->rs);
-    for (int d = -256; d < 256; d++) {
-        if (e->rs == 4) {
-            float v = d == -256 ? -0.5f : (d == 254 ? 1.5f : (float)(0.5 + 1.0 / 255.0 + 1.0 / 255.0 * (float)d));
-            ((float *)map.data())[d + 256] = v;
-        } else {
-            double v = d == -256 ? -0.5 : (d == 254 ? 1.5 : 0.5 + 1.0 / 255.0 + 1.0 / 255.0 * (double)d);
-            ((double *)map.data())[d + 256] = v;
-        }
-    }
-    HIPCHK(dev_alloc(&e->d_randmap, map.size()));
-    HIPCHK(hipMemcpy(e->d_randmap, map.data(), map.size(), hipMemcpyHostToDevice));
-    // per-slot state: ptr = n*spacing + 1, error feedback zero (dither.c:133-137)
-    const size_t ssz = e->rs == 4 ? sizeof(DitherState<float>) : sizeof(DitherState<double>);
-    std::vector<unsigned char> stv(ssz * n, 0);
-    for (int i = 0; i < n; i++) *(int *)(stv.data() + ssz * i) = e->dither_rank[i] * e->dither_spacing + 1;
-    HIPCHK(dev_alloc(&e->d_dither_state, stv.size()));
-    HIPCHK(hipMemcpy(e->d_dither_state, stv.data(), stv.size(), hipMemcpyHostToDevice));
+    // table, randmap, per-slot states (ptr = rank * spacing + 1, error feedback zero)
+    HIPCHK(dither_upload_tables(e->dither_table, e->dither_spacing, e->dither_rank, e->rs, &e->d_dither_table,
+                                &e->d_randmap, &e->d_dither_state));
     return BFHIP_OK;             // d_skip_quant / d_timeout: allocated with the channel set-up in finalize
 }
 

@@ -2033,30 +2033,26 @@ __device__ __forceinline__ double lane_value(double v, int i) {
 // byte stores.  The chain itself runs on wave-uniform values fetched with v_readlane -- no
 // memory access inside it -- and lane i keeps sample i's integer.  (The first version walked
 // the samples with one lane and a table load per sample: 6 ms per 8192-sample block.)
+//
+// dither_chain is that whole pass for ONE channel, run by one wave (lane = 0..63; every lane of the
+// wave calls it, no other wave does): x = the channel's L samples in output units, `state` its
+// slot, `rmap` the 512-entry randmap already in LDS (rmap[256 + d] for d = -256..255), `over` its
+// overflow struct, `raw` the output buffer (fmt.byte_offset / sample_spacing applied here).  The
+// status bits (1 non-finite, 2 safety limit) are ORed into *status by lane 0 before it returns.
 template <typename T>
-__global__ __launch_bounds__(64) void
-dither_kernel(const T *__restrict__ samples,          // [n_out][L] from ifft_out_kernel
-              const int *__restrict__ channels,       // output channel of each dither slot
-              DitherState<T> *__restrict__ state, const int8_t *__restrict__ table, int table_size,
-              const T *__restrict__ randmap,          // index -256..255 (centre pointer)
-              const DevFormat *__restrict__ fmt, DevOverflow *__restrict__ over,
-              uint8_t *__restrict__ raw, int L, double safety_limit, int *__restrict__ status) {
-    __shared__ T rmap[512];
-    const int slot = blockIdx.x, lane = threadIdx.x;
-    const int ch = channels[slot];
-    const DevFormat f = fmt[ch];
-    const T *x = samples + (size_t)ch * L;
+__device__ __forceinline__ void
+dither_chain(const T *__restrict__ x, DitherState<T> *__restrict__ state, const int8_t *__restrict__ table,
+             int table_size, const T *rmap, const DevFormat &f, DevOverflow *__restrict__ over,
+             uint8_t *__restrict__ raw, int L, double safety_limit, int *__restrict__ status, int lane) {
     uint8_t *base = raw + f.byte_offset;
     const size_t stride = (size_t)f.sample_spacing * f.bytes;
     const int bits = f.sbytes << 3;
     const int32_t imin = (int32_t)(-((uint64_t)1 << (bits - 1)));
     const int32_t imax = (int32_t)(((uint64_t)1 << (bits - 1)) - 1);
     const T rmin = (T)imin, rmax = (T)imax;
-    for (int i = lane; i < 512; i += 64) rmap[i] = randmap[i - 256];
-    __syncthreads();
 
-    const DitherState<T> st = state[slot];
-    DevOverflow of = over[ch];
+    const DitherState<T> st = *state;
+    DevOverflow of = *over;
     int ptr = st.ptr;
     const int8_t pred = table[ptr - 1];
     if (ptr + L >= table_size) ptr = 1;                 // dither_preloop_real2int_hp_tpdf
@@ -2129,12 +2125,30 @@ dither_kernel(const T *__restrict__ samples,          // [n_out][L] from ifft_ou
         DitherState<T> out = st;
         out.ptr = ptr + L;
         out.s0 = s0; out.s1 = s1;
-        state[slot] = out;
-        over[ch].n_overflows = n_over;
-        over[ch].intlargest = intlargest;
-        over[ch].largest = largest;
+        *state = out;
+        over->n_overflows = n_over;
+        over->intlargest = intlargest;
+        over->largest = largest;
         if (flags) atomicOr(status, flags);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void
+dither_kernel(const T *__restrict__ samples,          // [n_out][L] from ifft_out_kernel
+              const int *__restrict__ channels,       // output channel of each dither slot
+              DitherState<T> *__restrict__ state, const int8_t *__restrict__ table, int table_size,
+              const T *__restrict__ randmap,          // index -256..255 (centre pointer)
+              const DevFormat *__restrict__ fmt, DevOverflow *__restrict__ over,
+              uint8_t *__restrict__ raw, int L, double safety_limit, int *__restrict__ status) {
+    __shared__ T rmap[512];
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    const int ch = channels[slot];
+    const DevFormat f = fmt[ch];
+    for (int i = lane; i < 512; i += 64) rmap[i] = randmap[i - 256];
+    __syncthreads();
+    dither_chain<T>(samples + (size_t)ch * L, state + slot, table, table_size, rmap, f, over + ch, raw, L,
+                    safety_limit, status, lane);
 }
 
 // ------------------------------------------------------------------ real-time tail

@@ -34,6 +34,7 @@
 
 #include "../../include/bfhip_nupc.h"
 #include "alloc.h"
+#include "dither_init.h"
 #include "kernels.h"
 
 using namespace bfhip;
@@ -55,13 +56,47 @@ nupc_accumulate_kernel(T *__restrict__ acc, const T *__restrict__ seg, T *__rest
     if (acc2) acc2[cell] += seg2[i];
 }
 
-// output block b: L_0 frames out of the ring, scaled into output units (output gain folded into
-// inv_scale), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114), ring
-// region cleared.  One workgroup per output channel.
-// Outside a coefficient switch (acc_new == nullptr) only the live ring is read.  Inside one,
-// acc_old holds the old assignment's output and acc_new the new one's; frame t of the block
-// (rel = t - t_sw) is old before the switch frame, new from t_sw + F on, and the linear ramp
-// (1 - w) old + w new, w = rel / (F - 1), in between; both rings' cells are cleared.
+// frame n of output block b out of the ring(s), its cells cleared.  Outside a coefficient switch
+// (acc_new == nullptr) only the live ring is read.  Inside one, acc_old holds the old assignment's
+// output and acc_new the new one's; frame t of the block (rel = t - t_sw) is old before the switch
+// frame, new from t_sw + F on, and the linear ramp (1 - w) old + w new, w = rel / (F - 1), in
+// between.
+template <typename T>
+__device__ __forceinline__ T emit_take(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos,
+                                       int A, int n_out, int ch, int n, long long rel0, int F) {
+    const size_t c = (size_t)((pos + n) % (unsigned long long)A) * n_out + ch;
+    T y = acc_old[c];
+    acc_old[c] = (T)0;
+    if (acc_new) {
+        const T y_new = acc_new[c];
+        acc_new[c] = (T)0;
+        const long long rel = rel0 + n;
+        if (rel >= F) y = y_new;
+        else if (rel >= 0) {
+            const T w = (T)((double)rel / (double)(F - 1));
+            y = ((T)1 - w) * y + w * y_new;
+        }
+    }
+    return y;
+}
+
+// thread 0 of every emit workgroup, after its channel's status bits are in *status: the last
+// channel to finish hands the status bits of all segments (they OR into the same word) to the
+// host's pinned word: no device-to-host copy after the sync
+__device__ __forceinline__ void emit_hand_off(int *__restrict__ status, unsigned int *__restrict__ arrive,
+                                              int *__restrict__ host_status) {
+    __threadfence();
+    if (atomicAdd(arrive, 1u) + 1u == gridDim.x) {
+        *arrive = 0;
+        const int all_bits = atomicExch(status, 0);
+        if (all_bits) *host_status = *host_status | all_bits;
+        __threadfence_system();
+    }
+}
+
+// output block b: L_0 frames out of the ring (emit_take), scaled into output units (output gain
+// folded into inv_scale), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114),
+// ring region cleared.  One workgroup per output channel.
 template <typename T>
 __global__ __launch_bounds__(256) void
 nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
@@ -76,36 +111,61 @@ nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long
     const T sc = (T)inv_scale[ch];
     Quantiser<T> qz;
     qz.init(f, of, safety_limit);
-    for (int n = tid; n < L0; n += 256) {
-        const size_t c = (size_t)((pos + n) % (unsigned long long)A) * n_out + ch;
-        T y = acc_old[c];
-        acc_old[c] = (T)0;
-        if (acc_new) {
-            const T y_new = acc_new[c];
-            acc_new[c] = (T)0;
-            const long long rel = rel0 + n;
-            if (rel >= F) y = y_new;
-            else if (rel >= 0) {
-                const T w = (T)((double)rel / (double)(F - 1));
-                y = ((T)1 - w) * y + w * y_new;
-            }
-        }
-        qz.put(y * sc, base + (size_t)n * stride);
-    }
+    for (int n = tid; n < L0; n += 256)
+        qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
     qz.reduce(tid, 256);
     if (tid == 0) {
         qz.commit(of);
         over[ch] = of;
         if (qz.st) atomicOr(status, qz.st);
-        // the last channel to finish hands the status bits of all segments (they OR into the
-        // same word) to the host's pinned word: no device-to-host copy after the sync
-        __threadfence();
-        if (atomicAdd(arrive, 1u) + 1u == gridDim.x) {
-            *arrive = 0;
-            const int all_bits = atomicExch(status, 0);
-            if (all_bits) *host_status = *host_status | all_bits;
-            __threadfence_system();
+        emit_hand_off(status, arrive, host_status);
+    }
+}
+
+// the emit step of a convolver with dithered outputs (launched instead of nupc_emit_kernel, same
+// grid).  A channel without a dither slot (slot[ch] < 0) is requantised exactly as there.  A
+// dithered one stages its L_0 blended, scaled reals -- the very values nupc_emit_kernel would
+// hand to the quantiser -- in stage[slot][L0], and wave 0 runs the HP-TPDF chain over them
+// (dither_chain, kernels.h: the uniform engine's dither pass).  The chain ORs its status bits in
+// before thread 0 takes part in the hand-off, so they reach the host with this block's call.
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out,
+                        int L0, long long rel0, int F, const DevFormat *__restrict__ fmt,
+                        const double *__restrict__ inv_scale, DevOverflow *__restrict__ over, uint8_t *__restrict__ raw,
+                        double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
+                        int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
+                        DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
+                        const T *__restrict__ randmap /* index -256..255 (centre pointer) */) {
+    __shared__ T rmap[512];
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const int slot = dslot[ch];
+    const DevFormat f = fmt[ch];
+    const T sc = (T)inv_scale[ch];
+    if (slot < 0) {
+        DevOverflow of = over[ch];
+        uint8_t *base = raw + f.byte_offset;
+        const size_t stride = (size_t)f.sample_spacing * f.bytes;
+        Quantiser<T> qz;
+        qz.init(f, of, safety_limit);
+        for (int n = tid; n < L0; n += 256)
+            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
+        qz.reduce(tid, 256);
+        if (tid == 0) {
+            qz.commit(of);
+            over[ch] = of;
+            if (qz.st) atomicOr(status, qz.st);
+            emit_hand_off(status, arrive, host_status);
         }
+        return;
+    }
+    T *x = stage + (size_t)slot * L0;
+    for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc;
+    for (int i = tid; i < 512; i += 256) rmap[i] = randmap[i - 256];
+    __syncthreads();                  // the staged samples are visible to wave 0 (same workgroup)
+    if (tid < 64) {
+        dither_chain<T>(x, dstate + slot, table, table_size, rmap, f, over + ch, raw, L0, safety_limit, status, tid);
+        if (tid == 0) emit_hand_off(status, arrive, host_status);
     }
 }
 
@@ -198,6 +258,16 @@ struct bfhip_nupc {
     bool gain_dirty = false;
     double *h_inv = nullptr;               // pinned staging of the per-channel factors
     hipEvent_t ev_gain = nullptr;          // the last upload out of h_inv has been done
+    // HP-TPDF dither (dither.c; bfhip_nupc_enable_dither): one slot per dithered output, in
+    // ascending channel order; the table walk advances L0 per block call
+    std::vector<int> dither_ch;            // output channel of each slot
+    std::vector<int8_t> dither_table;
+    int dither_spacing = 0;
+    int *d_dither_slot = nullptr;          // [n_out]: slot of the channel, -1 = not dithered
+    void *d_dither_state = nullptr;        // [n_dither] DitherState
+    int8_t *d_dither_table = nullptr;
+    void *d_randmap = nullptr;             // 512 reals
+    void *d_dither_stage = nullptr;        // [n_dither][L0] reals: the emit step's input to the chain
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
@@ -262,7 +332,8 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
         if (s.ev_consumed) (void)hipEventDestroy(s.ev_consumed);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
-    void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive};
+    void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive,
+                 n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage};
     for (void *q : p) if (q) (void)hipFree(q);
     if (n->h_status) (void)hipHostFree(n->h_status);
     if (n->h_in) (void)hipHostFree(n->h_in);
@@ -285,6 +356,29 @@ int bfhip_nupc_set_format(bfhip_nupc *n, int io, int ch, const bfhip_format *f) 
     if (!n || !f || io < 0 || io > 1 || ch < 0 || ch >= (io ? n->n_out : n->n_in)) return nfail(BFHIP_EINVAL, "nupc_set_format: bad argument");
     if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_format after finalize");
     n->fmt[io][ch] = *f;
+    return BFHIP_OK;
+}
+
+// dither_init for the listed outputs (bfhip_engine_enable_dither's checks; max_samples_per_loop =
+// L0): the tables are made here, uploaded at finalize
+int bfhip_nupc_enable_dither(bfhip_nupc *n, const int out_channels[], int n_ch, int sample_rate, int max_size) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_enable_dither after finalize");
+    if (!out_channels || n_ch < 1 || sample_rate < 1) return nfail(BFHIP_EINVAL, "nupc_enable_dither: bad argument");
+    std::vector<int> chs(out_channels, out_channels + n_ch);
+    for (int i = 0; i < n_ch; i++) {
+        if (chs[i] < 0 || chs[i] >= n->n_out) return nfail(BFHIP_EINVAL, "nupc_enable_dither: output channel " + std::to_string(chs[i]));
+        if (i > 0 && chs[i] <= chs[i - 1]) return nfail(BFHIP_EINVAL, "nupc_enable_dither: channels must be ascending");
+        if (n->fmt[1][chs[i]].isfloat)
+            return nfail(BFHIP_EINVAL, "cannot dither floating point format (output " + std::to_string(chs[i]) + ")");
+    }
+    int spacing = 0;
+    std::vector<int8_t> table;
+    const std::string msg = dither_make_table(n_ch, sample_rate, max_size, n->seg[0].L, &spacing, &table);
+    if (!msg.empty()) return nfail(BFHIP_EINVAL, msg);
+    n->dither_spacing = spacing;
+    n->dither_table.swap(table);
+    n->dither_ch = chs;
     return BFHIP_OK;
 }
 
@@ -419,6 +513,20 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(hipEventCreateWithFlags(&n->ev_gain, hipEventDisableTiming));
     NCHK(hipEventRecord(n->ev_gain, n->stream));
     n->gain_dirty = false;
+    if (!n->dither_ch.empty()) {
+        std::vector<int> slot(n->n_out, -1), rank(n->dither_ch.size());
+        for (size_t i = 0; i < n->dither_ch.size(); i++) {
+            if (n->fmt[1][n->dither_ch[i]].isfloat)
+                return nfail(BFHIP_EINVAL, "cannot dither floating point format (output " + std::to_string(n->dither_ch[i]) + ")");
+            slot[n->dither_ch[i]] = (int)i;
+            rank[i] = (int)i;
+        }
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_dither_slot, slot.size() * sizeof(int)));
+        NCHK(hipMemcpy(n->d_dither_slot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice));
+        NCHK(dither_upload_tables(n->dither_table, n->dither_spacing, rank, n->rs, &n->d_dither_table, &n->d_randmap,
+                                  &n->d_dither_state));
+        NCHK(bfhip_internal_dev_alloc(&n->d_dither_stage, n->dither_ch.size() * L0 * n->rs));
+    }
     for (auto &c : n->coeff) n->can_switch = n->can_switch || c.size() > 1;
     if (n->can_switch) {
         NCHK(bfhip_internal_dev_alloc((void **)&n->d_acc2, (size_t)A * n->n_out * n->rs));
@@ -609,7 +717,21 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     // inside a switch window the old assignment's ring is read beside the new one's
     void *acc_old = n->ring(n->cur), *acc_new = n->sw ? n->ring(1 - n->cur) : nullptr;
     const long long rel0 = n->sw ? (long long)opos - n->t_sw : 0;
-    if (n->rs == 4)
+    if (!n->dither_ch.empty()) {
+        const int tsz = (int)n->dither_table.size();
+        if (n->rs == 4)
+            hipLaunchKernelGGL(nupc_emit_dither_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)acc_old,
+                               (float *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
+                               n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
+                               n->d_dither_slot, (float *)n->d_dither_stage, (DitherState<float> *)n->d_dither_state,
+                               n->d_dither_table, tsz, (const float *)n->d_randmap + 256);
+        else
+            hipLaunchKernelGGL(nupc_emit_dither_kernel<double>, dim3(n->n_out), dim3(256), 0, n->stream, (double *)acc_old,
+                               (double *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
+                               n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
+                               n->d_dither_slot, (double *)n->d_dither_stage, (DitherState<double> *)n->d_dither_state,
+                               n->d_dither_table, tsz, (const double *)n->d_randmap + 256);
+    } else if (n->rs == 4)
         hipLaunchKernelGGL(nupc_emit_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)acc_old, (float *)acc_new,
                            opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
                            (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);

@@ -52,6 +52,18 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
 int bfhip_nupc_sync(bfhip_nupc *n);
 int bfhip_nupc_get_overflow(bfhip_nupc *n, int out_channel, bfhip_overflow *of);
 
+/* HP-TPDF dither (dither.c, dither_funs.h:7-69) on the listed outputs, with dither_init()'s
+   parameters, like bfhip_engine_enable_dither; before finalize (BFHIP_ESTATE after).  Channels
+   ascending and in range, integer output formats only (set the formats first), sample_rate >= 1;
+   a max_size too small for the table fails with the reference's message.  The table spacing uses
+   max_samples_per_loop = seg_length[0], and the table walk advances seg_length[0] samples per
+   block call: the output equals what the reference produces with a period of seg_length[0] frames.
+   The dither input is the value the output would be quantised from without dither (cross-fade
+   blend, output gain and 1/scale applied), so gain 0 gives dithered silence.  Non-finite and
+   safety-limit samples are skipped and reported as BFHIP_ST_* bits by the same block call.
+   Runs inside the emit step: no launch of its own. */
+int bfhip_nupc_enable_dither(bfhip_nupc *n, const int out_channels[], int n_ch, int sample_rate, int max_size);
+
 /* ---- run-time control: coefficient switches (cfc) and output gain (cfoa) ------------------
  * Filters are numbered 0, 1, ... in add_filter order.  Each filter can hold several impulse
  * responses ("sets"); set 0 is add_filter's taps.  A switch changes which set filters run.

@@ -6,7 +6,13 @@ The I/O delay of the convolver is one period of L0 frames; what has to hold for 
 is that EVERY period, including the ones in which the long segments are due, is processed in
 less than its duration.  Prints one JSON line: median / p99 / max milliseconds per
 bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, next to the
-uniform engine's block time and I/O delay for the same filters."""
+uniform engine's block time and I/O delay for the same filters.
+
+    python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither]
+
+--out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
+on both outputs (an integer --out-format is needed; sample rate 48000)."""
+import argparse
 import json
 import os
 import sys
@@ -20,8 +26,13 @@ sys.path.insert(0, ROOT)
 
 def main():
     import brutefir_amd as bf
-    L0 = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
+    ap = argparse.ArgumentParser()
+    ap.add_argument("L0", nargs="?", type=int, default=64)
+    ap.add_argument("steps", nargs="?", type=int, default=4096)
+    ap.add_argument("--out-format", default="FLOAT64_LE")
+    ap.add_argument("--dither", action="store_true")
+    a = ap.parse_args()
+    L0, steps = a.L0, a.steps
     seg_len, k = [], L0
     while k < 8192:
         seg_len.append(k)
@@ -32,7 +43,9 @@ def main():
     seg_blk.append(-(-(1048576 - covered) // 8192))
     nu = bf.Nupc(seg_len, seg_blk, 8, 2, 2)
     nu.set_interleaved(0, "FLOAT64_LE")
-    nu.set_interleaved(1, "FLOAT64_LE")
+    nu.set_interleaved(1, a.out_format)
+    if a.dither:
+        nu.enable_dither([0, 1], 48000)
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -55,6 +68,7 @@ def main():
     full = ts[[i for i in range(len(ts)) if (i + 256 + 1) % ratio == 0]]
     print(json.dumps({
         "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s" % (nu.taps, seg_len, seg_blk),
+        "out_format": a.out_format, "dithered_outputs": [0, 1] if a.dither else [],
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
