@@ -544,6 +544,9 @@ class Nupc:
             raise BfhipError(lib().bfhip_nupc_last_error().decode())
         self.L0 = lib().bfhip_nupc_latency(self.h)
         self.taps = lib().bfhip_nupc_taps(self.h)
+        # raw bytes of one L0-frame period per side: L0 frames of sample_spacing * bytes each (the
+        # library copies whole frames, gaps included)
+        self.in_bytes = n_in * self.L0 * realsize
         self.out_bytes = n_out * self.L0 * realsize
 
     def _chk(self, r):
@@ -559,12 +562,23 @@ class Nupc:
     def __del__(self):
         self.close()
 
+    def set_format(self, io, ch, fmt):
+        """every channel of a side must share one frame layout (sample_spacing and bytes; checked at
+        finalize); the period size follows the last format set on the side"""
+        self._chk(lib().bfhip_nupc_set_format(self.h, io, ch, C.byref(fmt)))
+        nbytes = self.L0 * fmt.sample_spacing * fmt.bytes
+        if io == IN:
+            self.in_bytes = nbytes
+        else:
+            self.out_bytes = nbytes
+
     def set_interleaved(self, io, name):
         n = self.n_in if io == IN else self.n_out
         for c, f in enumerate(interleaved_formats(name, n)):
-            self._chk(lib().bfhip_nupc_set_format(self.h, io, c, C.byref(f)))
-        if io == OUT:
-            self.out_bytes = n * self.L0 * SAMPLE_FORMATS[name][0]
+            self.set_format(io, c, f)
+
+    def set_safety_limit(self, v):
+        self._chk(lib().bfhip_nupc_set_safety_limit(self.h, v))
 
     def add_filter(self, in_ch, out_ch, taps, in_scale=1.0, out_scale=1.0):
         taps = np.ascontiguousarray(taps, self.dt)
@@ -573,10 +587,14 @@ class Nupc:
     def finalize(self):
         self._chk(lib().bfhip_nupc_finalize(self.h))
 
-    def block(self, rawin):
+    def block(self, rawin, overflow=None):
+        """host buffers in / out; returns (status bits, raw output bytes).  overflow: n_out
+        Overflow structs (a ctypes array), read-modify-written like Engine.block's"""
         rawin = np.ascontiguousarray(rawin).view(np.uint8).ravel()
+        assert rawin.size >= self.in_bytes, (rawin.size, self.in_bytes)
+        assert overflow is None or len(overflow) >= self.n_out
         out = np.zeros(self.out_bytes, np.uint8)
-        st = self._chk(lib().bfhip_nupc_block(self.h, _ptr(rawin), _ptr(out), None))
+        st = self._chk(lib().bfhip_nupc_block(self.h, _ptr(rawin), _ptr(out), overflow))
         return st, out
 
     def block_dev(self, rawin_dev, rawout_dev):
