@@ -137,6 +137,7 @@ def lib():
     L.bfhip_engine_uses_wave_fft.argtypes = [vp]
     L.bfhip_engine_uses_stream_layout.argtypes = [vp]
     L.bfhip_engine_uses_diag_mac.argtypes = [vp]
+    L.bfhip_engine_window_blocks.argtypes = [vp]
     L.bfhip_engine_enable_pairs.argtypes = [vp, ci]
     L.bfhip_engine_block_pair_dev.argtypes = [vp, vp, vp, vp, vp]
     L.bfhip_engine_pair_launches.argtypes = [vp]
@@ -493,6 +494,11 @@ class Engine:
     @property
     def uses_diag_mac(self):
         return bool(lib().bfhip_engine_uses_diag_mac(self.h))
+
+    @property
+    def window_blocks(self):
+        """4: the plan in force runs long-window overlap-save (4-block windows); 2: standard"""
+        return _check(lib().bfhip_engine_window_blocks(self.h))
 
     @property
     def ring_depth(self):

@@ -27,6 +27,7 @@
 #include <mutex>
 #include <set>
 #include <tuple>
+#include <type_traits>
 
 #include "../../include/bfhip.h"
 #include "alloc.h"
@@ -437,6 +438,29 @@ struct bfhip_engine {
     bool mac_diag = false;
     const int *d_diag_jobs = nullptr;      // [n_chunks * n_out_padded] entry index or -1 (lives behind d_chunks)
     double alg_bytes_total = 0, alg_bytes_mac = 0;
+    // long-window overlap-save (kernels.h: windows of 4 blocks, partitions of 3 blocks of taps).
+    // lw_struct: decided at finalize (f32, L = 8192, wave transforms, N >= 8, >= 1 GiB of coefficients in
+    // the whole configuration, or BFHIP_LONG_WINDOW=1); then the long transforms run in every block and
+    // keep the history and the long ring current.  lw_active: the plan built last covers its blocks with
+    // the long MAC (a plain uniform crossbar without fades, private rings, powersave or dither); any
+    // other block runs the standard MAC and output pass, which the standard transforms keep exact.
+    bool lw_struct = false, lw_active = false;
+    void *d_hist = nullptr;        // [n_in][R][L] real blocks
+    void *d_lring = nullptr;       // [n_in][R][2L] long window spectra
+    void *d_tw14 = nullptr;        // twiddles of the 2L-point complex transform
+    void *d_lentries = nullptr;
+    size_t lentries_cap = 0;
+    ChunkRange *d_lchunks = nullptr;
+    size_t lchunks_cap = 0;
+    int lw_chunks = 1, lw_P = 0, lw_tiles = 0, lw_Pstd = 0;     // chunks per group, long / standard partitions, bin tiles
+    StreamLayout lstream = {nullptr, 0, 0, 0};
+    void *d_lstream = nullptr;
+    size_t lstream_cap = 0;
+    StreamWhere *d_lwhere = nullptr;
+    int *d_lwhich = nullptr;
+    size_t lwhere_cap = 0;
+    std::vector<std::array<const void *, OG + 1>> lkeys;     // per long entry: its sets and (delay, length)
+    bool zp_long[3] = {false, false, false};                   // d_Zp[i] holds long partial spectra
 
     // real-time mode (bfhip_engine_rt_*): pinned host double buffer, the block's launch
     // sequence replayed from a HIP graph, completion signalled through pinned memory
@@ -810,6 +834,46 @@ void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
     *err = hipGetLastError();
 }
 
+// the long-window MAC (kernels.h): the crossbar kernel over the long entries, ring step 3
+void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
+    const int n_tc = e->lw_tiles * e->lw_chunks;
+    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
+    const unsigned long long age64 = std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
+    hipLaunchKernelGGL((mac_xbar_kernel<float, true, 0, 3>), dim3(grid), dim3(256), 0, e->ls,
+                       (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,
+                       2 * e->L, e->n_out_padded, e->n_groups, e->lw_chunks, n_tc, e->blockcounter, (int)age64,
+                       (const BlockState *)e->bs_arg, e->lstream);
+    *err = hipGetLastError();
+}
+
+// [long K3 of `count` outputs from the long partial sums Zp | long K1 of this block's inputs (inputs)]
+constexpr int LW_LOG2 = 14;        // the 4B-point real transform of B = 8192: 2^14 complex points
+void launch_io_long(bfhip_engine *e, const void *Zp, int count, uint8_t *rawout, bool inputs, hipError_t *err) {
+    constexpr int NT = fft_threads<float>(LW_LOG2);
+    const int n_in = inputs ? e->n_ch[0] : 0;
+    if (count + n_in == 0) return;
+    const size_t lds = lds_fft_bytes(LW_LOG2, sizeof(c2<float>));
+    auto k = io_long_kernel<float, LW_LOG2>;
+    *err = allow_lds(k, lds);
+    if (*err != hipSuccess) return;
+    hipLaunchKernelGGL(k, dim3(count + n_in), dim3(NT), lds, e->ls, count, (const c2<float> *)Zp,
+                       (size_t)e->n_out_padded * 2 * e->L, e->lw_chunks, 0, e->d_fmt[1], e->d_over,
+                       (const unsigned char *)e->d_skip_quant, rawout, e->safety_limit, e->d_status,
+                       (const float *)e->d_prev, (float *)e->d_hist, (c2<float> *)e->d_lring, e->R, e->blockcounter,
+                       (const c2<float> *)e->d_tw14, (const BlockState *)e->bs_arg);
+    *err = hipGetLastError();
+}
+
+// which of the engine's partial-sum buffers Zp is (-1: a caller's buffer) and whether it holds long spectra
+int zp_index(const bfhip_engine *e, const void *Zp) {
+    for (int i = 0; i < 3; i++) if (Zp != nullptr && Zp == e->d_Zp[i]) return i;
+    return -1;
+}
+bool zp_is_long(const bfhip_engine *e, const void *Zp) {
+    const int i = zp_index(e, Zp);
+    return i >= 0 && e->zp_long[i];
+}
+
 template <typename T>
 void launch_sum(bfhip_engine *e, const void *Zp, void *Z, hipError_t *err) {
     const size_t n_per_chunk = (size_t)e->n_out_padded * e->L;
@@ -1001,6 +1065,37 @@ const void *const STREAM_KEY_STALE = (const void *)(uintptr_t)1;     // never a 
 void *const PROMOTED_ELSEWHERE = (void *)(uintptr_t)1;               // promoted[] of an inactive filter: no ring here
 int coeff_make_resident(bfhip_engine *e, int ci);
 
+// long partitions [p_first, p_first + n_p) of the long entries listed in d_lwhich[0 .. n_which)
+int derive_long(bfhip_engine *e, int p_first, int n_p, int n_which) {
+    const size_t lds = lds_fft_bytes(LW_LOG2, sizeof(c2<float>));
+    auto k = coeff_long_kernel<float, LW_LOG2>;
+    HIPCHK(allow_lds(k, lds));
+    hipLaunchKernelGGL(k, dim3((unsigned)n_p, (unsigned)OG, (unsigned)n_which), dim3(fft_threads<float>(LW_LOG2)), lds,
+                       e->stream, (const MacEntry<float> *)e->d_lentries, (const StreamWhere *)e->d_lwhere,
+                       (const int *)e->d_lwhich, p_first, e->lw_Pstd, e->N, e->n_groups, e->lw_chunks, e->lstream,
+                       (const c2<float> *)e->d_tw, (const c2<float> *)e->d_tw14);
+    HIPCHK(hipGetLastError());
+    return sync_all(e);
+}
+
+// standard partition `block` of set H changed in place: long partition block / 3 of every long entry
+// that uses H (or, with no long plan in force now, forget that those entries hold H)
+int long_refresh_block(bfhip_engine *e, const void *H, int block) {
+    if (e->lkeys.empty()) return BFHIP_OK;
+    std::vector<int> hit;
+    for (size_t i = 0; i < e->lkeys.size(); i++)
+        for (int j = 0; j < OG; j++) if (e->lkeys[i][j] == H) { hit.push_back((int)i); break; }
+    if (hit.empty()) return BFHIP_OK;
+    if (!e->lw_active || e->plan_dirty || block / 3 >= e->lw_P) {
+        for (int i : hit)
+            for (int j = 0; j < OG; j++) if (e->lkeys[i][j] == H) e->lkeys[i][j] = STREAM_KEY_STALE;
+        return BFHIP_OK;
+    }
+    { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
+    HIPCHK(hipMemcpy(e->d_lwhich, hit.data(), hit.size() * sizeof(int), hipMemcpyHostToDevice));
+    return derive_long(e, block / 3, 1, (int)hit.size());
+}
+
 template <typename T>
 int build_stream_layout(bfhip_engine *e, const std::vector<MacEntry<T>> &flat, const std::vector<ChunkRange> &chunks,
                         int S, double bytes_H) {
@@ -1077,6 +1172,10 @@ int build_stream_layout(bfhip_engine *e, const std::vector<MacEntry<T>> &flat, c
 // set): bring the stream-ordered copy up to date
 template <typename T>
 int stream_refresh_block(bfhip_engine *e, const void *H, int block) {
+    if constexpr (std::is_same<T, float>::value) {
+        const int r = long_refresh_block(e, H, block);
+        if (r != BFHIP_OK) return r;
+    }
     if (e->hstream.base == nullptr || e->plan_dirty) {
         // no copy now (the plan is about to be rebuilt, or this block runs without the stream-ordered
         // copy: a cross-fade block).  The rebuild compares entries by their set POINTERS, which an
@@ -1098,6 +1197,122 @@ int stream_refresh_block(bfhip_engine *e, const void *H, int block) {
                        block, e->L, e->n_groups, e->n_chunks, e->hstream);
     HIPCHK(hipGetLastError());
     return sync_all(e);
+}
+
+// The long-window plan for a plain uniform crossbar: the standard plan's entries with the long rings
+// (ring step 3 in the MAC), chunks of lw_chunks per group, and the long coefficient partitions derived
+// from the sets' standard spectra straight into their own stream-ordered layout (StreamLayout; only the
+// entries whose sets, delay or length changed since the last build).  Anything else: lw_active = false
+// and every block runs the standard path.
+// what build_plan_t found on the whole configuration's entries: a plain uniform crossbar (ok), its
+// entries per group (E) and partitions (P), and the whole-plan position of every entry of `flat`
+struct LongWhole { bool ok = false; int E = 0, P = 0; std::vector<int> wpos; };
+int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat, const std::vector<ChunkRange> &chunks, int S,
+                      const LongWhole &lwh) {
+    e->lw_active = false;
+    if (!lwh.ok || flat.empty() || e->mac_diag || !e->mac_nt || e->mac_unroll != 0 || e->mac_threads != 256)
+        return BFHIP_OK;
+    const size_t L = e->L, LL = 2 * L;
+    const c2<float> *ring0 = (const c2<float> *)e->d_ring;
+    // (a filter delayed by d blocks uses min(P, N - d) partitions: what the derivation cuts, coeff_long_kernel)
+    const int P = lwh.P;
+    int SL = 1;
+    if (const char *env = getenv("BFHIP_LONG_CHUNKS")) SL = std::max(1, atoi(env));
+    if (lwh.E % SL != 0) return BFHIP_OK;
+    // long chunk c of a group = the whole plan's entries [c E_c, (c + 1) E_c) of it (those of them this
+    // engine runs: a shard's entries keep their whole-plan order, its chunks may be shorter)
+    const int E_c = lwh.E / SL, PL = (P + 2) / 3;
+    std::vector<ChunkRange> lchunks((size_t)e->n_groups * SL);
+    int E_here = 1;
+    for (int g = 0; g < e->n_groups; g++) {
+        int idx = chunks[(size_t)g * S].begin;
+        const int end = chunks[(size_t)g * S + S - 1].end;
+        for (int c = 0; c < SL; c++) {
+            ChunkRange cr{idx, idx};
+            while (idx < end && lwh.wpos[idx] / E_c == c) idx++;
+            cr.end = idx;
+            lchunks[(size_t)g * SL + c] = cr;
+            E_here = std::max(E_here, cr.end - cr.begin);
+        }
+        if (idx != end) return BFHIP_OK;
+    }
+    const int tiles = (int)(LL * sizeof(c2<float>) / 4096u);
+    const int n_tc = tiles * SL;
+    if (n_tc % 8 != 0) return BFHIP_OK;
+    const unsigned int chunk = 256u * 16u;
+    const unsigned long long entry_bytes = (unsigned long long)PL * OG * chunk;
+    const unsigned long long slice = (unsigned long long)E_here * entry_bytes;
+    if (entry_bytes >= (1ull << 31) || slice >= (1ull << 32)) return BFHIP_OK;
+    const size_t total = (size_t)((unsigned long long)n_tc * e->n_groups * slice);
+    const bool same_geom = e->d_lstream != nullptr && e->lw_chunks == SL && e->lw_P == PL && e->lkeys.size() == flat.size() &&
+                           e->lstream.slice == slice;
+    if (!same_geom) {
+        if (total > e->lstream_cap) {
+            if (e->d_lstream) (void)hipFree(e->d_lstream);
+            e->d_lstream = nullptr; e->lstream_cap = 0;
+            if (dev_alloc(&e->d_lstream, total) != hipSuccess) {
+                (void)hipGetLastError();
+                return BFHIP_OK;                 // no room for the long copy: the standard path
+            }
+            e->lstream_cap = total;
+        }
+        e->lkeys.assign(flat.size(), std::array<const void *, OG + 1>{});
+    }
+    // the long entries, and which of them hold other sets (or another delay / length) than last time
+    std::vector<MacEntry<float>> lflat(flat);
+    std::vector<StreamWhere> where(flat.size());
+    std::vector<int> changed;
+    for (int g = 0; g < e->n_groups; g++)
+        for (int c = 0; c < SL; c++) {
+            const ChunkRange cr = lchunks[(size_t)g * SL + c];
+            for (int q = 0; q < cr.end - cr.begin; q++) {
+                const int idx = cr.begin + q;
+                MacEntry<float> &en = lflat[idx];
+                const size_t in = (size_t)(en.ring - ring0) / (e->R * L);
+                en.ring = (const c2<float> *)e->d_lring + in * e->R * LL;
+                en.shift = 3 * ((en.maxP + 2) / 3) - en.maxP;     // the last partition's (kernels.h)
+                en.maxP = (en.maxP + 2) / 3;
+                where[idx] = StreamWhere{g, c, q, 0};
+                std::array<const void *, OG + 1> key;
+                for (int j = 0; j < OG; j++) key[j] = en.term[j].H;
+                key[OG] = (const void *)(uintptr_t)(((size_t)(unsigned)en.delay << 32) | (unsigned)P);
+                if (key != e->lkeys[idx]) { changed.push_back(idx); e->lkeys[idx] = key; }
+            }
+        }
+    const size_t eb = lflat.size() * sizeof(MacEntry<float>), cb = lchunks.size() * sizeof(ChunkRange);
+    if (eb > e->lentries_cap) {
+        if (e->d_lentries) (void)hipFree(e->d_lentries);
+        e->d_lentries = nullptr; e->lentries_cap = 0;
+        HIPCHK(dev_alloc(&e->d_lentries, eb));
+        e->lentries_cap = eb;
+    }
+    if (cb > e->lchunks_cap) {
+        if (e->d_lchunks) (void)hipFree(e->d_lchunks);
+        e->d_lchunks = nullptr; e->lchunks_cap = 0;
+        HIPCHK(dev_alloc((void **)&e->d_lchunks, cb));
+        e->lchunks_cap = cb;
+    }
+    const size_t wb = where.size() * sizeof(StreamWhere), ib = flat.size() * sizeof(int);
+    if (wb + ib > e->lwhere_cap) {
+        if (e->d_lwhere) (void)hipFree(e->d_lwhere);
+        e->d_lwhere = nullptr; e->lwhere_cap = 0;
+        HIPCHK(dev_alloc((void **)&e->d_lwhere, wb + ib));
+        e->lwhere_cap = wb + ib;
+    }
+    e->d_lwhich = (int *)((unsigned char *)e->d_lwhere + wb);
+    { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
+    HIPCHK(hipMemcpy(e->d_lentries, lflat.data(), eb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_lchunks, lchunks.data(), cb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_lwhere, where.data(), wb, hipMemcpyHostToDevice));
+    e->lw_chunks = SL; e->lw_P = PL; e->lw_tiles = tiles; e->lw_Pstd = P;
+    e->lstream = StreamLayout{(const unsigned char *)e->d_lstream, slice, (unsigned int)entry_bytes, chunk};
+    if (!changed.empty()) {
+        HIPCHK(hipMemcpy(e->d_lwhich, changed.data(), changed.size() * sizeof(int), hipMemcpyHostToDevice));
+        const int r = derive_long(e, 0, PL, (int)changed.size());
+        if (r != BFHIP_OK) { e->lkeys.clear(); return r; }
+    }
+    e->lw_active = true;
+    return BFHIP_OK;
 }
 
 template <typename T>
@@ -1137,6 +1352,7 @@ int build_plan_t(bfhip_engine *e) {
     }
     // which terms belong to filters another engine runs: [group][entry] bit j
     std::vector<std::vector<unsigned int>> foreign(e->n_groups);
+    bool lw_plain = true;              // no filter mixes, cascades, fades or has a ring of its own
     double bytes_H_plan = 0;           // the whole configuration's: what the launch geometry is chosen for
 
     for (int fi = 0; fi < F; fi++) {
@@ -1152,6 +1368,7 @@ int build_plan_t(bfhip_engine *e) {
         const bool fading = f.crossfade && f.prevcoeff != f.coeff;
         const bool needY = e->is_source[fi] || fading;
         if (fading && f.active) e->any_fading = true;
+        if (owner || owner_kind || needY) lw_plain = false;        // (every engine sees every filter's state)
         if (f.active && needY && e->y_index[fi] < 0) return fail(BFHIP_ESTATE, "filter %d: no output buffer reserved", fi);
 
         // where this filter's history lives and how to index it
@@ -1417,6 +1634,26 @@ int build_plan_t(bfhip_engine *e) {
     // chunk boundaries from the WHOLE plan; then the terms of filters another engine runs are taken
     // out (an entry's path -- crossbar, single term, generic -- stays the one the whole plan gave it:
     // the single-term path rounds differently from the others), entries left empty are dropped
+    // Whether the long-window plan (kernels.h) can take this plan is decided on the WHOLE configuration's
+    // entries, before foreign terms are taken out: a shard then runs the plan the one-process engine runs,
+    // and every output is summed in the same order (the subset path rounds like the crossbar path).
+    LongWhole lwh;
+    lwh.ok = e->lw_struct && lw_plain;
+    for (int g = 0; g < e->n_groups && lwh.ok; g++) {
+        const auto &v = per_group[g];
+        if (g == 0) lwh.E = (int)v.size();
+        if ((int)v.size() != lwh.E || v.empty()) lwh.ok = false;
+        for (auto &en : v) lwh.P = std::max(lwh.P, en.maxP);
+    }
+    for (int g = 0; g < e->n_groups && lwh.ok; g++)
+        for (auto &en : per_group[g]) {
+            const ptrdiff_t off = (const c2<T> *)en.ring - (const c2<T> *)e->d_ring;
+            bool ok = en.dense == 1 && en.p0 == 0 && en.maxP >= 1 && en.maxP == std::min(lwh.P, e->N - en.delay) &&
+                      en.live == nullptr && en.R == e->R && en.ring != nullptr && off >= 0 &&
+                      off % (ptrdiff_t)(e->R * L) == 0 && off / (ptrdiff_t)(e->R * L) < I;
+            for (int j = 0; j < OG && ok; j++) ok = en.term[j].kind == TERM_COEFF;
+            if (!ok) { lwh.ok = false; break; }
+        }
     std::vector<MacEntry<T>> flat;
     std::vector<ChunkRange> chunks((size_t)e->n_groups * S);
     for (int g = 0; g < e->n_groups; g++) {
@@ -1447,6 +1684,7 @@ int build_plan_t(bfhip_engine *e) {
                         if (fm & (1u << q)) { en.term[q].kind = TERM_NONE; en.term[q].H = nullptr; }
                 }
                 flat.push_back(en);
+                lwh.wpos.push_back((int)pos - 1);
             }
             cr.end = (int)flat.size();
             chunks[(size_t)g * S + c] = cr;
@@ -1527,10 +1765,17 @@ int build_plan_t(bfhip_engine *e) {
         const int r = build_stream_layout<T>(e, flat, chunks, S, bytes_H);
         if (r != BFHIP_OK) return r;
     }
-    const size_t zb = (size_t)S * e->n_out_padded * L * sizeof(c2<T>);
+    e->lw_active = false;
+    if constexpr (std::is_same<T, float>::value) {
+        const int r = build_long_layout(e, flat, chunks, S, lwh);
+        if (r != BFHIP_OK) return r;
+    }
+    size_t zb = (size_t)S * e->n_out_padded * L * sizeof(c2<T>);
+    if (e->lw_active) zb = std::max(zb, (size_t)e->lw_chunks * e->n_out_padded * 2 * L * sizeof(c2<T>));
     if (zb > e->zp_bytes) {
         for (void *&z : e->d_Zp) { if (z) (void)hipFree(z); z = nullptr; }
         for (int i = 0; i < zp_depth(e); i++) HIPCHK(dev_alloc(&e->d_Zp[i], zb));
+        for (bool &z : e->zp_long) z = false;
         e->zp_bytes = zb;
         e->zp_last = 0;
     }
@@ -1899,6 +2144,8 @@ int do_inputs(bfhip_engine *e, const void *rawin_dev, unsigned int ahead = 0u /*
     else if (e->wave) { DISPATCH_WAVE(launch_fft_in_wave, e, (const uint8_t *)rawin_dev, slot, &err) }
     else DISPATCH(launch_fft_in, e, (const uint8_t *)rawin_dev, slot, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "fft_in launch: %s", hipGetErrorString(err));
+    if (e->lw_struct) launch_io_long(e, nullptr, 0, nullptr, true, &err);       // behind it: it reads prev
+    if (err != hipSuccess) return fail(BFHIP_EHIP, "long fft_in launch: %s", hipGetErrorString(err));
     return BFHIP_OK;
 }
 
@@ -1920,10 +2167,16 @@ int do_levels(bfhip_engine *e) {
     return record_end(e, T_LEVELS);
 }
 
-int do_mac(bfhip_engine *e, void *Zp) {
+int do_mac(bfhip_engine *e, void *Zp, bool may_long = true) {
     hipError_t err = hipSuccess;
     e->zp_is_sum = false;
-    if (e->rs == 4) launch_mac<float>(e, Zp, &err); else launch_mac<double>(e, Zp, &err);
+    // the long plan covers blocks whose partial sums stay in the engine's own buffers and are converted
+    // by its own output pass (not the phase calls, which hand standard spectra to the caller)
+    const int zi = zp_index(e, Zp);
+    const bool lng = e->lw_active && zi >= 0 && may_long;
+    if (zi >= 0) e->zp_long[zi] = lng;
+    if (lng) launch_mac_long(e, Zp, &err);
+    else if (e->rs == 4) launch_mac<float>(e, Zp, &err); else launch_mac<double>(e, Zp, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "mac launch: %s", hipGetErrorString(err));
     return BFHIP_OK;
 }
@@ -1942,7 +2195,10 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
     if (count <= 0) return BFHIP_OK;
     if (!e->vout_groups.empty() && (first != 0 || count != e->n_ch[1]))
         return fail(BFHIP_EINVAL, "outputs that share a physical channel cannot be split over several calls");
-    if (n_chunks > 2 && n_chunks == e->n_chunks && first == 0 && count == e->n_ch[1] &&
+    const bool lng = zp_is_long(e, Zp);
+    if (lng && (first != 0 || count != e->n_ch[1]))
+        return fail(BFHIP_EINVAL, "a long-window block's outputs are converted all at once");
+    if (!lng && n_chunks > 2 && n_chunks == e->n_chunks && first == 0 && count == e->n_ch[1] &&
         chunk_stride == (size_t)e->n_out_padded * e->L) {
         // many partials (few long filters): the one-workgroup-per-channel output pass would walk
         // them one dependent load after the other; add them up with the whole chip first
@@ -1956,7 +2212,8 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
     // what follows the inverse transforms as launches of its own (dither chains, N:1 mix, sub-sample
     // delay) is timed apart: the reference's real2raw column
     const bool post = !e->dither_channels.empty() || !e->vout_groups.empty() || side_uses_subdelay(e, 1);
-    if (e->big) DISPATCH_BIG(launch_ifft_out_big, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
+    if (lng) launch_io_long(e, Zp, count, (uint8_t *)rawout_dev, false, &err);
+    else if (e->big) DISPATCH_BIG(launch_ifft_out_big, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
     else if (e->wave) { DISPATCH_WAVE(launch_ifft_out_wave, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err) }
     else DISPATCH(launch_ifft_out, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "ifft_out launch: %s", hipGetErrorString(err));
@@ -1977,9 +2234,16 @@ int fused_outputs_inputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, i
     if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
     hipError_t err = hipSuccess;
     const int slot = (int)(e->blockcounter % (unsigned int)e->R);
-    if (e->wave) { DISPATCH_WAVE(launch_io_wave, e, Zp, chunk_stride, n_chunks, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err) }
-    else DISPATCH(launch_io, e, Zp, first, count, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err);   // (one chunk)
+    // an owed long-window block: its output pass rides with the long transforms of this block instead
+    const bool lng = zp_is_long(e, Zp);
+    if (lng && (first != 0 || count != e->n_ch[1]))
+        return fail(BFHIP_EINVAL, "a long-window block's outputs are converted all at once");
+    const int n_std = lng ? 0 : count;
+    if (e->wave) { DISPATCH_WAVE(launch_io_wave, e, Zp, chunk_stride, n_chunks, first, n_std, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err) }
+    else DISPATCH(launch_io, e, Zp, first, n_std, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err);   // (one chunk)
     if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
+    if (e->lw_struct) launch_io_long(e, Zp, lng ? count : 0, k3_target(e, rawout_dev), true, &err);
+    if (err != hipSuccess) return fail(BFHIP_EHIP, "long io launch: %s", hipGetErrorString(err));
     return post_outputs(e, rawout_dev, first, count);
 }
 
@@ -2360,7 +2624,8 @@ void bfhip_engine_destroy(bfhip_engine *e) {
                     e->d_dither_ch, e->d_dither_state, e->d_dither_table, e->d_randmap, e->d_skip_quant, e->d_timeout,
                     e->d_big[0], e->d_big[1], e->d_big[2], e->d_tw13, e->d_tww,
                     e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc, e->d_stream, e->d_where,
-                    e->d_planar[0], e->d_planar[1], e->d_phys_skip};
+                    e->d_planar[0], e->d_planar[1], e->d_phys_skip,
+                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto ev : e->ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -3189,6 +3454,31 @@ static int finalize_impl(bfhip_engine *e) {
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     HIPCHK(hipMemcpy(&bad, e->d_bad, sizeof(int), hipMemcpyDeviceToHost));
     if (bad) return fail(BFHIP_EINVAL, "NaN or Inf value among coefficients.");
+    {
+        // long-window plan: structure here, the per-plan conditions in build_long_layout.  The size test
+        // is on every set registered -- the whole configuration's, not a shard's share: a shard
+        // engine takes the long plan exactly when the one-process engine does (build_plan_t)
+        int want = -1;
+        if (const char *env = getenv("BFHIP_LONG_WINDOW")) want = atoi(env) != 0 ? 1 : 0;
+        double vol = 0;
+        for (auto &c : e->coeffs) vol += (double)c.n_blocks * (double)L * (double)e->csize();
+        // (what the configuration fixes for good -- powersave, dither, wide / shared / sub-sample outputs --
+        // is settled here: such an engine never runs the long transforms)
+        e->lw_struct = want != 0 && e->rs == 4 && e->L == 8192 && e->wave && !e->big && e->N >= 8 && !e->pairs &&
+                       e->powersave <= 0.0 && e->dither_channels.empty() && !e->wide[1] && e->vout_groups.empty() &&
+                       !side_uses_subdelay(e, 1) && (want == 1 || vol >= 1073741824.0);
+        if (e->lw_struct) {
+            const size_t hist_b = (size_t)e->n_ch[0] * e->R * L * sizeof(float);
+            const size_t lring_b = (size_t)e->n_ch[0] * e->R * 2 * L * sizeof(c2<float>);
+            const std::vector<unsigned char> tw = make_twiddle_table(LW_LOG2, 4, fft_threads<float>(LW_LOG2), true);
+            if (dev_alloc(&e->d_hist, hist_b) != hipSuccess || dev_alloc(&e->d_lring, lring_b) != hipSuccess ||
+                dev_alloc(&e->d_tw14, tw.size()) != hipSuccess)
+                return fail(BFHIP_ENOMEM, "out of device memory for the long-window rings");
+            HIPCHK(hipMemset(e->d_hist, 0, hist_b));
+            HIPCHK(hipMemset(e->d_lring, 0, lring_b));
+            HIPCHK(hipMemcpy(e->d_tw14, tw.data(), tw.size(), hipMemcpyHostToDevice));
+        }
+    }
     return build_plan(e);
 }
 
@@ -3268,11 +3558,27 @@ int bfhip_engine_set_fscale(bfhip_engine *e, int filter, int index, double scale
     return BFHIP_OK;
 }
 
+// The phase calls (a host that mixes partial spectra of several engines, bench.py --gpus N) hand
+// standard spectra to the caller: an engine driven through them runs the standard plan only, and
+// from its first phase call on no longer pays for the long transforms or keeps their memory.
+static int lw_drop(bfhip_engine *e) {
+    if (!e->lw_struct) return BFHIP_OK;
+    { const int r = sync_all(e); if (r != BFHIP_OK) return r; }
+    e->lw_struct = e->lw_active = false;
+    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    e->lstream_cap = 0;
+    e->lstream = StreamLayout{nullptr, 0, 0, 0};
+    e->lkeys.clear();
+    for (bool &z : e->zp_long) z = false;
+    return BFHIP_OK;
+}
+
 int bfhip_engine_inputs_dev(bfhip_engine *e, const void *rawin_dev) {
     int r = ensure_ready(e);
     if (r != BFHIP_OK) return r;
     if (!rawin_dev) return fail(BFHIP_EINVAL, "inputs: null buffer");
     if ((r = flush_pending(e)) != BFHIP_OK) return r;
+    if ((r = lw_drop(e)) != BFHIP_OK) return r;
     e->ls = e->stream;
     timing_begin(e);
     return block_inputs(e, rawin_dev);
@@ -3283,12 +3589,13 @@ int bfhip_engine_mac_dev(bfhip_engine *e, void *z_dev) {
     if (r != BFHIP_OK) return r;
     if (!z_dev) return fail(BFHIP_EINVAL, "mac: null buffer");
     if ((r = flush_pending(e)) != BFHIP_OK) return r;      // an output owed by bfhip_engine_block_dev goes first
+    if ((r = lw_drop(e)) != BFHIP_OK) return r;
     e->ls = e->stream;
     timing_begin(e);
     if ((r = do_levels(e)) != BFHIP_OK) return r;
     if ((r = record_begin(e, T_MAC)) != BFHIP_OK) return r;
     const bool direct = e->n_chunks == 1 && e->n_out_padded == e->n_ch[1];
-    if ((r = do_mac(e, direct ? z_dev : e->d_Zp[0])) != BFHIP_OK) return r;
+    if ((r = do_mac(e, direct ? z_dev : e->d_Zp[0], false)) != BFHIP_OK) return r;
     e->zp_last = 0;
     if ((r = record_end(e, T_MAC)) != BFHIP_OK) return r;
     return direct ? BFHIP_OK : sum_chunks(e, e->d_Zp[0], z_dev);
@@ -3298,6 +3605,7 @@ int bfhip_engine_outputs_dev(bfhip_engine *e, const void *z_dev, int first, int 
     int r = ensure_ready(e);
     if (r != BFHIP_OK) return r;
     if ((r = flush_pending(e)) != BFHIP_OK) return r;      // an output owed by bfhip_engine_block_dev goes first
+    if ((r = lw_drop(e)) != BFHIP_OK) return r;
     if (first < 0 || count < 0 || first + count > e->n_ch[1]) return fail(BFHIP_EINVAL, "outputs: channel range");
     if (!z_dev || !rawout_dev) return fail(BFHIP_EINVAL, "outputs: null buffer");
     e->ls = e->stream;
@@ -3312,6 +3620,7 @@ int bfhip_engine_outputs_inputs_dev(bfhip_engine *e, const void *z_dev, int firs
     int r = ensure_ready(e);
     if (r != BFHIP_OK) return r;
     if ((r = flush_pending(e)) != BFHIP_OK) return r;      // an output owed by bfhip_engine_block_dev goes first
+    if ((r = lw_drop(e)) != BFHIP_OK) return r;
     if (first < 0 || count < 0 || first + count > e->n_ch[1]) return fail(BFHIP_EINVAL, "outputs: channel range");
     if (!z_dev || !rawout_dev || !rawin_dev) return fail(BFHIP_EINVAL, "outputs_inputs: null buffer");
     if (!e->dither_channels.empty() || e->has_vchan || count == 0 || e->big) {
@@ -3393,7 +3702,7 @@ static int block_owed(bfhip_engine *e, const void *rawin_dev, void *rawout_dev,
     if ((r = block_mac(e, zi)) != BFHIP_OK) return r;
     bfhip_engine::Pending np;
     np.Zp = e->d_Zp[zi]; np.chunk_stride = (size_t)e->n_out_padded * e->L; np.n_chunks = e->n_chunks;
-    if (e->n_chunks > 2) {
+    if (e->n_chunks > 2 && !e->zp_long[zi]) {
         // many partials (few outputs, many inputs: an output-sharded rank; few long filters): add them
         // up with the whole chip here, in place, same order -- the fused launch that owes this block's
         // output then reads one spectrum per channel (and exists: it takes at most two)
@@ -3821,6 +4130,10 @@ int bfhip_engine_block_mode(const bfhip_engine *e) {
 int bfhip_engine_uses_wave_fft(const bfhip_engine *e) { return e && e->wave ? 1 : 0; }
 int bfhip_engine_uses_stream_layout(const bfhip_engine *e) { return e && e->hstream.base ? 1 : 0; }
 int bfhip_engine_uses_diag_mac(const bfhip_engine *e) { return e && e->mac_diag ? 1 : 0; }
+int bfhip_engine_window_blocks(const bfhip_engine *e) {
+    if (!e) return fail(BFHIP_EINVAL, "window_blocks: null engine");
+    return e->lw_active ? 4 : 2;
+}
 int bfhip_engine_ring_depth(const bfhip_engine *e) { return e ? e->R : 0; }
 
 int bfhip_engine_enable_timing(bfhip_engine *e, int on) {
@@ -3908,6 +4221,9 @@ int bfhip_engine_read_output_spectrum(bfhip_engine *e, int ch, void *dst) {
     { const int ro = check_owner(e); if (ro != BFHIP_OK) return ro; }
     HIPCHK(hipSetDevice(e->device));
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
+    if (e->zp_long[e->zp_last])
+        return fail(BFHIP_ESTATE, "read_output_spectrum: the last block ran the long-window plan, whose output spectra "
+                    "have 2L bins of a 4L-point transform; set BFHIP_LONG_WINDOW=0 to read standard spectra");
     const size_t row = (size_t)e->L * e->csize();
     std::vector<unsigned char> tmp(row);
     memset(dst, 0, row);

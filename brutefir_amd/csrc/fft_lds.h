@@ -111,7 +111,9 @@ constexpr int tw_total(int log2l, int nt, int log2ns) {
 // them -- still one coalesced load per value.
 template <typename T, int LOG2L, int NT, bool FORCE_LAZY = false> struct TwRegs {
     // FORCE_LAZY: kernels that run several transforms and keep other state across them
-    static constexpr bool LAZY = FORCE_LAZY || (size_t)tw_total(LOG2L, NT, 0) * sizeof(c2<T>) > 256;     // > 64 VGPRs
+    // (> 64 VGPRs; or 2^14 points at 1024 threads -- the long-window transforms -- where the
+    // 128 VGPRs a thread has are needed for the data)
+    static constexpr bool LAZY = FORCE_LAZY || LOG2L > 13 || (size_t)tw_total(LOG2L, NT, 0) * sizeof(c2<T>) > 256;
     static constexpr int N = (LAZY || tw_total(LOG2L, NT, 0) == 0) ? 1 : tw_total(LOG2L, NT, 0);
     c2<T> r[N];
     const c2<T> *g;                 // thread-ordered table, this thread's column
@@ -209,10 +211,11 @@ __device__ __forceinline__ void lds_fft(LdsArr<T> s, const TW &tw) {
 
 // Host: the table TwRegs::prefetch and the real-transform (un)tangling read, for the NT the
 // kernels of this precision use.  Values are computed in double and rounded once.
-inline std::vector<unsigned char> make_twiddle_table(int log2l, int realsize, int nt) {
+inline std::vector<unsigned char> make_twiddle_table(int log2l, int realsize, int nt, bool in_lds = false) {
     const size_t L = (size_t)1 << log2l;
-    // lengths above the LDS limit (bigfft.h) only use the base table
-    const size_t n_regs = log2l > 13 ? 0 : (size_t)tw_total(log2l, nt, 0);
+    // lengths above the LDS limit (bigfft.h) only use the base table; in_lds: a float transform of
+    // 2^14 points that does fit one workgroup's LDS (the long-window transforms, kernels.h)
+    const size_t n_regs = (log2l > 13 && !in_lds) ? 0 : (size_t)tw_total(log2l, nt, 0);
     const size_t total = 2 * L + n_regs * (size_t)nt;
     std::vector<unsigned char> out(total * 2 * (size_t)realsize);
     auto put = [&](size_t idx, size_t m) {

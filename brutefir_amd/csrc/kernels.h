@@ -58,6 +58,9 @@ template <typename T> struct MacEntry {
                         // 16: the same for the subset `mask` of the terms, the rest empty;
                         // 2 + j: term j is the only one; 0: generic per-term path
     int mask;           // dense == 16: bit j set = term j is active
+    int shift;          // long-window entries (ring step 3): how many blocks later the last partition's
+                        // window ends (0 in standard entries)
+    int pad;
     const int *live;    // powersave: how many of the ring's slots hold a non-silent block (null: n/a)
     MacTerm<T> term[OG];
 };
@@ -660,7 +663,7 @@ __device__ __forceinline__ void cmac(T &re, T &im, T xr, T xi, c2<T> h) {
 // need the same ring tile get the same blockIdx%8 (one XCD, adjacent dispatch) so that the
 // ring re-reads hit that XCD's L2.  Partial sums of the chunks go to Zp[chunk][o][k] and
 // are added up by the consumer (K3 or sum_partials_kernel): deterministic, no atomics.
-template <typename T, bool NT, int UNROLL = 2>
+template <typename T, bool NT, int UNROLL = 2, int PSTEP = 1>
 __global__ __launch_bounds__(256) void
 mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__restrict__ chunks,
                 c2<T> *__restrict__ Zp, int L, int n_out_padded, int n_groups, int n_chunks,
@@ -692,7 +695,16 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
         const int R = E->R, delay = E->delay;
         const int p0 = E->p0;
         int maxP = E->maxP;
-        if (maxP > age - delay) maxP = age - delay;     // blocks that exist yet (procblocks)
+        // long entries: the last partition holds the filter's last 3 standard partitions (taps
+        // that belong to the one before it are zeros there), its window ends `shift` blocks later
+        const int lastP = maxP - 1, shift = PSTEP == 1 ? 0 : E->shift;
+        if constexpr (PSTEP == 1) {
+            if (maxP > age - delay) maxP = age - delay;     // blocks that exist yet (procblocks)
+        } else {
+            // a long partition p reaches back to block t - PSTEP*p - delay: it exists for p < ceil((age - delay) / PSTEP)
+            const int avail = age - delay > 0 ? (age - delay + PSTEP - 1) / PSTEP : 0;
+            if (maxP > avail) maxP = avail;
+        }
         // powersave (bfrun.c:1541-1553, 1694-1770): every block this input still has in its ring
         // is silence -> nothing to add, nothing to read
         if (E->live != nullptr && *E->live == 0) continue;
@@ -721,9 +733,9 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             if (mask != 0xffu) {
 #pragma unroll 2
                 for (int p = p0; p < maxP; p++) {
-                    const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+                    const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                     const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                    const unsigned int hoff = ((unsigned int)p * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+                    const unsigned int hoff = (unsigned int)p * hstep + hlane;     // set-major: (p * L + k0) * sizeof
                     c2<T> x[V], h[OG][V];
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), x);
 #pragma unroll
@@ -750,7 +762,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
                 // the memory pipe never drains inside an entry.
                 struct Stage { c2<T> x[V]; c2<T> h[OG][V]; };
                 auto issue = [&](Stage &st, int p) {
-                    const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+                    const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                     const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
                     const unsigned int hoff = (unsigned int)p * hstep + hlane;
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), st.x);
@@ -794,7 +806,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             for (int p = p0; p < maxP; p++) {
                 // byte offsets kept in 32 bits (N * L * 16 < 4 GiB) so that the loads take the
                 // scalar-base + 32-bit lane-offset form
-                const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+                const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                 const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
                 const unsigned int hoff = ((unsigned int)p * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
                 c2<T> x[V], h[OG][V];
@@ -827,7 +839,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             for (int v = 0; v < 2 * V; v++) ta[v] = (T)0;
 #pragma unroll 4
             for (int p = p0; p < maxP; p++) {
-                const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+                const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                 const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
                 const unsigned int hoff = ((unsigned int)p * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
                 c2<T> x[V], h[V];
@@ -851,7 +863,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             continue;
         }
         for (int p = p0; p < maxP; p++) {
-            const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+            const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
             c2<T> x[V];
             {
                 const c2<T> *xp = ring + (size_t)slot * L + k0;
@@ -1514,7 +1526,7 @@ template <typename T> struct Quantiser {
 // float store, peak + overflow accounting, strided interleaved write.
 // `timeout` (may be NULL): if given, the samples are ALSO stored there as T [count][L]
 // (used by the dither pass and by debug taps).
-template <typename T, int LOG2L, int NTP = fft_threads<T>(LOG2L)>
+template <typename T, int LOG2L, int NTP = fft_threads<T>(LOG2L), int NOUT = (1 << LOG2L)>
 __device__ __forceinline__ void
 ifft_out_body(int zi /* index into Zp's channel axis */, unsigned char *smem,
               const c2<T> *__restrict__ Zp, size_t chunk_stride, int n_chunks,
@@ -1542,7 +1554,7 @@ ifft_out_body(int zi /* index into Zp's channel axis */, unsigned char *smem,
     if (tid == 0) z0 = z[0];
     // the second chunk rides along only where the registers allow it (8 bins per thread in
     // float64 at L = 8192 would spill)
-    constexpr bool PRELOAD2 = QU * sizeof(c2<T>) <= 64;
+    constexpr bool PRELOAD2 = QU * sizeof(c2<T>) <= 64 && NOUT == L;
     if (PRELOAD2 && n_chunks > 1) {
         const c2<T> *zc = z + chunk_stride;
 #pragma unroll
@@ -1595,12 +1607,12 @@ ifft_out_body(int zi /* index into Zp's channel axis */, unsigned char *smem,
     Quantiser<T> qz;
     qz.init(f, of, safety_limit);
 
-    for (int n = tid; n < L / 2; n += NT) {
+    for (int n = tid; n < NOUT / 2; n += NT) {
         const c2<T> zz = s[n];
         T xs[2] = {zz.x, zz.y};
         if (timeout != nullptr) {
-            timeout[(size_t)zi * L + 2 * n] = xs[0];
-            timeout[(size_t)zi * L + 2 * n + 1] = xs[1];
+            timeout[(size_t)zi * NOUT + 2 * n] = xs[0];
+            timeout[(size_t)zi * NOUT + 2 * n + 1] = xs[1];
         }
         if (!quant) continue;
 #pragma unroll
@@ -1851,6 +1863,182 @@ io_kernel(int n_k3,
                                 rawout, timeout, tw, safety_limit, status);
     else
         fft_in_body<T, LOG2L>(xcd_channel((int)blockIdx.x - n_k3, (int)gridDim.x - n_k3), smem, rawin, fmt_in, prev, ring, tw, R, slot, ps);
+}
+
+// ------------------------------------------------------------------ long-window overlap-save (4 blocks)
+// Uniform f32 crossbars with B = 8192 can also run with windows of FOUR blocks: the window of input c
+// at block t is w_t = [x_(t-3) | x_(t-2) | x_(t-1) | x_t] (4B reals, a 2B-point complex FFT, LOG2L =
+// log2(2B) below), and long partition p holds taps [3pB, 3pB + 3B) placed the way a standard partition
+// sits in its 2B window -- B zeros, then the taps -- over the transform size 4B.  The first B samples
+// of the inverse transform of sum_p W_(t-3p-delay) G_p are then the block's output: 2 coefficient
+// reals per tap become 4/3, i.e. config C reads 11 long partitions per filter instead of 32 standard
+// ones.  The standard transforms keep running beside these (the standard ring stays current), so any
+// block the long plan does not cover runs the standard MAC and output pass instead.
+
+// One workgroup per input channel: x_t (the real block the standard K1 of this block just left in
+// prev) goes into slot t of the channel's history of real blocks, the three before it come from the
+// slots t-1..t-3, and the window's spectrum goes into slot t of the long ring.
+template <typename T, int LOG2L>
+__device__ __forceinline__ void
+fft_in_long_body(int ch, unsigned char *smem, const T *__restrict__ prev, T *__restrict__ hist,
+                 c2<T> *__restrict__ ring, const c2<T> *__restrict__ tw, int R, unsigned int t) {
+    constexpr int L = 1 << LOG2L, NT = fft_threads<T>(LOG2L), B = L / 2;     // B reals = B/2 pairs per block
+    constexpr int QB = (B / 2 + NT - 1) / NT, QU = UT<T, LOG2L>::QU;
+    static_assert((B / 2) % NT == 0, "whole pairs per thread");
+    LdsArr<T> s{reinterpret_cast<c2<T> *>(smem)};
+    const int tid = threadIdx.x;
+    const c2<T> *pv = reinterpret_cast<const c2<T> *>(prev + (size_t)ch * B);
+    c2<T> *h = reinterpret_cast<c2<T> *>(hist + (size_t)ch * R * B);
+    c2<T> v[4][QB];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const unsigned int slot = (t + (unsigned int)R * 4u - 3u + (unsigned int)j) % (unsigned int)R;
+#pragma unroll
+        for (int i = 0; i < QB; i++) v[j][i] = h[(size_t)slot * (B / 2) + tid + i * NT];
+    }
+#pragma unroll
+    for (int i = 0; i < QB; i++) v[3][i] = pv[tid + i * NT];
+    TwRegs<T, LOG2L, NT> twr;
+    twr.prefetch(tw);
+    c2<T> uw[QU];
+#pragma unroll
+    for (int i = 0; i < QU; i++) { const int k = 1 + tid + i * NT; uw[i] = tw[k <= L / 2 ? k : 0]; }
+    c2<T> *hs = h + (size_t)(t % (unsigned int)R) * (B / 2);
+#pragma unroll
+    for (int i = 0; i < QB; i++) {
+        hs[tid + i * NT] = v[3][i];
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j * (B / 2) + tid + i * NT] = v[j][i];
+    }
+    __syncthreads();
+    lds_fft<T, LOG2L, NT, false>(s, twr);
+    c2<T> *out = ring + ((size_t)ch * R + t % (unsigned int)R) * L;
+    if (tid == 0) out[0] = mk<T>(s[0].x + s[0].y, s[0].x - s[0].y);
+#pragma unroll
+    for (int i = 0; i < QU; i++) {
+        const int k = 1 + tid + i * NT;
+        if (k <= L / 2) {
+            c2<T> xk, xlk;
+            untangle(s[k], conj(s[L - k]), uw[i], xk, xlk);
+            out[k] = xk;
+            if (k != L - k) out[L - k] = xlk;
+        }
+    }
+}
+
+// [long K3 of an owed block | long K1 of this block] in one launch: the first n_k3 workgroups sum the
+// chunk partials of a long partial-sum buffer, inverse-transform 4B points and write the first B
+// samples (the standard K3 statement otherwise: formats, overflow bookkeeping, status bits); the
+// others transform the inputs' windows.
+template <typename T, int LOG2L>
+__global__ __launch_bounds__(fft_threads<T>(LOG2L)) void
+io_long_kernel(int n_k3,
+               const c2<T> *__restrict__ Zp, size_t chunk_stride, int n_chunks, int first_channel,
+               const DevFormat *__restrict__ fmt_out, DevOverflow *__restrict__ over,
+               const unsigned char *__restrict__ skip_quant, uint8_t *__restrict__ rawout,
+               double safety_limit, int *__restrict__ status,
+               const T *__restrict__ prev, T *__restrict__ hist, c2<T> *__restrict__ ring, int R, unsigned int t,
+               const c2<T> *__restrict__ tw, const BlockState *__restrict__ bs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (bs) t = bs->t;
+    if ((int)blockIdx.x < n_k3)
+        ifft_out_body<T, LOG2L, fft_threads<T>(LOG2L), (1 << LOG2L) / 2>(
+            xcd_channel(blockIdx.x, n_k3), smem, Zp, chunk_stride, n_chunks, first_channel, fmt_out, over,
+            skip_quant, rawout, (T *)nullptr, tw, safety_limit, status);
+    else
+        fft_in_long_body<T, LOG2L>(xcd_channel((int)blockIdx.x - n_k3, (int)gridDim.x - n_k3), smem, prev, hist,
+                                   ring, tw, R, t);
+}
+
+// Long coefficient partitions, derived on the device from the standard spectra of the sets (however a
+// set was registered) and written straight into the stream-ordered layout of the long MAC.  One
+// workgroup per (long partition p, term j, entry): the standard partitions 3p+2, 3p+1, 3p of the
+// term's set are inverse-transformed one after the other in the low half of the LDS array (2B-point
+// real transforms: the taps are the second half of each window, unnormalised inverse of a spectrum
+// pre-divided by 2B); each block of B taps is moved to where it sits in the long window, partitions
+// the entry does not use (beyond its length, or cut by its delay: min(maxP, N - delay)) are zeros;
+// then the 4B-point forward transform, / 4B, and each 512-bin tile goes to its place in the stream.
+template <typename T, int LOG2L>
+__global__ __launch_bounds__(fft_threads<T>(LOG2L)) void
+coeff_long_kernel(const MacEntry<T> *__restrict__ entries, const StreamWhere *__restrict__ where,
+                  const int *__restrict__ which, int p_first, int n_std, int N, int n_groups, int n_chunks,
+                  StreamLayout sl, const c2<T> *__restrict__ tw_std, const c2<T> *__restrict__ tw) {
+    constexpr int L = 1 << LOG2L, LS = L / 2, NT = fft_threads<T>(LOG2L), B = LS;    // B taps per standard partition
+    constexpr int QU = UT<T, LOG2L>::QU, QS = UT<T, LOG2L - 1, NT>::QU, QB = (B / 2 + NT - 1) / NT;
+    static_assert(fft_threads<T>(LOG2L - 1) == NT && (B / 2) % NT == 0, "one thread count for both transforms");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsArr<T> s{reinterpret_cast<c2<T> *>(smem)};
+    const int p = p_first + (int)blockIdx.x, j = blockIdx.y, tid = threadIdx.x;
+    const int e = which[blockIdx.z];
+    const MacEntry<T> &en = entries[e];
+    const c2<T> *H = en.term[j].H;
+    if (en.term[j].kind != TERM_COEFF || H == nullptr) return;       // a term another engine runs (shards)
+    const int q_end = n_std < N - en.delay ? n_std : N - en.delay;     // (en.maxP counts long partitions)
+    // the last partition is aligned to the end of the filter: partitions q_end - 3 .. q_end - 1, of which
+    // those below 3p belong to partition p - 1 and are zeros here (then no window reaches further back
+    // than the standard ones: N blocks)
+    const int q0 = p == en.maxP - 1 ? q_end - 3 : 3 * p;
+    for (int jj = 2; jj >= 0; jj--) {
+        const int q = q0 + jj;
+        c2<T> v[QB];
+        if (q >= 3 * p && q < q_end) {
+            TwRegs<T, LOG2L - 1, NT, true> twr;             // (read per pass: no registers to spare)
+            twr.prefetch(tw_std);
+            const c2<T> *z = H + (size_t)q * LS;
+            if (tid == 0) { const c2<T> a = z[0]; s[0] = mk<T>(a.x + a.y, a.x - a.y); }
+#pragma unroll
+            for (int i = 0; i < QS; i++) {
+                const int k = 1 + tid + i * NT;
+                if (k <= LS / 2) {
+                    c2<T> zk, zlk;
+                    tangle(z[k], conj(z[LS - k]), tw_std[k], zk, zlk);
+                    s[k] = zk;
+                    if (k != LS - k) s[LS - k] = zlk;
+                }
+            }
+            __syncthreads();
+            lds_fft<T, LOG2L - 1, NT, true>(s, twr);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < QB; i++) v[i] = s[B / 2 + tid + i * NT];
+        } else {
+#pragma unroll
+            for (int i = 0; i < QB; i++) v[i] = mk<T>((T)0, (T)0);
+        }
+        __syncthreads();
+        // taps [B + jj*B, B + (jj+1)*B) of the long window = pairs [(1 + jj) B/2, (2 + jj) B/2)
+#pragma unroll
+        for (int i = 0; i < QB; i++) s[(1 + jj) * (B / 2) + tid + i * NT] = v[i];
+    }
+#pragma unroll
+    for (int i = 0; i < QB; i++) s[tid + i * NT] = mk<T>((T)0, (T)0);
+    TwRegs<T, LOG2L, NT> twr;
+    twr.prefetch(tw);
+    __syncthreads();
+    lds_fft<T, LOG2L, NT, false>(s, twr);
+    const StreamWhere w = where[e];
+    const T inv = (T)1.0 / (T)(2 * L);
+    constexpr int TB = 256 * 16 / (int)sizeof(c2<T>);       // bins per 4 KiB tile
+    auto put = [&](int k, c2<T> x) {
+        const int tile = k / TB;
+        const int tc = tile * n_chunks + w.chunk;
+        const unsigned long long bid = (unsigned long long)((tc >> 3) * n_groups + w.group) * 8ull + (unsigned long long)(tc & 7);
+        c2<T> *dst = reinterpret_cast<c2<T> *>(const_cast<unsigned char *>(sl.base) + bid * sl.slice +
+                                               (unsigned long long)w.q * sl.entry_bytes +
+                                               ((unsigned long long)p * OG + (unsigned long long)j) * sl.chunk);
+        dst[k % TB] = mk<T>(x.x * inv, x.y * inv);
+    };
+    if (tid == 0) put(0, mk<T>(s[0].x + s[0].y, s[0].x - s[0].y));
+#pragma unroll
+    for (int i = 0; i < QU; i++) {
+        const int k = 1 + tid + i * NT;
+        if (k <= L / 2) {
+            c2<T> xk, xlk;
+            untangle(s[k], conj(s[L - k]), tw[k], xk, xlk);
+            put(k, xk);
+            if (k != L - k) put(L - k, xlk);
+        }
+    }
 }
 
 // ------------------------------------------------------------------ N:1 virtual channels: delay, mute, mix

@@ -400,6 +400,10 @@ int bfhip_engine_uses_stream_layout(const bfhip_engine *e);
    configs[3]) and the MAC runs as mac_diag_kernel -- a workgroup per (part, output) walking whole
    spectra -- instead of the crossbar kernel */
 int bfhip_engine_uses_diag_mac(const bfhip_engine *e);
+/* 4: the plan in force runs long-window overlap-save (windows of 4 blocks, partitions of 3 blocks of
+   taps: f32 uniform crossbars at L = 8192 with >= 1 GiB of coefficients, BFHIP_LONG_WINDOW=0/1 to
+   force); 2: the standard windows of 2 blocks.  < 0 on a NULL handle */
+int bfhip_engine_window_blocks(const bfhip_engine *e);
 /* depth of the input spectrum rings (n_blocks, plus one spare slot when the block is pipelined) */
 int bfhip_engine_ring_depth(const bfhip_engine *e);
 
