@@ -183,6 +183,10 @@ def lib():
     L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
     L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
+    L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
+    L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
+    L.bfhip_nupc_set_mute.argtypes = [vp, ci, ci, ci]
+    L.bfhip_nupc_get_delay.argtypes = [vp, ci, ci]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -645,6 +649,24 @@ class Nupc:
         """HP-TPDF dither on the listed (integer-format) outputs; before finalize"""
         self._chk(lib().bfhip_nupc_enable_dither(self.h, _iarr(list(channels)), len(channels),
                                                  sample_rate, max_size))
+
+    # per-channel integer delay and mute on the raw I/O blocks (dai.c's delay: / maxdelay:, cid /
+    # cod, cmi / cmo); io is IN or OUT
+    def set_maxdelay(self, io, ch, maxdelay):
+        """before finalize; < 0: fixed (the default)"""
+        self._chk(lib().bfhip_nupc_set_maxdelay(self.h, io, ch, maxdelay))
+
+    def set_delay(self, io, ch, frames):
+        """before finalize the initial delay, after it in force from the next block call; a value
+        above maxdelay, or a change of a fixed channel, leaves the delay as it is"""
+        self._chk(lib().bfhip_nupc_set_delay(self.h, io, ch, frames))
+
+    def set_mute(self, io, ch, muted):
+        self._chk(lib().bfhip_nupc_set_mute(self.h, io, ch, 1 if muted else 0))
+
+    def get_delay(self, io, ch):
+        """the delay in force (curdelay)"""
+        return self._chk(lib().bfhip_nupc_get_delay(self.h, io, ch))
 
 
 def device_count():

@@ -169,6 +169,155 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
     }
 }
 
+// ---- per-channel integer delay and mute on the raw I/O blocks (dai.c's do_mute / update_delay)
+//
+// One channel's period step of the reference's delay machine (delay.c:229-340).  The state
+// transitions (change_delay, curbuf) depend on the requested delays only, never on the samples,
+// so the host keeps them (NupcDelay below) and passes each period's step as a job in the kernel
+// arguments.  The line's data lives in a device arena per channel:
+//     [n_full_cap whole fragments][rest][short 0][short 1][scratch], `fragp` bytes each
+// (fragp = L0 * bytes rounded up to 16, so change_delay's whole-fragment zero-fill is one range).
+struct NupcDelayJob {
+    uint8_t *line;                 // the channel's arena
+    unsigned long long zfull;      // change_delay: bytes of whole fragments to zero, from line[0]
+    int rest_frag;                 // index of the rest fragment (n_full_cap)
+    int byte_offset;               // the channel's first sample in a raw frame
+    int kind;                      // 0 mute only, 1 whole fragments (update_delay_buffer),
+                                   // 2 short (update_delay_short_buffer)
+    int muted;
+    int cur, last;                 // kind 1: fragment written / read; kind 2: short buffer written / read
+    int rr;                        // n_rest
+    int zrest, zshort;             // change_delay: bytes to zero in the rest / in each short buffer
+};
+constexpr int kDelayJobs = 32;     // jobs per launch (1792 bytes of kernel arguments)
+struct NupcDelayJobs { NupcDelayJob j[kDelayJobs]; };
+
+__device__ __forceinline__ unsigned long long smp_ld(const uint8_t *p, int ss) {
+    unsigned long long v = 0;
+    for (int b = 0; b < ss; b++) v |= (unsigned long long)p[b] << (8 * b);
+    return v;
+}
+__device__ __forceinline__ void smp_st(uint8_t *p, unsigned long long v, int ss) {
+    for (int b = 0; b < ss; b++) p[b] = (uint8_t)(v >> (8 * b));
+}
+// p is 16-byte aligned (arena fragments)
+__device__ __forceinline__ void zero_bytes(uint8_t *p, unsigned long long n) {
+    const unsigned long long n16 = n / 16;
+    for (unsigned long long i = threadIdx.x; i < n16; i += blockDim.x) ((uint4 *)p)[i] = make_uint4(0, 0, 0, 0);
+    for (unsigned long long i = n16 * 16 + threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}
+
+// One workgroup per job, on the raw block `raw` of F frames (frame_bytes apart, ss-byte
+// samples).  mute_first: input side (do_mute before update_delay: zeros enter the line); else
+// output side (the delayed block is muted).  Every thread reads and writes only its own samples of
+// the raw block; the exchange between samples goes through the arena's scratch fragment.
+__global__ __launch_bounds__(256) void
+nupc_delay_kernel(const NupcDelayJobs jobs, uint8_t *__restrict__ raw, int F, int ss, int frame_bytes,
+                  unsigned long long fragp, int mute_first) {
+    const NupcDelayJob j = jobs.j[blockIdx.x];
+    uint8_t *buf = raw + j.byte_offset;
+    const size_t stride = (size_t)frame_bytes;
+    if (j.kind == 0) {                                             // no delay in force: a muted channel
+        for (int n = threadIdx.x; n < F; n += blockDim.x) smp_st(buf + n * stride, 0, ss);
+        return;
+    }
+    uint8_t *rest = j.line + (size_t)j.rest_frag * fragp, *sh0 = rest + fragp, *sh1 = sh0 + fragp, *tmp = sh1 + fragp;
+    // change_delay's zero-fills, and the block into the scratch (zeros if muted before the line)
+    zero_bytes(j.line, j.zfull);
+    zero_bytes(rest, (unsigned long long)j.zrest);
+    zero_bytes(sh0, (unsigned long long)j.zshort);
+    zero_bytes(sh1, (unsigned long long)j.zshort);
+    const bool mute_in = mute_first && j.muted, mute_out = !mute_first && j.muted;
+    for (int n = threadIdx.x; n < F; n += blockDim.x)
+        smp_st(tmp + (size_t)n * ss, mute_in ? 0ull : smp_ld(buf + n * stride, ss), ss);
+    __syncthreads();                                               // scratch and zero-fills are visible
+    __threadfence_block();
+    const int rr = j.rr;
+    if (j.kind == 1) {                                             // update_delay_buffer, delay.c:229-262
+        uint8_t *fcur = j.line + (size_t)j.cur * fragp;
+        const uint8_t *last = j.line + (size_t)j.last * fragp;
+        for (int n = threadIdx.x; n < F; n += blockDim.x) {
+            smp_st(fcur + (size_t)n * ss, smp_ld(tmp + (size_t)n * ss, ss), ss);
+            unsigned long long y;
+            if (n < rr) {
+                y = smp_ld(rest + (size_t)n * ss, ss);
+                smp_st(rest + (size_t)n * ss, smp_ld(last + (size_t)(F - rr + n) * ss, ss), ss);
+            } else
+                y = smp_ld(last + (size_t)(n - rr) * ss, ss);
+            smp_st(buf + n * stride, mute_out ? 0ull : y, ss);
+        }
+    } else {                                                       // update_delay_short_buffer, :264-281
+        uint8_t *shw = j.cur ? sh1 : sh0;
+        const uint8_t *shr = j.last ? sh1 : sh0;
+        for (int n = threadIdx.x; n < F; n += blockDim.x) {
+            const unsigned long long y = n < rr ? smp_ld(shr + (size_t)n * ss, ss) : smp_ld(tmp + (size_t)(n - rr) * ss, ss);
+            if (n < rr) smp_st(shw + (size_t)n * ss, smp_ld(tmp + (size_t)(F - rr + n) * ss, ss), ss);
+            smp_st(buf + n * stride, mute_out ? 0ull : y, ss);
+        }
+    }
+}
+
+// host side of one channel's delay machine: delay_allocate_buffer / change_delay / the curbuf
+// walk of delay.c, mirrored from the oracle's bfo_delay (pinned to delay.c by the CPU tests)
+struct NupcDelay {
+    int maxdelay = -1;             // < 0: fixed
+    int req = 0;                   // before finalize the initial delay, after it the requested one
+    bool muted = false;
+    int curdelay = 0, cur = 0, n_full = 0, n_rest = 0, n_full_cap = 0, F = 0, ss = 0;
+    uint8_t *arena = nullptr;      // null: no line (a delay of 0 that cannot change)
+    size_t fragp = 0;
+
+    // delay_allocate_buffer's state (delay.c:357-407); returns the arena bytes, 0 = no line
+    size_t init(int fragment, int sample_size) {
+        F = fragment; ss = sample_size;
+        int initdelay = req;
+        int delay = maxdelay <= 0 ? initdelay : maxdelay;
+        if (maxdelay >= 0 && delay > maxdelay) delay = initdelay = maxdelay;
+        if (maxdelay > 0 && initdelay > maxdelay) initdelay = maxdelay;
+        curdelay = req = initdelay;
+        if (delay == 0) return 0;
+        fragp = ((size_t)F * ss + 15) / 16 * 16;
+        n_full_cap = delay > F ? delay / F + 1 : 0;
+        if (delay <= F) n_rest = initdelay;
+        else {
+            n_rest = initdelay % F;
+            n_full = initdelay / F + 1;
+            if (n_full == 1) n_full = 0;
+        }
+        return (size_t)(n_full_cap + 4) * fragp;
+    }
+
+    // this period's step (change_delay with the requested delay, then the update); false: nothing to do
+    bool step(NupcDelayJob &jb) {
+        jb = NupcDelayJob();
+        jb.muted = muted;
+        if (arena) {
+            const int nd = req;
+            if (nd != curdelay && nd <= maxdelay) {                // change_delay, delay.c:283-318
+                if (nd <= F) {
+                    n_rest = nd;
+                    if (curdelay > F || curdelay < nd) jb.zshort = nd * ss;
+                    n_full = 0;
+                } else {
+                    n_rest = nd % F;
+                    n_full = nd / F + 1;
+                    if (curdelay < nd) { jb.zfull = (unsigned long long)n_full * fragp; jb.zrest = n_rest * ss; }
+                }
+                cur = 0; curdelay = nd;
+            }
+            jb.line = arena; jb.rest_frag = n_full_cap; jb.rr = n_rest;
+            if (n_full > 0) {
+                jb.kind = 1; jb.cur = cur; jb.last = cur == n_full - 1 ? 0 : cur + 1;
+                if (++cur == n_full) cur = 0;
+            } else if (n_rest > 0) {
+                jb.kind = 2; jb.cur = cur; jb.last = !cur;
+                cur = !cur;
+            }
+        }
+        return jb.kind != 0 || muted;
+    }
+};
+
 thread_local std::string n_err;
 
 // (a runtime failure's sticky error is cleared; argument / state errors make no HIP call)
@@ -268,6 +417,9 @@ struct bfhip_nupc {
     int8_t *d_dither_table = nullptr;
     void *d_randmap = nullptr;             // 512 reals
     void *d_dither_stage = nullptr;        // [n_dither][L0] reals: the emit step's input to the chain
+    // integer delay and mute per raw channel (bfhip_nupc_set_delay / _set_mute): [io][channel]
+    std::vector<NupcDelay> dl[2];
+    std::vector<NupcDelayJob> dl_jobs;     // this period's jobs of one side (host scratch)
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
@@ -314,6 +466,8 @@ bfhip_nupc *bfhip_nupc_create(int device, int realsize, int n_in, int n_out, int
     }
     n->crossfade = seg_length[0];          // the reference's one-block fade
     n->gain.assign(n_out, 1.0);
+    n->dl[0].resize(n_in);
+    n->dl[1].resize(n_out);
     return n;
 }
 
@@ -335,6 +489,7 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive,
                  n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage};
     for (void *q : p) if (q) (void)hipFree(q);
+    for (auto &side : n->dl) for (auto &d : side) if (d.arena) (void)hipFree(d.arena);
     if (n->h_status) (void)hipHostFree(n->h_status);
     if (n->h_in) (void)hipHostFree(n->h_in);
     if (n->h_out) (void)hipHostFree(n->h_out);
@@ -527,6 +682,13 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
                                   &n->d_dither_state));
         NCHK(bfhip_internal_dev_alloc(&n->d_dither_stage, n->dither_ch.size() * L0 * n->rs));
     }
+    for (int io = 0; io < 2; io++)
+        for (auto &d : n->dl[io]) {
+            const size_t bytes = d.init(L0, n->fmt[io][0].bytes);     // delay_allocate_buffer
+            if (bytes == 0) continue;
+            NCHK(bfhip_internal_dev_alloc((void **)&d.arena, bytes));
+            NCHK(hipMemset(d.arena, 0, bytes));
+        }
     for (auto &c : n->coeff) n->can_switch = n->can_switch || c.size() > 1;
     if (n->can_switch) {
         NCHK(bfhip_internal_dev_alloc((void **)&n->d_acc2, (size_t)A * n->n_out * n->rs));
@@ -576,6 +738,37 @@ int nupc_accumulate(bfhip_nupc *n, const Seg &s, unsigned long long pos, void *a
         hipLaunchKernelGGL(nupc_accumulate_kernel<double>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->stream,
                            (double *)acc, (const double *)s.d_out, (double *)acc2, (const double *)s.d_out2, pos, n->A, n->n_out, s.L);
     NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+// this period's delay / mute step of one side on its raw block; no launch if no channel of the
+// side is muted or has a delay line with work
+int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
+    for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
+        const bfhip_format &f = n->fmt[io][ch];
+        if ((n->dl[io][ch].arena || n->dl[io][ch].muted) &&
+            (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->frame_bytes[io]))
+            return nfail(BFHIP_EINVAL, "nupc: delay / mute on a channel whose samples lie outside the raw frame");
+    }
+    auto &jobs = n->dl_jobs;
+    jobs.clear();
+    for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
+        NupcDelayJob jb;
+        if (!n->dl[io][ch].step(jb)) continue;
+        jb.byte_offset = n->fmt[io][ch].byte_offset;
+        jobs.push_back(jb);
+    }
+    const NupcDelay &d0 = n->dl[io][0];
+    const unsigned long long fragp = ((unsigned long long)n->seg[0].L * d0.ss + 15) / 16 * 16;
+    for (size_t first = 0; first < jobs.size(); first += kDelayJobs) {
+        const int cnt = (int)std::min(jobs.size() - first, (size_t)kDelayJobs);
+        NupcDelayJobs args;
+        memset(&args, 0, sizeof(args));
+        std::copy(jobs.begin() + first, jobs.begin() + first + cnt, args.j);
+        hipLaunchKernelGGL(nupc_delay_kernel, dim3(cnt), dim3(256), 0, n->stream, args, raw, n->seg[0].L, d0.ss,
+                           (int)n->frame_bytes[io], fragp, io == BFHIP_IN ? 1 : 0);
+        NCHK(hipGetLastError());
+    }
     return BFHIP_OK;
 }
 
@@ -662,6 +855,9 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     const size_t wpos = (size_t)((end - L0) % (unsigned long long)n->in_frames);
     if ((const uint8_t *)rawin_dev != n->d_in + wpos * n->frame_bytes[0])     // block() uploads straight into the slot
         NCHK(hipMemcpyAsync(n->d_in + wpos * n->frame_bytes[0], rawin_dev, (size_t)L0 * n->frame_bytes[0], hipMemcpyDeviceToDevice, n->stream));
+    // input delay and mute on the slot, before any segment (or ev_in, which the background
+    // segment streams wait on) reads it
+    { const int r = nupc_delay_side(n, BFHIP_IN, n->d_in + wpos * n->frame_bytes[0]); if (r < 0) return r; }
     if (n->gain_dirty) {
         // output gains set since the last block: in force from this block's first frame
         NCHK(hipEventSynchronize(n->ev_gain));                    // the previous upload has read h_inv
@@ -740,6 +936,8 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
                            opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
                            (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);
     NCHK(hipGetLastError());
+    // output delay and mute on the quantised block (block() copies it out behind this)
+    { const int r = nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev); if (r < 0) return r; }
     n->block++;
     if (n->sw && !nupc_switch_left(n, end)) {
         // the old ring has been emitted and cleared down to its last written frame: it is the spare now
@@ -867,6 +1065,39 @@ int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain) {
     if (out_ch < 0 || out_ch >= n->n_out || !std::isfinite(gain)) return nfail(BFHIP_EINVAL, "nupc_set_output_gain: bad argument");
     if (n->gain[out_ch] != gain) { n->gain[out_ch] = gain; n->gain_dirty = true; }
     return BFHIP_OK;
+}
+
+// ---- run-time control: per-channel delay and mute -------------------------------------------
+
+static int delay_channel_ok(const bfhip_nupc *n, int io, int ch) {
+    return n && io >= 0 && io <= 1 && ch >= 0 && ch < (io ? n->n_out : n->n_in);
+}
+
+int bfhip_nupc_set_maxdelay(bfhip_nupc *n, int io, int ch, int maxdelay) {
+    if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_set_maxdelay: bad argument");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_maxdelay after finalize");
+    n->dl[io][ch].maxdelay = maxdelay;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_delay(bfhip_nupc *n, int io, int ch, int delay) {
+    if (!delay_channel_ok(n, io, ch) || delay < 0) return nfail(BFHIP_EINVAL, "nupc_set_delay: bad argument");
+    n->dl[io][ch].req = delay;                  // change_delay at the next block call ignores what it must
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_mute(bfhip_nupc *n, int io, int ch, int muted) {
+    if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_set_mute: bad argument");
+    n->dl[io][ch].muted = muted != 0;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_get_delay(const bfhip_nupc *n, int io, int ch) {
+    if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_get_delay: bad argument");
+    if (n->finalized) return n->dl[io][ch].curdelay;
+    NupcDelay d = n->dl[io][ch];                // what finalize will start with
+    (void)d.init(n->seg[0].L, 1);
+    return d.curdelay;
 }
 
 }  // extern "C"

@@ -112,6 +112,44 @@ int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *ta
    output; 0.0 mutes; default 1.0 (folded into the 1/scale factor: exact) */
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);
 
+/* ---- run-time control: per-channel integer delay and mute (delay: / maxdelay:, cid / cod,
+ * cmi / cmo) -------------------------------------------------------------------------------
+ * io is BFHIP_IN or BFHIP_OUT; channels are the side's raw channels.  The reference does these
+ * on dai.c's raw period buffers (dai.c:1386-1390, 1444-1449, 1664-1668; delay.c:229-340); the
+ * convolver does the same on the device, so its raw output is what dai.c makes of it.
+ *
+ * Period.  The delay line's fragment is seg_length[0] (L0) frames and a requested delay is read
+ * once per block call: the output is the reference's at a period of L0 frames.
+ * Input side.  A muted input's samples are zeroed on the raw block before its delay line; the
+ * zeros enter the line and the line keeps advancing (do_mute, then update_delay).  The delay runs
+ * in place on the block in the input ring, so every segment, whatever its length and however
+ * late it is launched, reads delayed input.
+ * Output side.  The delay runs on the quantised raw output, after dither, output gain and the
+ * cross-fade; the mute comes after the delay (update_delay, then mute).  The overflow structs and
+ * status bits count the undelayed, unmuted samples, as real2raw does before dai.c touches the
+ * buffer.
+ * Changes follow change_delay (delay.c:283-318) exactly: an increase zero-fills the line, so it
+ * makes a gap of silence, and a decrease reuses the line's history.  There is no cross-fade; that
+ * is the reference's behaviour.  The delay machine's state transitions do not depend on the
+ * samples, so the host keeps them and hands each period's step to one kernel launch per side as
+ * kernel arguments: no host wait per period, and a side where no channel is muted or delayed
+ * makes no launch at all.  An initial delay above a maxdelay > 0 starts at maxdelay (the
+ * reference would overrun its buffer).  Packed 3-byte samples with a delay <= L0 hang the
+ * reference (shift_samples); here they get a pure delay.  Sub-sample delay (subdelay: / sdf_length, and the
+ * extra_delay dai.c:233-236 adds for it) is not provided.
+ */
+/* before finalize; < 0: fixed (the reference's maxdelay: -1, the default); BFHIP_ESTATE after */
+int bfhip_nupc_set_maxdelay(bfhip_nupc *n, int io, int channel, int maxdelay);
+/* before finalize: the initial delay (delay:); after finalize: in force from the first frame of
+   the next block call (cid / cod).  delay < 0: BFHIP_EINVAL.  A value above the channel's
+   limit, or any change of a fixed channel, is accepted and leaves the delay as it is
+   (change_delay, delay.c:289-291; bfhip_engine_set_delay has the same contract) */
+int bfhip_nupc_set_delay(bfhip_nupc *n, int io, int channel, int delay_frames);
+/* any time; in force from the first frame of the next block call */
+int bfhip_nupc_set_mute(bfhip_nupc *n, int io, int channel, int muted);
+/* the delay in force (curdelay), for a CLI's "info" */
+int bfhip_nupc_get_delay(const bfhip_nupc *n, int io, int channel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,11 @@ less than its duration.  Prints one JSON line: median / p99 / max milliseconds p
 bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, next to the
 uniform engine's block time and I/O delay for the same filters.
 
-    python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither]
+    python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
-on both outputs (an integer --out-format is needed; sample rate 48000)."""
+on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
+outputs a maxdelay of 48 000 frames and new delays (seeded, up to 48 000) every 300 periods."""
 import argparse
 import json
 import os
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("steps", nargs="?", type=int, default=4096)
     ap.add_argument("--out-format", default="FLOAT64_LE")
     ap.add_argument("--dither", action="store_true")
+    ap.add_argument("--delay", action="store_true")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
     seg_len, k = [], L0
@@ -46,6 +48,10 @@ def main():
     nu.set_interleaved(1, a.out_format)
     if a.dither:
         nu.enable_dither([0, 1], 48000)
+    if a.delay:
+        for o in range(2):
+            nu.set_maxdelay(bf.OUT, o, 48000)
+            nu.set_delay(bf.OUT, o, 1000 * (o + 1))
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -56,7 +62,13 @@ def main():
     import gc
     gc.disable()                       # the timed loop allocates one small array per period
     ts = []
+    drng = np.random.default_rng(9)
+    n_changes = 0
     for s in range(steps + 256):
+        if a.delay and s % 300 == 299:
+            for o in range(2):
+                nu.set_delay(bf.OUT, o, int(drng.integers(0, 48001)))
+            n_changes += 1
         t0 = time.perf_counter()
         st, _ = nu.block(x[s & 7])
         ts.append(time.perf_counter() - t0)
@@ -69,6 +81,7 @@ def main():
     print(json.dumps({
         "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s" % (nu.taps, seg_len, seg_blk),
         "out_format": a.out_format, "dithered_outputs": [0, 1] if a.dither else [],
+        "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
