@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs: set-up, warm-up, the timed steps, the dump of
+the outputs (if asked for) and the result line.  `--full` adds, after the timed region, the
+end-to-end check of the timed configuration's outputs against a float64 convolution (`verify`)
+and, on one GPU, the CPU baseline (`cpu_baseline`); `--no-verify` / `--no-cpu-baseline` drop
+either one from a full run.
 
 One "step" = one block of the hot path over one batch of synthetic input: L new samples on
 each of the 64 input channels -> forward FFTs -> 64x64 crossbar multiply-accumulate over 32
@@ -376,9 +382,13 @@ def main():
                     help="INFORMATIVE, never the headline: two blocks per pass over the coefficients "
                          "(bfhip_engine_block_pair_dev) -- what a host with two periods in hand gets; one period "
                          "of extra I/O delay, the same output bits")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also check the timed configuration's outputs end to end "
+                         "(`verify`) and, on one GPU, time the CPU baseline (`cpu_baseline`); a plain run "
+                         "does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the end-to-end check of the timed configuration's outputs (after the timed region)")
+                    help="--full without the end-to-end check of the timed configuration's outputs")
     ap.add_argument("--host-io", action="store_true",
                     help="time bfhip_engine_block() with HOST raw buffers (PCIe both ways and a "
                          "sync per block included) -- informative, never the headline value")
@@ -756,7 +766,7 @@ def main():
                            "noise block with the impulse response loaded for that (output, input) pair"}
 
     ver = None
-    if not args.no_verify and not args.host_io:
+    if args.full and not args.no_verify and not args.host_io:
         ver = verify()
         if dist is not None:
             allv = [None] * world
@@ -859,7 +869,7 @@ def main():
             if rccl_rehearsal:
                 out["exposed_collective_ms"] = per_rank[0]["exposed_collective_ms"]
                 out["backend"] = "rccl (one-rank communicator)"
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(wl)
         else:
             # the dominant kernel on the slowest rank prices the job; every rank's own figure beside it

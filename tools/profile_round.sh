@@ -20,9 +20,9 @@ export TMPDIR=/tmp
 EXTRA=""
 if [ "$WL" != "C" ]; then EXTRA="--workload $WL"; fi
 
-echo "[profile_round] kernel trace + stats of: python3 bench.py $EXTRA --no-cpu-baseline"
+echo "[profile_round] kernel trace + stats of: python3 bench.py $EXTRA --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ktrace_$WL" -- \
-    python3 bench.py $EXTRA --no-cpu-baseline > "$OUT/bench_config${WL}_under_rocprofv3.json"
+    python3 bench.py $EXTRA --full --no-cpu-baseline > "$OUT/bench_config${WL}_under_rocprofv3.json"
 cat "$OUT/bench_config${WL}_under_rocprofv3.json"
 STATS=$(find "$OUT/ktrace_$WL" -name '*kernel_stats.csv' | head -1)
 # our kernels only (the torch RNG kernels that synthesise the inputs are not the product)

@@ -9,7 +9,7 @@ FAILED=0
 for n in 2 4 8; do
   for mode in input output; do
     name=configC_rank0of${n}_${mode}_sharded_rehearsal
-    BFHIP_BENCH_REHEARSE_RANKS=$n python bench.py --shard $mode --no-cpu-baseline 2> "$OUT/$name.err" | tail -1 > "$OUT/bench_$name.json"
+    BFHIP_BENCH_REHEARSE_RANKS=$n python bench.py --full --shard $mode --no-cpu-baseline 2> "$OUT/$name.err" | tail -1 > "$OUT/bench_$name.json"
     rc=${PIPESTATUS[0]}
     if [ "$rc" != 0 ] || [ ! -s "$OUT/bench_$name.json" ]; then mv -f "$OUT/bench_$name.json" "$OUT/bench_$name.json.FAILED" 2>/dev/null; FAILED=$((FAILED + 1)); fi
     python3 - "$OUT/bench_$name.json" "$n" "$mode" <<'PY'
