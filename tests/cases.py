@@ -89,6 +89,16 @@ def samples(raw, fmt):
     return np.frombuffer(raw.tobytes(), RAW_NP[fmt]).astype(np.float64)
 
 
+def fade_cascade_parts():
+    """fade_cascade_network's data: (L, N, blocks, switch block, [ha, hb, hc, hd], input [frames][2])"""
+    L, N = 1024, 4
+    rng = np.random.default_rng(21)
+    irs = [make_ir(rng, L * N - 17 * k, 2) for k in range(4)]
+    nblk = 3 * N + 2
+    x = rng.standard_normal((nblk * L, 2)) * 0.1
+    return L, N, nblk, 2 * N + 1, irs, x
+
+
 def fade_cascade_network(engine_cls, rs):
     """One network that exercises delay bookkeeping, cascade evaluation and a cross-fade at once,
     and its float64 numpy model (scipy fftconvolve; nothing from oracle/):
@@ -103,9 +113,8 @@ def fade_cascade_network(engine_cls, rs):
     (fftw_convolver.c:330-368, bfrun.c:1803-1838).  Returns (engine output, model, L, sw)."""
     from scipy.signal import fftconvolve
     dt = np.float32 if rs == 4 else np.float64
-    L, N = 1024, 4
-    rng = np.random.default_rng(21)
-    ha, hb, hc, hd = [make_ir(rng, L * N - 17 * k, 2).astype(dt) for k in range(4)]
+    L, N, nblk, sw, irs, x = fade_cascade_parts()
+    ha, hb, hc, hd = [h.astype(dt) for h in irs]
     e = engine_cls(L, N, rs, 2, 2)
     e.set_interleaved(0, "FLOAT64_LE")
     e.set_interleaved(1, "FLOAT_LE" if rs == 4 else "FLOAT64_LE")
@@ -117,8 +126,6 @@ def fade_cascade_network(engine_cls, rs):
     e.add_filter(in_ch=[1], out_ch=[1, 0], out_scale=[1.0, -0.5], coeff=cd, delayblocks=2)
     if hasattr(e, "finalize"):
         e.finalize()
-    nblk, sw = 3 * N + 2, 2 * N + 1
-    x = rng.standard_normal((nblk * L, 2)) * 0.1
     n = len(x)
     got = []
     for b in range(nblk):
@@ -145,3 +152,18 @@ def fade_cascade_network(engine_cls, rs):
     yc[(sw + 1) * L:] = yc_new[(sw + 1) * L:]
     yd = conv(delayed(x[:, 1], 2), hd[:(N - 2) * L])
     return y, np.stack([0.8 * yc - 0.5 * yd, yd], axis=1), L, sw
+
+
+def act(e, a):
+    """one run-time call on an oracle or HIP engine: ("coeff", f, c), ("scale", f, io, idx, v),
+    ("fscale", f, idx, v) or ("delay", f, d) (xbar_ref.Network.act models the same tuples)"""
+    if a[0] == "coeff":
+        e.set_coeff(a[1], a[2])
+    elif a[0] == "scale":
+        e.set_scale(a[1], a[2], a[3], a[4])
+    elif a[0] == "fscale":
+        e.set_fscale(a[1], a[2], a[3])
+    elif a[0] == "delay":
+        e.set_delayblocks(a[1], a[2])
+    else:
+        raise ValueError(a)

@@ -136,3 +136,140 @@ def test_model_requantises_and_counts_overflows_like_the_oracle(fmt):
         assert g.n_overflows == ofs[c].n_overflows and g.max == ofs[c].max, c
         assert abs(g.intlargest - ofs[c].intlargest) <= (0 if fmt == "S16_LE" else 1), c
         assert g.largest == pytest.approx(ofs[c].largest, rel=1e-9, abs=1e-9), c
+
+
+# ------------------------------------------------------------------ networks
+
+def _net_run(spec, nblk, actions, seed=9, amplitude=0.1):
+    """the spec through the oracle's float64 engine and the model: -> (oracle, model) [frames][O]"""
+    e = cases.build(bo.Engine, spec)
+    blocks = cases.raw_blocks(seed, nblk, spec["L"], spec["n_in"], spec["infmt"], amplitude=amplitude)
+    out = []
+    for k, b in enumerate(blocks):
+        for a in actions.get(k, ()):
+            cases.act(e, a)
+        st, raw = e.block(b)
+        assert st == 0, k
+        out.append(raw)
+    got = xr.decode(np.concatenate(out), spec["outfmt"], spec["n_out"])
+    x = xr.decode(np.concatenate(blocks), spec["infmt"], spec["n_in"])
+    return got, xr.Network(spec).output(x, nblk, actions)
+
+
+def _hold_blocks(got, want, L, tol=1e-11):
+    """per block and output: relative RMS error, against the block's RMS or, for a block that is
+    (nearly) silent, against 1e-3 of the output's RMS per block over the run"""
+    nblk = len(want) // L
+    for c in range(want.shape[1]):
+        floor = 1e-3 * np.sqrt((want[:, c] ** 2).sum() / nblk)
+        for k in range(nblk):
+            s = slice(k * L, (k + 1) * L)
+            err = np.sqrt(((got[s, c] - want[s, c]) ** 2).sum())
+            assert err <= tol * max(np.sqrt((want[s, c] ** 2).sum()), floor), (k, c, err)
+
+
+def test_model_matches_the_fade_cascade_network():
+    """cases.fade_cascade_network's engine run (the oracle, float64) and its hand-written model, both
+    held to the network model built from the same description"""
+    got, hand, L, sw = cases.fade_cascade_network(bo.Engine, 8)
+    L_, N, nblk, sw_, (ha, hb, hc, hd), x = cases.fade_cascade_parts()
+    assert (L_, sw_, nblk * L) == (L, sw, len(got))
+    spec = dict(L=L, N=N, n_out=2, coeffs=[(h, 1.0, 0) for h in (ha, hb, hc, hd)], filters=[
+        dict(in_ch=[0], coeff=0, delayblocks=1),
+        dict(in_ch=[1], coeff=1),
+        dict(in_ch=[0], in_scale=[0.25], in_f=[0, 1], in_fscale=[0.5, -1.0], out_ch=[0], out_scale=[0.8],
+             coeff=2, crossfade=True),
+        dict(in_ch=[1], out_ch=[1, 0], out_scale=[1.0, -0.5], coeff=3, delayblocks=2)])
+    want = xr.Network(spec).output(x, nblk, {sw: [("coeff", 2, 3)]})
+    _hold_blocks(got, want, L)
+    _hold_blocks(hand, want, L, 1e-13)
+
+
+def _feature_spec(L, N, rs=8, infmt="S24_4LE", outfmt="FLOAT64_LE"):
+    """the network of test_gpu_lengths.test_every_filter_feature_at_16384: a cascade with a mixed
+    channel + filter input, a dirac clamped from delay 7, a multi-output filter, a scaled short set"""
+    coeffs = [(_ir(210 + k, L * N, 2), 1.0, 0) for k in range(3)] + [(_ir(214, L, 2), 0.5, 1)]
+    filters = [
+        dict(in_ch=[0], coeff=0, out_ch=[2], crossfade=True),
+        dict(in_ch=[1], coeff=1, delayblocks=1),
+        dict(in_f=[0, 1], in_fscale=[1.0, -0.5], out_ch=[0], coeff=2, crossfade=True),
+        dict(in_ch=[0, 1], in_scale=[0.5, 0.25], in_f=[1], out_ch=[1], coeff=3),
+        dict(in_ch=[1], out_ch=[0, 1], out_scale=[0.25, -1.0], coeff=-1, delayblocks=7),
+    ]
+    return dict(L=L, N=N, rs=rs, n_in=2, n_out=3, infmt=infmt, outfmt=outfmt, coeffs=coeffs, filters=filters)
+
+
+FEATURE_ACTIONS = {2: [("coeff", 0, 1)], 3: [("coeff", 2, -1), ("scale", 3, 0, 1, -0.75)],
+                   4: [("coeff", 0, 0), ("coeff", 2, 2), ("fscale", 2, 1, 0.3)],
+                   5: [("coeff", 2, 0), ("scale", 4, 1, 0, 2.0)],
+                   7: [("fscale", 3, 0, -1.5), ("scale", 1, 0, 0, 0.5)]}
+
+
+def test_model_matches_the_every_feature_network():
+    """with the lengths test's switch sequence (hard and cross-faded, to and from a dirac) and, on
+    top, in/out scale and fscale changes (slot by slot, the eval half of the block before)"""
+    spec = _feature_spec(64, 3)
+    got, want = _net_run(spec, 12, FEATURE_ACTIONS)
+    _hold_blocks(got, want, 64)
+
+
+def random_dag(rng, L, N, n_in, n_out, n_filters=6, n_coeffs=5):
+    """a random cases.build network: every filter reads 0-2 channels and (after the first two) 0-2
+    earlier filters, writes 0-2 outputs (at least one filter per output), a delay up to N + 1, a
+    dirac or one of the sets (full, one tap into the last partition, short and scaled)"""
+    lens = [N * L, (N - 1) * L + 1, L * N - L // 2, 2 * L, L]
+    coeffs = [(rng.standard_normal(lens[k % 5]) / np.sqrt(lens[k % 5]) / 4, [1.0, 1.0, 0.5, -2.0, 1.0][k % 5],
+               [0, 0, 0, 0, 1][k % 5]) for k in range(n_coeffs)]
+    filters = []
+    for f in range(n_filters):
+        ins = sorted(rng.choice(n_in, int(rng.integers(0 if f >= 2 else 1, 3)), replace=False).tolist())
+        fin = sorted(rng.choice(f, int(rng.integers(0, min(f, 2) + 1)), replace=False).tolist()) if f >= 2 else []
+        if not ins and not fin:
+            ins = [int(rng.integers(n_in))]
+        outs = sorted(rng.choice(n_out, int(rng.integers(0, 3)), replace=False).tolist())
+        filters.append(dict(in_ch=ins, in_scale=rng.uniform(-1, 1, len(ins)).round(3).tolist(), in_f=fin,
+                            in_fscale=rng.uniform(-1, 1, len(fin)).round(3).tolist(), out_ch=outs,
+                            out_scale=rng.uniform(-1.5, 1.5, len(outs)).round(3).tolist(),
+                            coeff=int(rng.integers(-1, n_coeffs)), delayblocks=int(rng.integers(0, N + 2)),
+                            crossfade=bool(rng.integers(2))))
+    for o in range(n_out):
+        if not any(o in fd["out_ch"] for fd in filters):
+            fd = filters[int(rng.integers(n_filters))]
+            fd["out_ch"].append(o)
+            fd["out_scale"].append(1.0)
+    return coeffs, filters
+
+
+def random_actions(rng, filters, n_coeffs, t0, t1, n=6):
+    """n run-time calls on random filters between blocks t0 and t1"""
+    acts = {}
+    for _ in range(n):
+        t = int(rng.integers(t0, t1))
+        f = int(rng.integers(len(filters)))
+        fd = filters[f]
+        kinds = ["coeff", "coeff"] + (["in"] if fd["in_ch"] else []) + (["out"] if fd["out_ch"] else []) + \
+            (["fs"] if fd["in_f"] else [])
+        k = kinds[int(rng.integers(len(kinds)))]
+        v = round(float(rng.uniform(-1.5, 1.5)), 3)
+        if k == "coeff":
+            a = ("coeff", f, int(rng.integers(-1, n_coeffs)))
+        elif k == "in":
+            a = ("scale", f, 0, int(rng.integers(len(fd["in_ch"]))), v)
+        elif k == "out":
+            a = ("scale", f, 1, int(rng.integers(len(fd["out_ch"]))), v)
+        else:
+            a = ("fscale", f, int(rng.integers(len(fd["in_f"]))), v)
+        acts.setdefault(t, []).append(a)
+    return acts
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+def test_model_matches_a_random_dag(seed):
+    L_, N_, I, O = 32, 5, 3, 3
+    rng = np.random.default_rng(seed)
+    coeffs, filters = random_dag(rng, L_, N_, I, O)
+    spec = dict(L=L_, N=N_, rs=8, n_in=I, n_out=O, infmt="FLOAT64_LE", outfmt="FLOAT64_LE", coeffs=coeffs,
+                filters=filters)
+    nblk = 3 * N_ + 2
+    got, want = _net_run(spec, nblk, random_actions(rng, filters, len(coeffs), 1, nblk - 1, 8))
+    _hold_blocks(got, want, L_)

@@ -6,10 +6,12 @@ engine: numpy and scipy only.
              they are);
     inputs   a virtual input of an N:1 input map is its physical channel delayed by its sample
              delay, and zero from the block it is muted at;
-    filters  each filter (input, output) has a per-block timeline of states: the taps in force,
+    filters  each filter (channel inputs, filter inputs, outputs) has a per-block timeline of
+             states: the taps in force (a dirac: DIRAC; a short or scaled set: coeff()),
              delayblocks (clamped to N - 1, the taps then cut to N - d partitions: cblocks_of,
-             bfrun.c:1579-1591), the input and output scales, and whether the block of a change is
-             a cross-fade;
+             bfrun.c:1579-1591), the input, filter-input and output scales, and whether the block
+             of a change is a cross-fade; filters are evaluated in list order, a filter input
+             reading an earlier filter's unscaled output;
     output   block t is the sum over filters of block t of scale * conv(x delayed by d_t * B, h_t)
              while the delay and input scale have been constant for N blocks; after a run-time
              change the filter's ring is followed slot by slot (output()); on a cross-fade block the ramp (1 - w) old + w new, w = k / (B - 1)
@@ -126,92 +128,210 @@ def virtual_inputs(x, virt2phys, delay=None, mute_from=None, L=None):
     return out
 
 
-class Filter:
-    """one filter of the crossbar: input channel, output channel and its timeline of states"""
+DIRAC = None       # the taps of a dirac filter (coeff = -1): the input, delayed by the filter's delay
 
-    def __init__(self, i, o, taps, delay=0, in_scale=1.0, out_scale=1.0):
+
+def coeff(taps, L, scale=1.0, n_blocks=0):
+    """the taps a coefficient set holds (add_coeff): scale * taps, cut to n_blocks partitions when
+    n_blocks is given (a short set), as coeffs2cbuf renders them"""
+    taps = np.asarray(taps, np.float64)
+    if n_blocks > 0:
+        taps = taps[:n_blocks * L]
+    return taps * scale
+
+
+def _vec(v, n):
+    if v is None:
+        return (1.0,) * n
+    if np.isscalar(v):
+        return (float(v),) * n
+    v = tuple(float(a) for a in v)
+    assert len(v) == n, (v, n)
+    return v
+
+
+def _taps(t):
+    return np.ones(1) if t is None else np.asarray(t, np.float64)
+
+
+class Filter:
+    """one filter: channel inputs `i` (an index or a list) with their scales, filter inputs `in_f`
+    (indices of earlier filters in the list handed to output()) with their scales, outputs `o` (an
+    index or a list) with their scales, and its timeline of states"""
+
+    def __init__(self, i, o, taps, delay=0, in_scale=1.0, out_scale=1.0, in_f=(), in_fscale=None):
+        self.ins = [i] if np.isscalar(i) else list(i)
+        self.outs = [o] if np.isscalar(o) else list(o)
+        self.in_f = list(in_f)
         self.i, self.o = i, o
-        self.segs = [(0, dict(taps=np.asarray(taps, np.float64), delay=delay, in_scale=in_scale,
-                              out_scale=out_scale), False)]
+        self.segs = [(0, dict(taps=_taps(taps), delay=delay, in_scale=_vec(in_scale, len(self.ins)),
+                              out_scale=_vec(out_scale, len(self.outs)),
+                              fscale=_vec(in_fscale, len(self.in_f))), False)]
 
     @property
     def state(self):
         return self.segs[-1][1]
 
     def change(self, t, fade=False, **kw):
-        """from block t on: the state with `kw` changed; fade: block t is a cross-fade from the state
+        """from block t on: the state with `kw` changed; fade: block t is a cross-fade from the taps
         before (several changes at one block merge; the fade flag is kept if any asked for it)"""
         st = dict(self.state)
-        st.update(kw)
-        if "taps" in kw:
-            st["taps"] = np.asarray(kw["taps"], np.float64)
+        n = {"in_scale": len(self.ins), "out_scale": len(self.outs), "fscale": len(self.in_f)}
+        for k, v in kw.items():
+            st[k] = _taps(v) if k == "taps" else _vec(v, n[k]) if k in n else v
         if self.segs[-1][0] == t and t > 0:
             _, _, f0 = self.segs.pop()
             fade = fade or f0
         assert not self.segs or t >= self.segs[-1][0]
         self.segs.append((t, st, fade))
 
+    def set_scale(self, t, io, idx, v):
+        """set_scale(filter, io, idx, v) issued before block t"""
+        key = "in_scale" if io == 0 else "out_scale"
+        s = list(self.state[key])
+        s[idx] = v
+        self.change(t, **{key: s})
 
-def _window_out(x, s, h_i, L):
-    """the B outputs one ring slot adds: window [x_(s-1) | x_s] of block s through partition h_i"""
-    w = np.zeros(2 * L)
-    if s >= 1:
-        w[:L] = x[(s - 1) * L:s * L]
-    w[L:] = x[s * L:(s + 1) * L]
+    def set_fscale(self, t, idx, v):
+        s = list(self.state["fscale"])
+        s[idx] = v
+        self.change(t, fscale=s)
+
+
+def _window_out(w, h_i, L):
+    """the L outputs one ring slot adds: the 2L window w through partition h_i"""
     return fftconvolve(w, h_i)[L:2 * L]
 
 
 def output(x, filters, L, N, n_out, n_blocks):
     """x: [frames][n_in] float64 inputs (virtual ones for an input map); -> [n_blocks * L][n_out].
 
-    Delays and input scales act where the reference applies them: when a block ENTERS the
-    filter's ring (block s goes to slot (s + d_s) mod N scaled by a_s, bfrun.c:1600-1641; output
-    block t reads slots t - i, i < min(cblocks, blocks processed)).  While every block in the ring
-    entered with the delay and scale in force, that is scale * conv(x delayed by d B, h cut to
-    N - d partitions): one fftconvolve per distinct state.  The N blocks after a run-time delay or
-    input-scale change are summed slot by slot."""
+    What enters a filter's ring at block s is the 2L window of its mixed input, sum_k a_s[k] x_k over
+    blocks s-1 and s, plus, for filter inputs, sum_j fs[j] u_j (u_j: the unscaled time output of
+    upstream filter j, its cross-fade ramp included) with the fscale in force at block s-1 in the
+    first half and at block s in the second (convolve_eval keeps the mixed half of the last block,
+    fftw_convolver.c:411-433).  Delays and input scales act where the reference applies them: when a
+    block ENTERS the filter's ring (block s goes to slot (s + d_s) mod N scaled by a_s,
+    bfrun.c:1600-1641; output block t reads slots t - i, i < min(cblocks, blocks processed)).  While
+    every block in the ring entered with the delay and scales in force, that is conv(mixed input
+    delayed by d B, h cut to N - d partitions): one fftconvolve per distinct state.  The N blocks
+    after a run-time delay, input-scale or fscale change are summed slot by slot.  A cross-fade
+    block is (1 - w) old + w new, w = k / (B - 1), the old taps read through the same ring
+    (bfrun.c:1725-1777); output scales act on the block they are set for."""
     n = n_blocks * L
     y = np.zeros((n, n_out))
+    z = []                                            # per filter: unscaled time output
     w = np.arange(L) / (L - 1.0)
-    clamp = lambda d: min(max(int(d), 0), N - 1)
-    for f in filters:
-        xi = x[:, f.i]
+    clamp = lambda d: min(max(int(d), 0), N - 1)      # noqa: E731
+    for fi, f in enumerate(filters):
+        assert all(0 <= j < fi for j in f.in_f), "filter inputs must precede"
         starts = [s[0] for s in f.segs]
         st_of = [f.segs[int(np.searchsorted(starts, t, side="right")) - 1][1] for t in range(n_blocks)]
-        entry = [(clamp(st["delay"]), st["in_scale"]) for st in st_of]
-        cache = {}
+        entry = [(clamp(st["delay"]), st["in_scale"], st["fscale"]) for st in st_of]
+        cache, parts = {}, {}
+
+        def part(kind, v):
+            """sum_k a[k] x_k ("a") or sum_j fs[j] u_j ("fs") over the whole run"""
+            if (kind, v) not in parts:
+                m = np.zeros(n)
+                for k, c in enumerate(f.ins if kind == "a" else f.in_f):
+                    m += v[k] * (x[:n, c] if kind == "a" else z[c])
+                parts[(kind, v)] = m
+            return parts[(kind, v)]
+
+        def mixed(a, fs):
+            return part("a", a) + part("fs", fs) if f.in_f else part("a", a)
+
+        def window(s):
+            """the 2L window block s put in the ring"""
+            _, a, fs = entry[s]
+            w2 = np.zeros(2 * L)
+            w2[L:] = part("a", a)[s * L:(s + 1) * L]
+            if f.in_f:
+                w2[L:] += part("fs", fs)[s * L:(s + 1) * L]
+            if s >= 1:
+                w2[:L] = part("a", a)[(s - 1) * L:s * L]
+                if f.in_f:
+                    w2[:L] += part("fs", entry[s - 1][2])[(s - 1) * L:s * L]
+            return w2
 
         def full(st):
             d = clamp(st["delay"])
-            key = (id(st["taps"]), d, st["in_scale"])
+            key = (id(st["taps"]), d, st["in_scale"], st["fscale"])
             if key not in cache:
                 h = st["taps"][:(N - d) * L]
                 xd = np.zeros(n)
-                xd[d * L:] = xi[:n - d * L]
-                cache[key] = fftconvolve(xd, h)[:n] * st["in_scale"] if len(h) else np.zeros(n)
+                xd[d * L:] = mixed(st["in_scale"], st["fscale"])[:n - d * L]
+                cache[key] = fftconvolve(xd, h)[:n] if len(h) else np.zeros(n)
             return cache[key]
 
         def block(t, st):
-            d, a = clamp(st["delay"]), st["in_scale"]
-            if all(entry[s] == (d, a) for s in range(max(0, t - N + 1), t + 1)):
-                return full(st)[t * L:(t + 1) * L] * st["out_scale"]
+            d = clamp(st["delay"])
+            key = (d, st["in_scale"], st["fscale"])
+            if all(entry[s] == key for s in range(max(0, t - N + 1), t + 1)) and \
+                    (t < N or entry[t - N][2] == st["fscale"]):
+                return full(st)[t * L:(t + 1) * L]
             h = st["taps"][:(N - d) * L]
             cb = (len(h) + L - 1) // L
             out = np.zeros(L)
             for i in range(min(cb, t + 1, N)):
                 j = (t - i) % N
                 writers = [s for s in range(t + 1) if (s + entry[s][0]) % N == j]
-                if not writers:
-                    continue
-                s = writers[-1]
-                out += entry[s][1] * _window_out(xi, s, h[i * L:(i + 1) * L], L)
-            return out * st["out_scale"]
+                if writers:
+                    out += _window_out(window(writers[-1]), h[i * L:(i + 1) * L], L)
+            return out
 
+        zf = np.zeros(n)
         for t in range(n_blocks):
             k = int(np.searchsorted(starts, t, side="right")) - 1
             t0, st, fade = f.segs[k]
             r = block(t, st)
             if fade and t == t0 and k > 0:
-                r = (1 - w) * block(t, f.segs[k - 1][1]) + w * r
-            y[t * L:(t + 1) * L, f.o] += r
+                r = (1 - w) * block(t, dict(st, taps=f.segs[k - 1][1]["taps"])) + w * r
+            zf[t * L:(t + 1) * L] = r
+            for c, g in zip(f.outs, st["out_scale"]):
+                y[t * L:(t + 1) * L, c] += g * r
+        z.append(zf)
     return y
+
+
+# ------------------------------------------------------------------ networks (cases.build specs)
+
+class Network:
+    """the model of a filter network given as a cases.build spec (coeffs [(taps, scale, n_blocks)],
+    filters [add_filter keywords]), and of the run-time calls made on it: act(t, a) for a call
+    issued before block t, a one of ("coeff", f, c), ("scale", f, io, idx, v), ("fscale", f, idx,
+    v), ("delay", f, d) -- the tuples cases.act() hands an engine"""
+
+    def __init__(self, spec):
+        self.spec, self.L, self.N = spec, spec["L"], spec["N"]
+        self.cur = [fd.get("coeff", -1) for fd in spec["filters"]]
+        self.filters = [Filter(fd.get("in_ch", ()), fd.get("out_ch", ()), self.taps(fd.get("coeff", -1)),
+                               fd.get("delayblocks", 0),
+                               fd.get("in_scale"), fd.get("out_scale"), fd.get("in_f", ()), fd.get("in_fscale"))
+                        for fd in spec["filters"]]
+
+    def taps(self, c):
+        if c < 0:
+            return DIRAC
+        t, scale, nb = self.spec["coeffs"][c]
+        return coeff(t, self.L, scale, nb)
+
+    def act(self, t, a):
+        f = self.filters[a[1]]
+        if a[0] == "coeff":
+            fade = bool(self.spec["filters"][a[1]].get("crossfade")) and a[2] != self.cur[a[1]]
+            self.cur[a[1]] = a[2]
+            f.change(t, fade=fade, taps=self.taps(a[2]))
+        elif a[0] == "scale":
+            f.set_scale(t, a[2], a[3], a[4])
+        elif a[0] == "fscale":
+            f.set_fscale(t, a[2], a[3])
+        elif a[0] == "delay":
+            f.change(t, delay=a[2])
+
+    def output(self, x, n_blocks, actions=None):
+        for t in sorted(actions or {}):
+            for a in actions[t]:
+                self.act(t, a)
+        return output(x, self.filters, self.L, self.N, self.spec["n_out"], n_blocks)
