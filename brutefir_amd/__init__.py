@@ -18,6 +18,7 @@ IN, OUT = 0, 1
 RT_SPIN, RT_NO_GRAPH, RT_COPY_ENGINE, RT_OVERLAP = 1, 2, 4, 8      # bfhip_engine_rt_begin flags
 COEFF_WATCH, COEFF_LAZY = 1, 2                                       # bfhip_engine_add_coeff_processed_blocks flags
 ST_NONFINITE, ST_SAFETY = 1, 2
+UNDEFINED_SUBDELAY = -100                                            # BFHIP_UNDEFINED_SUBDELAY
 
 
 class BfhipError(RuntimeError):
@@ -187,6 +188,10 @@ def lib():
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_mute.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_get_delay.argtypes = [vp, ci, ci]
+    L.bfhip_nupc_enable_subdelay.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_set_subdelay.argtypes = [vp, ci, ci, ci]
+    L.bfhip_nupc_get_subdelay.argtypes = [vp, ci, ci]
+    L.bfhip_selftest_subdelay_filter.argtypes = [ci, ci, ci, vp]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -667,6 +672,22 @@ class Nupc:
     def get_delay(self, io, ch):
         """the delay in force (curdelay)"""
         return self._chk(lib().bfhip_nupc_get_delay(self.h, io, ch))
+
+    # per-channel sub-sample delay (sdf_length: / subdelay:), hundredths of a sample in (-100, 100)
+    def enable_subdelay(self, sdf_length, beta=9.0):
+        """before finalize; filters of 2 * sdf_length + 1 taps"""
+        self._chk(lib().bfhip_nupc_enable_subdelay(self.h, sdf_length, beta))
+
+    def set_subdelay(self, io, ch, value):
+        """before finalize: which channels have a filter (UNDEFINED_SUBDELAY = none) and its initial
+        value; after it: the value, in force from the next block call"""
+        self._chk(lib().bfhip_nupc_set_subdelay(self.h, io, ch, value))
+
+    def get_subdelay(self, io, ch):
+        """the value in force, UNDEFINED_SUBDELAY for a channel without a filter"""
+        if io not in (IN, OUT) or not 0 <= ch < (self.n_out if io == OUT else self.n_in):
+            raise BfhipError("get_subdelay: bad argument")     # (a value may be negative: no code to tell by)
+        return lib().bfhip_nupc_get_subdelay(self.h, io, ch)
 
 
 def device_count():

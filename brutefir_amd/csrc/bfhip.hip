@@ -34,6 +34,7 @@
 #include "conv_shared.h"
 #include "dither_init.h"
 #include "kernels.h"
+#include "subdelay_filter.h"
 #include "bigfft.h"
 
 using namespace bfhip;
@@ -2423,43 +2424,7 @@ int rt_capture(bfhip_engine *e, int p) {
 
 namespace {
 
-
-// Kaiser window exactly as the reference applies it to its sub-sample filters
-// (firwindow.c:12-160 via delay.c:56-76; note the window is applied twice when offset != 0)
-double sd_bessel_i0(double x) {
-    double n = 1.0, a = 1.0, sum = 1.0;
-    const double h = x / 2.0;
-    do { a *= h; a /= n; sum += a * a; n += 1.0; } while (a != 0.0 && std::isfinite(sum));
-    return sum;
-}
-
-template <typename T>
-void sd_make_filter(std::vector<T> &f, int half, double offset, double beta) {
-    const int len = 2 * half + 1;
-    f.assign(len, (T)0);
-    if (offset == 0.0) { f[half] = (T)1; return; }            // delay.c:476-483: a unit pulse
-    for (int n = 0; n < len; n++) {
-        const double x = M_PI * ((double)(n - half) - offset);
-        f[n] = (T)(x == 0.0 ? 1.0 : sin(x) / x);
-    }
-    const double inv = 1.0 / sd_bessel_i0(beta);
-    auto kaiser = [&](double x) {
-        if (x < -1.0) x = -1.0;
-        if (x > 1.0) x = 1.0;
-        return sd_bessel_i0(beta * sqrt(1.0 - x * x)) * inv;
-    };
-    int max = half + (int)floor(offset);
-    offset -= floor(offset);
-    if (fabs(offset) < 1e-20) offset = 0.0;
-    double step = 1.0 / ((double)max + offset);
-    if (offset == 0.0) max -= 1;
-    int n = 0;
-    for (; n <= max; n++) { const double y = kaiser(-1.0 + (double)n * step); f[n] = (T)(f[n] * y); f[n] = (T)(f[n] * y); }
-    if (offset == 0.0) max += 1;
-    step = 1.0 / ((double)(len - max - 1) - offset);
-    for (; n < len; n++) { const double y = kaiser(((double)(n - max) - offset) * step); f[n] = (T)(f[n] * y); f[n] = (T)(f[n] * y); }
-}
-
+// (the filters themselves: subdelay_filter.h, shared with the non-uniform convolver)
 int subdelay_setup(bfhip_engine *e) {
     if (e->sdf_length <= 0) return BFHIP_OK;
     int n_slots[2] = {0, 0};
@@ -2468,18 +2433,7 @@ int subdelay_setup(bfhip_engine *e) {
             e->sd_slot[io][v] = e->subdelay[io][v] != -100 ? n_slots[io]++ : -1;      // bfrun.c:1133-1142
     if (n_slots[0] + n_slots[1] == 0) { e->sdf_length = 0; return BFHIP_OK; }
     // bank: index 99 + subdelay, subdelay in (-100, 100) hundredths of a sample (BF_SAMPLE_SLOTS)
-    std::vector<unsigned char> bank((size_t)199 * e->sd_flen * e->rs);
-    for (int sd = -99; sd <= 99; sd++) {
-        if (e->rs == 4) {
-            std::vector<float> f;
-            sd_make_filter(f, e->sdf_length, (double)sd / 100, 9.0);
-            memcpy(bank.data() + (size_t)(99 + sd) * e->sd_flen * 4, f.data(), f.size() * 4);
-        } else {
-            std::vector<double> f;
-            sd_make_filter(f, e->sdf_length, (double)sd / 100, 9.0);
-            memcpy(bank.data() + (size_t)(99 + sd) * e->sd_flen * 8, f.data(), f.size() * 8);
-        }
-    }
+    const std::vector<unsigned char> bank = sd_make_bank(e->sdf_length, e->rs);
     HIPCHK(dev_alloc(&e->d_sd_bank, bank.size()));
     HIPCHK(hipMemcpy(e->d_sd_bank, bank.data(), bank.size(), hipMemcpyHostToDevice));
     for (int io = 0; io < 2; io++) {

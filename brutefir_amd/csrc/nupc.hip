@@ -36,6 +36,7 @@
 #include "alloc.h"
 #include "dither_init.h"
 #include "kernels.h"
+#include "subdelay_filter.h"
 
 using namespace bfhip;
 
@@ -94,15 +95,91 @@ __device__ __forceinline__ void emit_hand_off(int *__restrict__ status, unsigned
     }
 }
 
+// ---- per-channel sub-sample delay (subdelay: / sdf_length; delay.c:416-442 at a period of L0)
+//
+// What the reference computes per period is the causal FIR  y[t] = sum_k h[k] x[t - k]  over the
+// channel's stream, h one of the 199 filters of the bank (subdelay_filter.h) and the last `bs`
+// unfiltered samples carried from period to period.  This period's value of every channel of a
+// side travels in the kernel arguments (-100: the channel has no filter), so a change needs no
+// host wait and reaches the device with the block call it was made before.
+constexpr int kSdChannels = 256;   // channels per side when the side uses sub-delay (BF_MAXCHANNELS)
+constexpr int kSdTile = 2048;      // frames filtered per pass through LDS
+constexpr int kSdMaxBs = 1024;     // largest filter block size: 4 history samples per thread
+struct NupcSdVals { signed char v[kSdChannels]; };
+template <typename T> struct NupcSd {
+    const T *bank;                 // [199][flen] taps, index 99 + value
+    T *hist;                       // [channels of the side][bs]: the last bs unfiltered samples
+    int bs, flen, tile;            // tile = min(L0, kSdTile); bs <= tile, both powers of two
+    NupcSdVals vals;
+};
+static size_t nupc_sd_lds(int bs, int flen, int tile, int rs) { return (size_t)(bs + tile + flen) * rs; }
+
+// One channel's period, by its whole workgroup (256 threads, every thread calls): src(n) is the
+// unfiltered sample of frame n, each asked for once and in order of the tiles; sink(n, y) takes
+// the filtered one.  LDS: xx[bs + tile] = [history | tile], hh[flen] the taps, so no tap and no
+// sample is read from global memory more than once.  L0 above the tile is filtered tile by tile
+// with the history moved down in between.
+template <typename T, typename Src, typename Sink>
+__device__ __forceinline__ void
+sd_fir_period(unsigned char *smem, const NupcSd<T> &sd, int ch, int L0, Src src, Sink sink) {
+    const int tid = threadIdx.x, bs = sd.bs, flen = sd.flen, tile = sd.tile;
+    T *xx = reinterpret_cast<T *>(smem), *hh = xx + bs + tile;
+    const T *taps = sd.bank + (size_t)(99 + sd.vals.v[ch]) * flen;
+    T *hist = sd.hist + (size_t)ch * bs;
+    for (int k = tid; k < flen; k += 256) hh[k] = taps[k];
+    for (int n = tid; n < bs; n += 256) xx[n] = hist[n];
+    for (int t0 = 0; t0 < L0; t0 += tile) {
+        for (int n = tid; n < tile; n += 256) xx[bs + n] = src(t0 + n);
+        __syncthreads();
+        for (int n = tid; n < tile; n += 256) {
+            T acc = (T)0;
+            for (int k = 0; k < flen; k++) acc += hh[k] * xx[bs + n - k];      // flen <= bs: index >= 1
+            sink(t0 + n, acc);
+        }
+        T keep[kSdMaxBs / 256];
+#pragma unroll
+        for (int i = 0; i < kSdMaxBs / 256; i++) { const int n = tid + i * 256; if (n < bs) keep[i] = xx[tile + n]; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kSdMaxBs / 256; i++) { const int n = tid + i * 256; if (n < bs) xx[n] = keep[i]; }
+    }
+    for (int n = tid; n < bs; n += 256) hist[n] = xx[n];          // each thread's own writes: no barrier
+}
+
+// Input side, one launch per period behind the delay / mute step: one workgroup per input channel
+// converts the slot's L0 raw frames with load_raw -- the conversion the engines' input transform
+// uses -- into the ring of reals the segment engines read ([frame][n_in], interleaved), through the
+// FIR for a channel that has a filter.
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_subdelay_in_kernel(const uint8_t *__restrict__ raw, const DevFormat *__restrict__ fmt, T *__restrict__ real,
+                        int n_in, int L0, const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
+    const int ch = blockIdx.x;
+    const DevFormat f = fmt[ch];
+    const uint8_t *base = raw + f.byte_offset;
+    const size_t stride = (size_t)f.sample_spacing * f.bytes;
+    if (sd.vals.v[ch] == -100) {
+        for (int n = threadIdx.x; n < L0; n += 256) real[(size_t)n * n_in + ch] = load_raw<T>(base + (size_t)n * stride, f);
+        return;
+    }
+    sd_fir_period<T>(sd_smem, sd, ch, L0, [&](int n) { return load_raw<T>(base + (size_t)n * stride, f); },
+                     [&](int n, T y) { real[(size_t)n * n_in + ch] = y; });
+}
+
 // output block b: L_0 frames out of the ring (emit_take), scaled into output units (output gain
 // folded into inv_scale), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114),
-// ring region cleared.  One workgroup per output channel.
-template <typename T>
+// ring region cleared.  One workgroup per output channel.  SD: the output side uses sub-delay; a
+// channel that has a filter runs the FIR over the scaled reals -- the values it would have been
+// quantised from -- and quantises the result (sd_fir_period); the others take the plain path.
+template <typename T, bool SD>
 __global__ __launch_bounds__(256) void
 nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
                  long long rel0, int F, const DevFormat *__restrict__ fmt, const double *__restrict__ inv_scale,
                  DevOverflow *__restrict__ over, uint8_t *__restrict__ raw, double safety_limit,
-                 int *__restrict__ status, unsigned int *__restrict__ arrive, int *__restrict__ host_status) {
+                 int *__restrict__ status, unsigned int *__restrict__ arrive, int *__restrict__ host_status,
+                 const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
     const int ch = blockIdx.x, tid = threadIdx.x;
     const DevFormat f = fmt[ch];
     DevOverflow of = over[ch];
@@ -111,8 +188,13 @@ nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long
     const T sc = (T)inv_scale[ch];
     Quantiser<T> qz;
     qz.init(f, of, safety_limit);
-    for (int n = tid; n < L0; n += 256)
-        qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
+    if (SD && sd.vals.v[ch] != -100)
+        sd_fir_period<T>(sd_smem, sd, ch, L0,
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                         [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
+    else
+        for (int n = tid; n < L0; n += 256)
+            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
     qz.reduce(tid, 256);
     if (tid == 0) {
         qz.commit(of);
@@ -125,10 +207,11 @@ nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long
 // the emit step of a convolver with dithered outputs (launched instead of nupc_emit_kernel, same
 // grid).  A channel without a dither slot (slot[ch] < 0) is requantised exactly as there.  A
 // dithered one stages its L_0 blended, scaled reals -- the very values nupc_emit_kernel would
-// hand to the quantiser -- in stage[slot][L0], and wave 0 runs the HP-TPDF chain over them
-// (dither_chain, kernels.h: the uniform engine's dither pass).  The chain ORs its status bits in
-// before thread 0 takes part in the hand-off, so they reach the host with this block's call.
-template <typename T>
+// hand to the quantiser, behind the sub-delay FIR if the channel has a filter -- in
+// stage[slot][L0], and wave 0 runs the HP-TPDF chain over them (dither_chain, kernels.h: the
+// uniform engine's dither pass).  The chain ORs its status bits in before thread 0 takes part in
+// the hand-off, so they reach the host with this block's call.
+template <typename T, bool SD>
 __global__ __launch_bounds__(256) void
 nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out,
                         int L0, long long rel0, int F, const DevFormat *__restrict__ fmt,
@@ -136,20 +219,27 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
                         double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
                         int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
                         DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
-                        const T *__restrict__ randmap /* index -256..255 (centre pointer) */) {
+                        const T *__restrict__ randmap /* index -256..255 (centre pointer) */, const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
     __shared__ T rmap[512];
     const int ch = blockIdx.x, tid = threadIdx.x;
     const int slot = dslot[ch];
     const DevFormat f = fmt[ch];
     const T sc = (T)inv_scale[ch];
+    const bool fir = SD && sd.vals.v[ch] != -100;
     if (slot < 0) {
         DevOverflow of = over[ch];
         uint8_t *base = raw + f.byte_offset;
         const size_t stride = (size_t)f.sample_spacing * f.bytes;
         Quantiser<T> qz;
         qz.init(f, of, safety_limit);
-        for (int n = tid; n < L0; n += 256)
-            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
+        if (fir)
+            sd_fir_period<T>(sd_smem, sd, ch, L0,
+                             [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                             [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
+        else
+            for (int n = tid; n < L0; n += 256)
+                qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
         qz.reduce(tid, 256);
         if (tid == 0) {
             qz.commit(of);
@@ -160,7 +250,12 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
         return;
     }
     T *x = stage + (size_t)slot * L0;
-    for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc;
+    if (fir)
+        sd_fir_period<T>(sd_smem, sd, ch, L0,
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                         [&](int n, T y) { x[n] = y; });
+    else
+        for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc;
     for (int i = tid; i < 512; i += 256) rmap[i] = randmap[i - 256];
     __syncthreads();                  // the staged samples are visible to wave 0 (same workgroup)
     if (tid < 64) {
@@ -262,6 +357,9 @@ nupc_delay_kernel(const NupcDelayJobs jobs, uint8_t *__restrict__ raw, int F, in
 struct NupcDelay {
     int maxdelay = -1;             // < 0: fixed
     int req = 0;                   // before finalize the initial delay, after it the requested one
+    int extra = 0;                 // whole frames added at finalize to a channel without a sub-delay filter
+                                   // on a side that uses sub-delay (dai.c:230-243): part of req, maxdelay
+                                   // and curdelay from then on, never reported
     bool muted = false;
     int curdelay = 0, cur = 0, n_full = 0, n_rest = 0, n_full_cap = 0, F = 0, ss = 0;
     uint8_t *arena = nullptr;      // null: no line (a delay of 0 that cannot change)
@@ -420,6 +518,15 @@ struct bfhip_nupc {
     // integer delay and mute per raw channel (bfhip_nupc_set_delay / _set_mute): [io][channel]
     std::vector<NupcDelay> dl[2];
     std::vector<NupcDelayJob> dl_jobs;     // this period's jobs of one side (host scratch)
+    // sub-sample delay (bfhip_nupc_enable_subdelay / _set_subdelay): [io][channel] values in
+    // hundredths of a sample, -100 = the channel has no filter
+    int sdf_length = 0, sd_flen = 0, sd_bs = 0;
+    std::vector<int> sd[2];
+    bool sd_use[2] = {false, false};       // the side has a filter (fixed at finalize)
+    void *d_sd_bank = nullptr;             // [199][sd_flen] reals
+    void *d_sd_hist[2] = {nullptr, nullptr};   // [channels][sd_bs] reals: unfiltered history
+    DevFormat *d_fmt_in = nullptr;         // input formats for the conversion kernel
+    uint8_t *d_in_real = nullptr;          // [in_frames][n_in] reals: the ring the engines read instead of d_in
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
@@ -468,6 +575,8 @@ bfhip_nupc *bfhip_nupc_create(int device, int realsize, int n_in, int n_out, int
     n->gain.assign(n_out, 1.0);
     n->dl[0].resize(n_in);
     n->dl[1].resize(n_out);
+    n->sd[0].assign(n_in, BFHIP_UNDEFINED_SUBDELAY);
+    n->sd[1].assign(n_out, BFHIP_UNDEFINED_SUBDELAY);
     return n;
 }
 
@@ -487,7 +596,8 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
     void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive,
-                 n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage};
+                 n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage,
+                 n->d_sd_bank, n->d_sd_hist[0], n->d_sd_hist[1], n->d_fmt_in, n->d_in_real};
     for (void *q : p) if (q) (void)hipFree(q);
     for (auto &side : n->dl) for (auto &d : side) if (d.arena) (void)hipFree(d.arena);
     if (n->h_status) (void)hipHostFree(n->h_status);
@@ -609,6 +719,29 @@ int bfhip_nupc_finalize(bfhip_nupc *n) {
 
 static int nupc_finalize_impl(bfhip_nupc *n) {
     OWNER(n);
+    for (int io = 0; io < 2; io++) {
+        for (size_t ch = 0; ch < n->sd[io].size(); ch++) {
+            if (n->sd[io][ch] == BFHIP_UNDEFINED_SUBDELAY) continue;
+            if (n->sdf_length <= 0)
+                return nfail(BFHIP_EINVAL, std::string("nupc: ") + (io ? "output " : "input ") + std::to_string(ch) +
+                             " has a sub-sample delay but bfhip_nupc_enable_subdelay was not called");
+            n->sd_use[io] = true;
+        }
+        if (n->sd_use[io] && n->sd[io].size() > (size_t)kSdChannels)
+            return nfail(BFHIP_EINVAL, "nupc: a side that uses sub-sample delay can have at most " + std::to_string(kSdChannels) + " channels");
+        if (!n->sd_use[io]) continue;
+        // a channel without a filter follows the filtered ones sdf_length whole frames later, through
+        // its integer delay line (dai.c:205-215, 230-243); a fixed line stays fixed
+        for (size_t ch = 0; ch < n->sd[io].size(); ch++) {
+            if (n->sd[io][ch] != BFHIP_UNDEFINED_SUBDELAY) continue;
+            NupcDelay &d = n->dl[io][ch];
+            d.extra = n->sdf_length;
+            if (d.maxdelay > 0 && d.req > d.maxdelay) d.req = d.maxdelay;
+            if (d.maxdelay == 0) d.req = 0;
+            d.req += d.extra;
+            if (d.maxdelay >= 0) d.maxdelay += d.extra;
+        }
+    }
     NCHK(hipSetDevice(n->device));
     int prio_least = 0, prio_greatest = 0;
     NCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
@@ -689,13 +822,47 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
             NCHK(bfhip_internal_dev_alloc((void **)&d.arena, bytes));
             NCHK(hipMemset(d.arena, 0, bytes));
         }
+    if (n->sd_use[0] || n->sd_use[1]) {
+        const std::vector<unsigned char> bank = sd_make_bank(n->sdf_length, n->rs);
+        NCHK(bfhip_internal_dev_alloc(&n->d_sd_bank, bank.size()));
+        NCHK(hipMemcpy(n->d_sd_bank, bank.data(), bank.size(), hipMemcpyHostToDevice));
+        for (int io = 0; io < 2; io++) {
+            if (!n->sd_use[io]) continue;
+            const size_t bytes = n->sd[io].size() * n->sd_bs * n->rs;
+            NCHK(bfhip_internal_dev_alloc(&n->d_sd_hist[io], bytes));
+            NCHK(hipMemset(n->d_sd_hist[io], 0, bytes));
+        }
+    }
+    if (n->sd_use[0]) {
+        std::vector<DevFormat> dfi(n->n_in);
+        for (int ch = 0; ch < n->n_in; ch++) {
+            const bfhip_format &f = n->fmt[0][ch];
+            if (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->frame_bytes[0])
+                return nfail(BFHIP_EINVAL, "nupc: sub-sample delay on a side with a channel whose samples lie outside the raw frame");
+            dfi[ch].isfloat = f.isfloat; dfi[ch].swap = f.swap; dfi[ch].bytes = f.bytes; dfi[ch].sbytes = f.sbytes;
+            dfi[ch].sample_spacing = f.sample_spacing; dfi[ch].byte_offset = f.byte_offset; dfi[ch].alt = nullptr;
+        }
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_fmt_in, dfi.size() * sizeof(DevFormat)));
+        NCHK(hipMemcpy(n->d_fmt_in, dfi.data(), dfi.size() * sizeof(DevFormat), hipMemcpyHostToDevice));
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_in_real, (size_t)n->in_frames * n->n_in * n->rs));
+        NCHK(hipMemset(n->d_in_real, 0, (size_t)n->in_frames * n->n_in * n->rs));
+    }
     for (auto &c : n->coeff) n->can_switch = n->can_switch || c.size() > 1;
     if (n->can_switch) {
         NCHK(bfhip_internal_dev_alloc((void **)&n->d_acc2, (size_t)A * n->n_out * n->rs));
         NCHK(hipMemset(n->d_acc2, 0, (size_t)A * n->n_out * n->rs));
     }
     for (auto &s : n->seg) {
-        for (int ch = 0; ch < n->n_in; ch++) ECHK(bfhip_engine_set_format(s.eng, BFHIP_IN, ch, &n->fmt[0][ch]));
+        for (int ch = 0; ch < n->n_in; ch++) {
+            bfhip_format f = n->fmt[0][ch];
+            if (n->sd_use[0]) {
+                // the ring of converted (and filtered) reals; the format's scale stays where it is
+                // applied today, in the engines' filter scales
+                f.isfloat = 1; f.swap = 0; f.bytes = f.sbytes = n->rs;
+                f.sample_spacing = n->n_in; f.byte_offset = ch * n->rs;
+            }
+            ECHK(bfhip_engine_set_format(s.eng, BFHIP_IN, ch, &f));
+        }
         for (int ch = 0; ch < n->n_out; ch++) {
             bfhip_format f;
             f.isfloat = 1; f.swap = 0; f.bytes = f.sbytes = n->rs; f.scale = 1.0;
@@ -770,6 +937,56 @@ int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
         NCHK(hipGetLastError());
     }
     return BFHIP_OK;
+}
+
+// this period's sub-delay arguments of one side: the values in force now
+template <typename T> NupcSd<T> nupc_sd_args(const bfhip_nupc *n, int io) {
+    NupcSd<T> a;
+    memset(&a, 0, sizeof(a));
+    if (!n->sd_use[io]) return a;
+    a.bank = (const T *)n->d_sd_bank;
+    a.hist = (T *)n->d_sd_hist[io];
+    a.bs = n->sd_bs; a.flen = n->sd_flen; a.tile = std::min(n->seg[0].L, kSdTile);
+    memset(a.vals.v, -100, sizeof(a.vals.v));
+    for (size_t ch = 0; ch < n->sd[io].size(); ch++) a.vals.v[ch] = (signed char)n->sd[io][ch];
+    return a;
+}
+size_t nupc_sd_smem(const bfhip_nupc *n, int io) {
+    return n->sd_use[io] ? nupc_sd_lds(n->sd_bs, n->sd_flen, std::min(n->seg[0].L, kSdTile), n->rs) : 0;
+}
+
+// input side with sub-delay: the slot's raw frames (delayed and muted already) become the reals
+// of the same slot of the ring the segment engines read
+int nupc_subdelay_in(bfhip_nupc *n, const uint8_t *raw_slot, size_t wpos) {
+    const int L0 = n->seg[0].L;
+    uint8_t *real = n->d_in_real + wpos * (size_t)n->n_in * n->rs;
+    if (n->rs == 4)
+        hipLaunchKernelGGL(nupc_subdelay_in_kernel<float>, dim3(n->n_in), dim3(256), nupc_sd_smem(n, 0), n->stream, raw_slot,
+                           n->d_fmt_in, (float *)real, n->n_in, L0, nupc_sd_args<float>(n, 0));
+    else
+        hipLaunchKernelGGL(nupc_subdelay_in_kernel<double>, dim3(n->n_in), dim3(256), nupc_sd_smem(n, 0), n->stream, raw_slot,
+                           n->d_fmt_in, (double *)real, n->n_in, L0, nupc_sd_args<double>(n, 0));
+    NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+// one emit launch: the four kernels (dither or not, sub-delay on the output side or not) share
+// their leading arguments
+template <typename T, bool SD>
+void nupc_emit_launch(bfhip_nupc *n, void *acc_old, void *acc_new, unsigned long long opos, long long rel0, void *rawout_dev) {
+    const int L0 = n->seg[0].L;
+    const NupcSd<T> sd = nupc_sd_args<T>(n, 1);
+    const size_t smem = SD ? nupc_sd_smem(n, 1) : 0;
+    if (!n->dither_ch.empty())
+        hipLaunchKernelGGL((nupc_emit_dither_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old,
+                           (T *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
+                           n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
+                           n->d_dither_slot, (T *)n->d_dither_stage, (DitherState<T> *)n->d_dither_state,
+                           n->d_dither_table, (int)n->dither_table.size(), (const T *)n->d_randmap + 256, sd);
+    else
+        hipLaunchKernelGGL((nupc_emit_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old, (T *)acc_new,
+                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
+                           (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status, sd);
 }
 
 // point a segment engine's filters at an assignment (a plan rebuild at its next call if any moved)
@@ -858,6 +1075,8 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     // input delay and mute on the slot, before any segment (or ev_in, which the background
     // segment streams wait on) reads it
     { const int r = nupc_delay_side(n, BFHIP_IN, n->d_in + wpos * n->frame_bytes[0]); if (r < 0) return r; }
+    // sub-delay on the input side: convert (and filter) the slot once, in front of all segments
+    if (n->sd_use[0]) { const int r = nupc_subdelay_in(n, n->d_in + wpos * n->frame_bytes[0], wpos); if (r < 0) return r; }
     if (n->gain_dirty) {
         // output gains set since the last block: in force from this block's first frame
         NCHK(hipEventSynchronize(n->ev_gain));                    // the previous upload has read h_inv
@@ -883,7 +1102,7 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
             if (mode == 2) acc2 = n->ring(1 - n->cur);
             if (need_old) n->old_hi = std::max(n->old_hi, (long long)(pos + s.L));
         }
-        const uint8_t *in = n->d_in + rpos * n->frame_bytes[0];
+        const uint8_t *in = n->sd_use[0] ? n->d_in_real + rpos * (size_t)n->n_in * n->rs : n->d_in + rpos * n->frame_bytes[0];
         if (s.delay_steps == 0) {
             { const int r = seg_run(n, s, in, mode); if (r < 0) return r; }
             { const int r = nupc_accumulate(n, s, pos, acc, acc2); if (r < 0) return r; }
@@ -913,28 +1132,13 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     // inside a switch window the old assignment's ring is read beside the new one's
     void *acc_old = n->ring(n->cur), *acc_new = n->sw ? n->ring(1 - n->cur) : nullptr;
     const long long rel0 = n->sw ? (long long)opos - n->t_sw : 0;
-    if (!n->dither_ch.empty()) {
-        const int tsz = (int)n->dither_table.size();
-        if (n->rs == 4)
-            hipLaunchKernelGGL(nupc_emit_dither_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)acc_old,
-                               (float *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
-                               n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
-                               n->d_dither_slot, (float *)n->d_dither_stage, (DitherState<float> *)n->d_dither_state,
-                               n->d_dither_table, tsz, (const float *)n->d_randmap + 256);
-        else
-            hipLaunchKernelGGL(nupc_emit_dither_kernel<double>, dim3(n->n_out), dim3(256), 0, n->stream, (double *)acc_old,
-                               (double *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
-                               n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
-                               n->d_dither_slot, (double *)n->d_dither_stage, (DitherState<double> *)n->d_dither_state,
-                               n->d_dither_table, tsz, (const double *)n->d_randmap + 256);
-    } else if (n->rs == 4)
-        hipLaunchKernelGGL(nupc_emit_kernel<float>, dim3(n->n_out), dim3(256), 0, n->stream, (float *)acc_old, (float *)acc_new,
-                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
-                           (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);
-    else
-        hipLaunchKernelGGL(nupc_emit_kernel<double>, dim3(n->n_out), dim3(256), 0, n->stream, (double *)acc_old, (double *)acc_new,
-                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
-                           (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status);
+    if (n->rs == 4) {
+        if (n->sd_use[1]) nupc_emit_launch<float, true>(n, acc_old, acc_new, opos, rel0, rawout_dev);
+        else nupc_emit_launch<float, false>(n, acc_old, acc_new, opos, rel0, rawout_dev);
+    } else {
+        if (n->sd_use[1]) nupc_emit_launch<double, true>(n, acc_old, acc_new, opos, rel0, rawout_dev);
+        else nupc_emit_launch<double, false>(n, acc_old, acc_new, opos, rel0, rawout_dev);
+    }
     NCHK(hipGetLastError());
     // output delay and mute on the quantised block (block() copies it out behind this)
     { const int r = nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev); if (r < 0) return r; }
@@ -1082,7 +1286,7 @@ int bfhip_nupc_set_maxdelay(bfhip_nupc *n, int io, int ch, int maxdelay) {
 
 int bfhip_nupc_set_delay(bfhip_nupc *n, int io, int ch, int delay) {
     if (!delay_channel_ok(n, io, ch) || delay < 0) return nfail(BFHIP_EINVAL, "nupc_set_delay: bad argument");
-    n->dl[io][ch].req = delay;                  // change_delay at the next block call ignores what it must
+    n->dl[io][ch].req = delay + n->dl[io][ch].extra;   // change_delay at the next block call ignores what it must
     return BFHIP_OK;
 }
 
@@ -1094,10 +1298,65 @@ int bfhip_nupc_set_mute(bfhip_nupc *n, int io, int ch, int muted) {
 
 int bfhip_nupc_get_delay(const bfhip_nupc *n, int io, int ch) {
     if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_get_delay: bad argument");
-    if (n->finalized) return n->dl[io][ch].curdelay;
+    if (n->finalized) return n->dl[io][ch].curdelay - n->dl[io][ch].extra;
     NupcDelay d = n->dl[io][ch];                // what finalize will start with
     (void)d.init(n->seg[0].L, 1);
     return d.curdelay;
+}
+
+// ---- run-time control: per-channel sub-sample delay -----------------------------------------
+
+int bfhip_nupc_enable_subdelay(bfhip_nupc *n, int sdf_length, double kaiser_beta) {
+    (void)kaiser_beta;       // parsed by the reference (sdf_beta) but its filters are built with 9 (delay.c:73)
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_enable_subdelay after finalize");
+    const int L0 = n->seg[0].L;
+    if (sdf_length < 1) return nfail(BFHIP_EINVAL, "Invalid half filter length " + std::to_string(sdf_length) + ".");
+    if (2 * sdf_length + 1 > L0) return nfail(BFHIP_EINVAL, "The filter_length must be at least 2 x sdf_length + 1.");
+    int bs = 1;
+    while (bs < 2 * sdf_length + 1) bs <<= 1;
+    if (L0 % bs != 0)
+        return nfail(BFHIP_EINVAL, "Incompatible fragment/filter sizes (" + std::to_string(L0) + "/" + std::to_string(2 * sdf_length + 1) + ").");
+    if (bs > kSdMaxBs)
+        return nfail(BFHIP_EINVAL, "nupc_enable_subdelay: sdf_length above " + std::to_string(kSdMaxBs / 2 - 1) + " is not supported");
+    n->sdf_length = sdf_length; n->sd_flen = 2 * sdf_length + 1; n->sd_bs = bs;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_subdelay(bfhip_nupc *n, int io, int ch, int subdelay) {
+    if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_set_subdelay: bad argument");
+    const bool in_range = subdelay > -100 && subdelay < 100;
+    if (!n->finalized) {
+        if (!in_range && subdelay != BFHIP_UNDEFINED_SUBDELAY) return nfail(BFHIP_EINVAL, "nupc_set_subdelay: value out of range (-100, 100)");
+        n->sd[io][ch] = subdelay;
+        return BFHIP_OK;
+    }
+    // set_subdelay, bfrun.c:520-541
+    if (n->sd[io][ch] == BFHIP_UNDEFINED_SUBDELAY) return nfail(BFHIP_EINVAL, "nupc_set_subdelay: the channel has no sub-sample delay filter");
+    if (!in_range) return nfail(BFHIP_EINVAL, "nupc_set_subdelay: value out of range (-100, 100)");
+    n->sd[io][ch] = subdelay;                   // read by the next block call
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_get_subdelay(const bfhip_nupc *n, int io, int ch) {
+    if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_get_subdelay: bad argument");
+    return n->sd[io][ch];
+}
+
+// the taps the device filters with (no HIP call: the bank is made of these)
+int bfhip_selftest_subdelay_filter(int sdf_length, int subdelay, int realsize, void *out) {
+    if (sdf_length < 1 || subdelay <= -100 || subdelay >= 100 || (realsize != 4 && realsize != 8) || !out)
+        return nfail(BFHIP_EINVAL, "selftest_subdelay_filter: bad argument");
+    if (realsize == 4) {
+        std::vector<float> f;
+        sd_make_filter(f, sdf_length, (double)subdelay / 100, 9.0);
+        memcpy(out, f.data(), f.size() * 4);
+    } else {
+        std::vector<double> f;
+        sd_make_filter(f, sdf_length, (double)subdelay / 100, 9.0);
+        memcpy(out, f.data(), f.size() * 8);
+    }
+    return 2 * sdf_length + 1;
 }
 
 }  // extern "C"

@@ -135,8 +135,7 @@ int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);
  * kernel arguments: no host wait per period, and a side where no channel is muted or delayed
  * makes no launch at all.  An initial delay above a maxdelay > 0 starts at maxdelay (the
  * reference would overrun its buffer).  Packed 3-byte samples with a delay <= L0 hang the
- * reference (shift_samples); here they get a pure delay.  Sub-sample delay (subdelay: / sdf_length, and the
- * extra_delay dai.c:233-236 adds for it) is not provided.
+ * reference (shift_samples); here they get a pure delay.
  */
 /* before finalize; < 0: fixed (the reference's maxdelay: -1, the default); BFHIP_ESTATE after */
 int bfhip_nupc_set_maxdelay(bfhip_nupc *n, int io, int channel, int maxdelay);
@@ -149,6 +148,59 @@ int bfhip_nupc_set_delay(bfhip_nupc *n, int io, int channel, int delay_frames);
 int bfhip_nupc_set_mute(bfhip_nupc *n, int io, int channel, int muted);
 /* the delay in force (curdelay), for a CLI's "info" */
 int bfhip_nupc_get_delay(const bfhip_nupc *n, int io, int channel);
+
+/* ---- run-time control: per-channel sub-sample delay (sdf_length: / subdelay:, bfaccess->
+ * set_subdelay) -------------------------------------------------------------------------------
+ * The reference filters the time-domain reals of a channel once per period (bfrun.c:1497-1531,
+ * 1921-1925, delay.c:416-442); the convolver does the same once per block call of L0 frames, in
+ * front of all segments and behind the accumulator ring, so its output is the reference's at a
+ * period of L0 frames.  A side "uses sub-delay" when at least one of its channels has a filter.
+ *
+ * The filter is the causal FIR  y[t] = sum_k h_s[k] x[t - k]  over the channel's whole stream, h_s
+ * the reference's 2 * sdf_length + 1 taps for the value s in hundredths of a sample (s = 0: a unit
+ * pulse at tap sdf_length; else sample_sinc with its Kaiser window, beta 9, delay.c:56-76), x[t < 0]
+ * = 0.  A filtered channel is delayed by sdf_length + s / 100 samples.  A value set between block
+ * calls switches h from the next call's first frame and keeps reading the unfiltered history; there
+ * is no cross-fade (the reference's behaviour).
+ * Channels without a filter on a side that uses sub-delay get sdf_length whole frames of extra
+ * delay through their integer delay line (dai.c:205-215, 230-243): added to the delay and to a
+ * non-negative maxdelay; a fixed line (maxdelay < 0) stays fixed at delay + sdf_length (DESIGN.md
+ * section 7).  bfhip_nupc_get_delay keeps reporting the delay without the extra.
+ * Input side: mute and integer delay on the raw block as above, then raw -> real with the channel's
+ * format, then the FIR (zeros from a mute enter the filter's history).  One kernel launch per
+ * period converts the block into a ring of reals that every segment reads, however long it is and
+ * however late it is launched.
+ * Output side: cross-fade blend, output gain, the format's 1/scale, then the FIR, then dither,
+ * quantisation, and integer delay and mute on the raw block: the FIR's input is the value the
+ * output would have been quantised from without it (the dither section's definition), its history
+ * holds those scaled values, and the overflow structs and status bits count the filtered samples.
+ * Runs inside the emit step: no launch of its own.
+ * A side that does not use sub-delay makes no launch, allocates nothing and changes no byte.
+ * Limits: the filter block size bs (the smallest power of two >= 2 * sdf_length + 1) is at most
+ * 1024, i.e. sdf_length <= 511 (BFHIP_EINVAL above); any L0 is supported, blocks above 2048 frames
+ * are filtered 2048 frames at a time; a side that uses sub-delay has at most 256 channels.
+ * Cost (configs[4], 64-frame periods, sdf_length 31 on both inputs and both outputs, new values
+ * every 300 periods; tools/nupc_latency.py 64 --subdelay, profiles/nupc_subdelay_latency.jsonl):
+ * one more launch per period on the input side, none on the output side.  The per-period wall
+ * time with the filters (medians 0.057-0.072 ms over seven runs) lies inside the run-to-run band
+ * of the convolver without them (0.051-0.085 ms): the added cost is below what the host clock
+ * resolves.  Worst period 0.30 ms of the 1.33 ms period.
+ */
+/* before finalize (BFHIP_ESTATE after).  sdf_length >= 1, 2 * sdf_length + 1 <= L0 and L0 a
+   multiple of bs, with the reference's messages (delay.c:458-470); kaiser_beta is accepted and
+   ignored, as in the reference (delay.c:73) */
+int bfhip_nupc_enable_subdelay(bfhip_nupc *n, int sdf_length, double kaiser_beta);
+/* before finalize: BFHIP_UNDEFINED_SUBDELAY (-100, the default) = no filter on this raw channel; a
+   value in (-100, 100) = a filter with that initial value (finalize fails with BFHIP_EINVAL if
+   enable_subdelay was not called).  After finalize: the value of a channel that has a filter, in
+   force from the first frame of the next block call; a channel without a filter or a value outside
+   (-100, 100): BFHIP_EINVAL and nothing changes (bfrun.c:520-541) */
+int bfhip_nupc_set_subdelay(bfhip_nupc *n, int io, int channel, int subdelay);
+/* the value in force, -100 for a channel without a filter */
+int bfhip_nupc_get_subdelay(const bfhip_nupc *n, int io, int channel);
+/* tests: the 2 * sdf_length + 1 taps (realsize wide) the device filters with for `subdelay` in
+   (-100, 100); returns the tap count or a negative error.  Makes no HIP call. */
+int bfhip_selftest_subdelay_filter(int sdf_length, int subdelay, int realsize, void *out);
 
 #ifdef __cplusplus
 }

@@ -8,11 +8,13 @@ less than its duration.  Prints one JSON line: median / p99 / max milliseconds p
 bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, next to the
 uniform engine's block time and I/O delay for the same filters.
 
-    python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay]
+    python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
-outputs a maxdelay of 48 000 frames and new delays (seeded, up to 48 000) every 300 periods."""
+outputs a maxdelay of 48 000 frames and new delays (seeded, up to 48 000) every 300 periods;
+--subdelay gives both inputs and both outputs a sub-sample delay filter (sdf_length 31) and new
+values (seeded, in (-100, 100)) every 300 periods."""
 import argparse
 import json
 import os
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--out-format", default="FLOAT64_LE")
     ap.add_argument("--dither", action="store_true")
     ap.add_argument("--delay", action="store_true")
+    ap.add_argument("--subdelay", action="store_true")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
     seg_len, k = [], L0
@@ -52,6 +55,11 @@ def main():
         for o in range(2):
             nu.set_maxdelay(bf.OUT, o, 48000)
             nu.set_delay(bf.OUT, o, 1000 * (o + 1))
+    if a.subdelay:
+        nu.enable_subdelay(31)
+        for io in (bf.IN, bf.OUT):
+            for c in range(2):
+                nu.set_subdelay(io, c, 37 - 62 * c)
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -63,12 +71,17 @@ def main():
     gc.disable()                       # the timed loop allocates one small array per period
     ts = []
     drng = np.random.default_rng(9)
-    n_changes = 0
+    n_changes = n_sd_changes = 0
     for s in range(steps + 256):
         if a.delay and s % 300 == 299:
             for o in range(2):
                 nu.set_delay(bf.OUT, o, int(drng.integers(0, 48001)))
             n_changes += 1
+        if a.subdelay and s % 300 == 299:
+            for io in (bf.IN, bf.OUT):
+                for c in range(2):
+                    nu.set_subdelay(io, c, int(drng.integers(-99, 100)))
+            n_sd_changes += 1
         t0 = time.perf_counter()
         st, _ = nu.block(x[s & 7])
         ts.append(time.perf_counter() - t0)
@@ -82,6 +95,8 @@ def main():
         "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s" % (nu.taps, seg_len, seg_blk),
         "out_format": a.out_format, "dithered_outputs": [0, 1] if a.dither else [],
         "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
+        "subdelay": {"sdf_length": 31, "inputs": [0, 1], "outputs": [0, 1], "changes_every_periods": 300,
+                     "changes": n_sd_changes} if a.subdelay else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
