@@ -2002,10 +2002,11 @@ int do_subdelay_t(bfhip_engine *e, int io, const void *rawin_dev) {
     memcpy(pin, jobs.data(), jobs.size() * sizeof(SdJob<T>));
     HIPCHK(hipMemcpyAsync(e->d_sdjobs[io], pin, jobs.size() * sizeof(SdJob<T>), hipMemcpyHostToDevice, e->ls));
     HIPCHK(e->st_sd[io].queued(e->ls));
-    const size_t lds = (size_t)(e->sd_bs + e->L) * sizeof(T);
+    const int tile = sd_tile_frames(e->L, e->sd_bs, (int)sizeof(T));        // > 0: enable_subdelay
+    const size_t lds = (size_t)(e->sd_bs + tile) * sizeof(T);
     auto k = subdelay_fir_kernel<T>;
     HIPCHK(allow_lds(k, lds));
-    hipLaunchKernelGGL(k, dim3((unsigned)jobs.size()), dim3(256), lds, e->ls, (const SdJob<T> *)e->d_sdjobs[io], e->L, e->sd_bs, e->sd_flen);
+    hipLaunchKernelGGL(k, dim3((unsigned)jobs.size()), dim3(256), lds, e->ls, (const SdJob<T> *)e->d_sdjobs[io], e->L, e->sd_bs, e->sd_flen, tile);
     HIPCHK(hipGetLastError());
     return BFHIP_OK;
 }
@@ -2658,6 +2659,10 @@ int bfhip_engine_enable_subdelay(bfhip_engine *e, int sdf_length, double kaiser_
     int bs = 1;
     while (bs < 2 * sdf_length + 1) bs <<= 1;
     if (e->L % bs != 0) return fail(BFHIP_EINVAL, "Incompatible fragment/filter sizes (%d/%d).", e->L, 2 * sdf_length + 1);
+    // the FIR keeps bs frames of history in LDS beside the tile it filters (subdelay_fir_kernel)
+    if (sd_tile_frames(e->L, bs, e->rs) == 0)
+        return fail(BFHIP_EINVAL, "sdf_length %d is too long for the sub-sample delay filter: its %d-frame history "
+                                  "leaves no room in %d KiB of LDS.", sdf_length, bs, SD_LDS_BYTES / 1024);
     e->sdf_length = sdf_length; e->sd_flen = 2 * sdf_length + 1; e->sd_bs = bs;
     return BFHIP_OK;
 }

@@ -2155,7 +2155,10 @@ __global__ void vout_spread_overflow_kernel(const VOutJob *__restrict__ jobs, co
 // delay_subsample_update (delay.c:416-442) runs a small FFT overlap-save (convolver_td_*) over
 // the block; what it computes is the causal FIR  y[n] = sum_k h[k] x[n - k]  with h one of 199
 // Kaiser-windowed sinc filters of 2*sdf_length+1 taps and the history carried in a `rest`
-// buffer.  Here it is evaluated directly: one workgroup per channel, block + history in LDS.
+// buffer.  Here it is evaluated directly: one workgroup per channel, history + samples in LDS.
+// A block that fits the CU's LDS with its history is one tile; a longer one is walked in tiles of
+// sd_tile_frames() frames, the last bs unfiltered samples of a tile sliding down to be the next
+// tile's history (the output side runs in place: they are gone from memory by then).
 template <typename T> struct SdJob {
     const uint8_t *raw;     // raw samples (input side, converted on the fly) or null
     DevFormat fmt;          // of raw
@@ -2166,31 +2169,55 @@ template <typename T> struct SdJob {
                             // history NOT updated (the reference returns early)
 };
 
+constexpr int SD_LDS_BYTES = 160 * 1024;        // what one workgroup may take of a gfx950 CU
+
+// frames per tile of subdelay_fir_kernel: the whole block where [bs | L] fits, else the largest
+// multiple of 256 beside the history (a multiple of the workgroup size: see the slide in the
+// kernel); 0: not even one such tile fits, the combination cannot run
+inline int sd_tile_frames(int L, int bs, int realsize) {
+    const long long room = SD_LDS_BYTES / realsize - (long long)bs;
+    if (room >= L) return L;
+    return room < 256 ? 0 : (int)(room / 256 * 256);
+}
+
+template <typename T>
+__device__ __forceinline__ T sd_sample(const SdJob<T> &job, int n) {
+    if (job.raw) return load_raw<T>(job.raw + job.fmt.byte_offset + (size_t)n * job.fmt.sample_spacing * job.fmt.bytes, job.fmt);
+    return job.src[n];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void
-subdelay_fir_kernel(const SdJob<T> *__restrict__ jobs, int L, int bs, int flen) {
+subdelay_fir_kernel(const SdJob<T> *__restrict__ jobs, int L, int bs, int flen, int tile) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    T *xx = reinterpret_cast<T *>(smem);          // [bs + L] = [history | block]
+    T *xx = reinterpret_cast<T *>(smem);          // [bs + tile] = [history | tile]
     const SdJob<T> job = jobs[blockIdx.x];
     const int tid = threadIdx.x;
-    for (int n = tid; n < L; n += 256) {
-        T v;
-        if (job.raw) v = load_raw<T>(job.raw + job.fmt.byte_offset + (size_t)n * job.fmt.sample_spacing * job.fmt.bytes, job.fmt);
-        else v = job.src[n];
-        xx[bs + n] = v;
-    }
-    if (job.taps) for (int n = tid; n < bs; n += 256) xx[n] = job.rest[n];
-    __syncthreads();
     if (job.taps == nullptr) {
-        for (int n = tid; n < L; n += 256) job.dst[n] = xx[bs + n];
+        for (int n = tid; n < L; n += 256) job.dst[n] = sd_sample(job, n);
         return;
     }
-    for (int n = tid; n < L; n += 256) {
-        T acc = (T)0;
-        for (int k = 0; k < flen; k++) acc += job.taps[k] * xx[bs + n - k];
-        job.dst[n] = acc;
+    for (int n = tid; n < bs; n += 256) xx[n] = job.rest[n];
+    int tl = 0;
+    for (int t0 = 0; t0 < L; t0 += tile) {
+        if (t0 > 0) {
+            // the tail of the tile just filtered becomes the history.  tile % 256 == 0: a thread reads
+            // and writes only indices congruent to its own, in ascending order, so the overlapping
+            // move (tile < bs) needs no barrier inside
+            __syncthreads();
+            for (int n = tid; n < bs; n += 256) xx[n] = xx[n + tile];
+            __syncthreads();
+        }
+        tl = min(tile, L - t0);
+        for (int n = tid; n < tl; n += 256) xx[bs + n] = sd_sample(job, t0 + n);
+        __syncthreads();
+        for (int n = tid; n < tl; n += 256) {
+            T acc = (T)0;
+            for (int k = 0; k < flen; k++) acc += job.taps[k] * xx[bs + n - k];
+            job.dst[t0 + n] = acc;
+        }
     }
-    for (int n = tid; n < bs; n += 256) job.rest[n] = xx[L + n];
+    for (int n = tid; n < bs; n += 256) job.rest[n] = xx[tl + n];
 }
 
 // ------------------------------------------------------------------ K3d: HP-TPDF dithered requantiser

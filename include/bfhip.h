@@ -114,7 +114,10 @@ int bfhip_engine_set_mute(bfhip_engine *e, int io, int virt_channel, int muted);
    (BF_UNDEFINED_SUBDELAY) = the channel has no filter.  Which channels have one is fixed at
    finalize; the value may change at run time (bfaccess->set_subdelay).  A filtered channel is
    delayed by sdf_length + subdelay/100 samples (delay.c:416-505); a channel WITHOUT a filter that
-   shares a physical channel is delayed by sdf_length whole samples (bfrun.c:1152-1162). */
+   shares a physical channel is delayed by sdf_length whole samples (bfrun.c:1152-1162).  Any block
+   length works (long blocks are filtered in tiles); BFHIP_EINVAL where 2 * sdf_length + 1 rounded
+   up to a power of two reaches 64 Ki samples in float32, 32 Ki in float64: that much history
+   leaves the filter no room on the device. */
 #define BFHIP_UNDEFINED_SUBDELAY (-100)
 int bfhip_engine_enable_subdelay(bfhip_engine *e, int sdf_length, double kaiser_beta);
 int bfhip_engine_set_subdelay(bfhip_engine *e, int io, int virt_channel, int subdelay);

@@ -165,5 +165,99 @@ def act(e, a):
         e.set_fscale(a[1], a[2], a[3])
     elif a[0] == "delay":
         e.set_delayblocks(a[1], a[2])
+    elif a[0] == "subdelay":
+        e.set_subdelay(a[1], a[2], a[3])
+    elif a[0] == "mute":
+        e.set_mute(a[1], a[2], a[3])
     else:
         raise ValueError(a)
+
+
+# ------------------------------------------------------------------ the channel stage
+
+def build_channels(engine_cls, spec, ch, **kw):
+    """a cases.build spec with the channel stage xbar_ref.Channels describes (in_map / out_map,
+    in_fmt / out_fmt, delay, sdf_length, subdelay, dither, rate, max_size) -> engine (oracle or HIP).
+    mute_from is run-time: mute_actions()"""
+    e = engine_cls(spec["L"], spec["N"], spec["rs"], spec["n_in"], spec["n_out"], **kw)
+    maps = [list(ch.get("in_map", range(spec["n_in"]))), list(ch.get("out_map", range(spec["n_out"])))]
+    for io in range(2):
+        if "in_map" in ch or "out_map" in ch:
+            e.map_channels(io, maps[io])
+        e.set_interleaved_phys(io, ch["in_fmt" if io == 0 else "out_fmt"], max(maps[io]) + 1)
+    if ch.get("sdf_length"):
+        e.enable_subdelay(ch["sdf_length"])
+        for (io, v), value in sorted(ch.get("subdelay", {}).items()):
+            e.set_subdelay(io, v, value)
+    for (io, v), d in sorted(ch.get("delay", {}).items()):
+        e.set_delay(io, v, d)
+        e.set_maxdelay(io, v, ch["maxdelay"])
+    if spec.get("safety_limit"):
+        e.set_safety_limit(spec["safety_limit"])
+    for taps, scale, nb in spec.get("coeffs", []):
+        e.add_coeff(taps, scale, nb)
+    if ch.get("dither"):
+        e.enable_dither(list(ch["dither"]), ch.get("rate", 44100), ch.get("max_size", 0))
+    for f in spec["filters"]:
+        e.add_filter(**f)
+    if hasattr(e, "finalize"):
+        e.finalize()
+    return e
+
+
+def mute_actions(ch, actions=None):
+    """the run-time calls of ch["mute_from"] merged into an action table {block: [tuples]}"""
+    out = {t: list(a) for t, a in (actions or {}).items()}
+    for (io, v), t in sorted(ch.get("mute_from", {}).items()):
+        out.setdefault(t, []).append(("mute", io, v, 1))
+    return out
+
+
+def subdelay_taps(half, rs):
+    """-> taps_of(value): the engine's sub-sample filter for `value` hundredths of a sample, as float64
+    (bfhip_selftest_subdelay_filter runs on the host; tests/test_nupc_subdelay_abi.py pins it to the
+    oracle)"""
+    import brutefir_amd as bf
+    cache = {}
+
+    def taps_of(value):
+        if value not in cache:
+            out = np.zeros(2 * half + 1, np.float32 if rs == 4 else np.float64)
+            assert bf.lib().bfhip_selftest_subdelay_filter(half, value, rs, out.ctypes.data) == 2 * half + 1
+            cache[value] = out.astype(np.float64)
+        return cache[value]
+    return taps_of
+
+
+def channel_stage(L, N, rs, outfmt, half, dither=(), loud=1.0, seed=5, rate=300, subdelay=None):
+    """(spec, ch, actions): 5 virtual channels a side on 3 physical ones (0,1,0,1 and a 1:1 channel),
+    every feature of the channel stage at once.  Member delays 0, 1, L - 1, L and 2L + 3; an input
+    and an output member muted from block N + 1 on; with half > 0 sub-sample filters on a shared
+    input (37), the 1:1 input read from raw (-99, then 12), a member of a shared output (99, then
+    -37) and the 1:1 output in place (0: the pure delay), the changes before block N + 2; subdelay:
+    other filtered channels {(io, v): value}, without run-time changes"""
+    rng = np.random.default_rng(seed + L)
+    n = (N - 1) * L + L // 2 + 1                         # flat taps that end mid-partition
+    coeffs = [(rng.standard_normal(n) / np.sqrt(n) / 2, 1.0, 0) for _ in range(10)]
+    gain = [1.0, loud, 1.0, loud, 1.0]                   # virtual outputs 1 and 3: physical 1
+    filters = [dict(in_ch=[i], out_ch=[o], coeff=2 * i + j, out_scale=[gain[o]])
+               for i in range(5) for j, o in enumerate((i, (i + 1) % 5))]
+    spec = dict(L=L, N=N, rs=rs, n_in=5, n_out=5, coeffs=coeffs, filters=filters)
+    ch = dict(in_map=[0, 1, 0, 1, 2], out_map=[0, 1, 0, 1, 2], in_fmt="S24_LE", out_fmt=outfmt,
+              delay={(0, 0): 0, (0, 2): L - 1, (0, 1): 1, (0, 3): 2 * L + 3,
+                     (1, 0): L, (1, 2): 1, (1, 1): 0, (1, 3): 2 * L + 3}, maxdelay=3 * L,
+              mute_from={(0, 2): N + 1, (1, 3): N + 1}, sdf_length=half,
+              subdelay={(0, 0): 37, (0, 4): -99, (1, 1): 99, (1, 4): 0} if subdelay is None else subdelay,
+              dither=dither, rate=rate)
+    changes = {N + 2: [("subdelay", 1, 1, -37), ("subdelay", 0, 4, 12)]} if half and subdelay is None else None
+    if not half:
+        ch["subdelay"] = {}
+    return spec, ch, mute_actions(ch, changes)
+
+
+def packed_input(seed, frames, fmts, amplitude=0.2):
+    """seeded noise as packed 24-bit frames (nupc_ref.pack) -> the raw stream, uint8"""
+    import nupc_ref as nr
+    rng = np.random.default_rng(seed)
+    q = np.clip(np.round(rng.standard_normal((frames, len(fmts))) * amplitude * (1 << 23)), -(1 << 23), (1 << 23) - 1)
+    return nr.pack(q.astype(np.int64), fmts)

@@ -37,6 +37,12 @@ def test_bad_arguments_are_errors_and_leave_the_engine_usable(hip):
     bad(lib.bfhip_engine_set_delay(h, 0, 0, -5))
     bad(lib.bfhip_engine_set_subdelay(h, 0, I, 0))
     bad(lib.bfhip_engine_enable_subdelay(h, 0, 9.0), "half filter length")
+    # a filter whose history alone (bs = 32768 doubles) is beyond the FIR kernel's LDS: refused when it
+    # is asked for, not as a launch error at the first block; one size down (tiled) is accepted
+    long_e = hip.Engine(32768, 2, 8, 1, 1)
+    bad(lib.bfhip_engine_enable_subdelay(long_e.h, 8192, 9.0), "too long for the sub-sample delay filter")
+    assert lib.bfhip_engine_enable_subdelay(long_e.h, 4095, 9.0) == 0
+    long_e.close()
     bad(lib.bfhip_engine_enable_dither(h, None, 1, 48000, 0))
     bad(lib.bfhip_engine_set_powersave(h, -1.0))
     bad(lib.bfhip_engine_block_dev(h, null, null), "not finalized")

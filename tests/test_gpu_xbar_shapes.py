@@ -39,12 +39,15 @@ def flat_ir(rng, n):
     return rng.standard_normal(n) / np.sqrt(n)
 
 
-def build(monkeypatch, spec, env=None, powersave=0.0):
+def build(monkeypatch, spec, env=None, powersave=0.0, ch=None):
+    """ch: the channel stage around the network (cases.build_channels, xbar_ref.Channels)"""
     monkeypatch.setenv("BFHIP_LONG_WINDOW", "0")
     for k in ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in (env or {}).items():
         monkeypatch.setenv(k, v)
+    if ch is not None:
+        return cases.build_channels(bf.Engine, spec, ch)
     e = bf.Engine(spec["L"], spec["N"], spec["rs"], spec["n_in"], spec["n_out"])
     e.set_interleaved(0, spec["infmt"])
     e.set_interleaved(1, spec["outfmt"])
@@ -60,10 +63,10 @@ def build(monkeypatch, spec, env=None, powersave=0.0):
     return e
 
 
-def run(monkeypatch, spec, blocks, actions=None, env=None, powersave=0.0, wave=None, diag=False):
+def run(monkeypatch, spec, blocks, actions=None, env=None, powersave=0.0, wave=None, diag=False, ch=None):
     """-> (outputs [frames][O] in the output format's units, status per block, engine); the path is
-    asserted on every block"""
-    e = build(monkeypatch, spec, env, powersave)
+    asserted on every block.  With a channel stage (ch) the outputs are the raw stream, uint8"""
+    e = build(monkeypatch, spec, env, powersave, ch)
     wave = spec["L"] in (4096, 8192) if wave is None else wave
     outs, sts, modes = [], [], set()
     for k, b in enumerate(blocks):
@@ -76,6 +79,8 @@ def run(monkeypatch, spec, blocks, actions=None, env=None, powersave=0.0, wave=N
         modes.add(e.block_mode)
     assert len(modes) == 1, modes
     e.sync()
+    if ch is not None:
+        return np.concatenate(outs), sts, e
     return xr.decode(np.concatenate(outs), spec["outfmt"], spec["n_out"]), sts, e
 
 

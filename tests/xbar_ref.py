@@ -1,6 +1,8 @@
 """Float64 reference model of the crossbar engine's block semantics (include/bfhip.h), for the
 tests.  It knows nothing about partitions, rings or plans, and uses neither the oracle nor the
-engine: numpy and scipy only.
+engine: numpy and scipy only.  (The Channels layer at the end is the exception: it borrows the
+FFT-free codecs of nupc_ref -- the oracle's raw2real / real2raw -- and is handed its sub-sample
+filters by the caller.)
 
     decode   raw interleaved blocks -> float64, exactly (integers times 2^-(bits-1), floats as
              they are);
@@ -18,6 +20,10 @@ engine: numpy and scipy only.
              (cases.fade_cascade_network, fftw_convolver.c:330-368);
     encode   integer formats requantised in float64 the way the reference's no-dither real2raw
              does (+0.5, truncate, clip), with its overflow records and status bits.
+
+    channels the stage between the raw buffers and the network (Channels): formats, N:1 maps with
+             integer delay and mute, the sub-sample delay FIR, the mix of a shared output, one
+             quantisation (HP-TPDF dither included) per physical output.
 
 One fftconvolve per distinct filter state, not per block, so that the model stays
 cheap at L = 8192."""
@@ -335,3 +341,126 @@ class Network:
             for a in actions[t]:
                 self.act(t, a)
         return output(x, self.filters, self.L, self.N, self.spec["n_out"], n_blocks)
+
+
+# ------------------------------------------------------------------ the channel stage
+
+def shifted(x, d):
+    """the stream x delayed by d frames (zeros in front)"""
+    out = np.zeros(len(x))
+    if d < len(x):
+        out[d:] = x[:len(x) - d]
+    return out
+
+
+def subdelay_fir(x, taps_per_block, L):
+    """y[n] = sum_k h_t[k] x[n - k] over the continuous unfiltered stream x (x[n < 0] = 0), h_t the
+    taps in force in block t = n // L (delay.c:416-442: the history is never the filtered signal)"""
+    x = np.asarray(x, np.float64)
+    y = np.zeros(len(x))
+    for t, h in enumerate(taps_per_block):
+        seg = np.concatenate([np.zeros(len(h) - 1), x])[t * L:(t + 1) * L + len(h) - 1]
+        y[t * L:(t + 1) * L] = (fftconvolve(seg, h, mode="valid") if len(h) > 512 else
+                                np.convolve(seg, h, mode="valid"))
+    return y
+
+
+class Channels:
+    """The channel stage around a Network, in float64.  `ch` describes it:
+
+        in_map / out_map   virt2phys per side (default: 1:1)
+        in_fmt / out_fmt   sample format name of the side's physical channels (interleaved)
+        delay, mute_from   {(io, v): frames} / {(io, v): block}: members of a shared channel only (a
+                           1:1 channel's delay and mute are the sound-card layer's, dai.c)
+        sdf_length         half length of the sub-sample filters, 0: none
+        subdelay           {(io, v): value}: the channels that have a filter, and its first value
+        dither             ascending physical outputs with HP-TPDF dither; rate, max_size
+
+    taps_of(value) -> the 2 * sdf_length + 1 float64 taps of a sub-sample value.  Run-time changes:
+    the Network's action tuples plus ("subdelay", io, v, value), issued before block t.
+
+    Input side: virtual v is physical in_map[v]; a member of a shared input is delayed by delay[v],
+    and by sdf_length more when the side filters any channel and v has no filter (bfrun.c:1152-1162,
+    1512-1516), then zero from block mute_from[v] on; a filtered input then goes through its FIR.
+    Output side (bfrun.c:1926-2003): the FIR; for members of a shared output the integer delay (+
+    sdf_length as above) and the mute; the sum of the un-muted members in ascending order; one
+    quantisation per physical output (nupc_ref.encode: the oracle's real2raw); every member of a
+    shared output carries the group's overflow record."""
+
+    def __init__(self, spec, ch, taps_of=None):
+        self.spec, self.ch, self.taps_of = spec, ch, taps_of
+        self.L, self.half = spec["L"], ch.get("sdf_length", 0)
+        self.maps = [list(ch.get("in_map", range(spec["n_in"]))), list(ch.get("out_map", range(spec["n_out"])))]
+        assert len(self.maps[0]) == spec["n_in"] and len(self.maps[1]) == spec["n_out"]
+        self.sd = {k: [(0, v)] for k, v in ch.get("subdelay", {}).items()}     # (io, v): [(block, value)]
+        self.net = Network(spec)
+
+    def formats(self, io):
+        import nupc_ref as nr
+        n_phys = max(self.maps[io]) + 1
+        return nr.layout([self.ch["in_fmt" if io == 0 else "out_fmt"]] * n_phys)
+
+    def shared(self, io, v):
+        return self.maps[io].count(self.maps[io][v]) > 1
+
+    def _taps(self, io, v, n_blocks):
+        seg = self.sd[(io, v)]
+        starts = [s[0] for s in seg]
+        return [self.taps_of(seg[int(np.searchsorted(starts, t, side="right")) - 1][1]) for t in range(n_blocks)]
+
+    def _member(self, io, v, x):
+        """delay and mute of virtual channel v (a member of a shared physical channel)"""
+        filters = any(k[0] == io for k in self.sd)
+        extra = self.half if filters and (io, v) not in self.sd else 0
+        x = shifted(x, self.ch.get("delay", {}).get((io, v), 0) + extra)
+        m = self.ch.get("mute_from", {}).get((io, v))
+        if m is not None:
+            x[m * self.L:] = 0.0
+        return x
+
+    def inputs(self, raw, n_blocks):
+        """raw input stream -> [frames][n_in] float64 virtual inputs"""
+        import nupc_ref as nr
+        n = n_blocks * self.L
+        x = nr.decode(np.ascontiguousarray(raw).view(np.uint8).ravel(), self.formats(0), n)
+        out = np.zeros((n, len(self.maps[0])))
+        for v, p in enumerate(self.maps[0]):
+            s = self._member(0, v, x[:, p]) if self.shared(0, v) else x[:, p].copy()
+            if (0, v) in self.sd:
+                s = subdelay_fir(s, self._taps(0, v, n_blocks), self.L)
+            out[:, v] = s
+        return out
+
+    def mix(self, y, n_blocks):
+        """[frames][n_out] virtual outputs of the network -> [frames][n_phys] reals to quantise"""
+        out = np.zeros((len(y), max(self.maps[1]) + 1))
+        for v, p in enumerate(self.maps[1]):
+            s = y[:, v]
+            if (1, v) in self.sd:
+                s = subdelay_fir(s, self._taps(1, v, n_blocks), self.L)
+            if self.shared(1, v):
+                s = self._member(1, v, s)
+            out[:, p] += s
+        return out
+
+    def reals(self, raw, n_blocks, actions=None):
+        """-> [frames][n_phys out] float64, unit scale: what the quantiser is handed"""
+        net_actions = {}
+        for t in sorted(actions or {}):
+            for a in actions[t]:
+                if a[0] == "subdelay":
+                    assert (a[1], a[2]) in self.sd, "only a channel that starts with a filter has one"
+                    self.sd[(a[1], a[2])].append((t, a[3]))
+                else:
+                    net_actions.setdefault(t, []).append(a)
+        return self.mix(self.net.output(self.inputs(raw, n_blocks), n_blocks, net_actions), n_blocks)
+
+    def run(self, raw, n_blocks, actions=None, safety_limit=0.0):
+        """-> (y [frames][n_phys] reals, raw output stream, overflow records per VIRTUAL output,
+        status per block)"""
+        import nupc_ref as nr
+        y = self.reals(raw, n_blocks, actions)
+        out, ofs, status = nr.encode(y, self.formats(1), self.L, dither=tuple(self.ch.get("dither", ())),
+                                     rate=self.ch.get("rate", 44100), max_size=self.ch.get("max_size", 0),
+                                     safety_limit=safety_limit)
+        return y, out, [ofs[p] for p in self.maps[1]], status
