@@ -183,6 +183,14 @@ def lib():
     L.bfhip_nupc_switch_busy.argtypes = [vp]
     L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
     L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_reserve_update.argtypes = [vp]
+    L.bfhip_nupc_update_buffer.restype = vp
+    L.bfhip_nupc_update_buffer.argtypes = [vp]
+    L.bfhip_nupc_update_coeff_async.argtypes = [vp, ci, ci, vp, C.c_long]
+    L.bfhip_nupc_update_coeff_dev_async.argtypes = [vp, ci, ci, vp, C.c_long, vp]
+    L.bfhip_nupc_update_busy.argtypes = [vp]
+    L.bfhip_nupc_update_result.argtypes = [vp]
+    L.bfhip_nupc_update_wait.argtypes = [vp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -646,6 +654,43 @@ class Nupc:
     def update_coeff(self, filt, coeff, taps):
         taps = np.ascontiguousarray(taps, self.dt)
         self._chk(lib().bfhip_nupc_update_coeff(self.h, filt, coeff, _ptr(taps), len(taps)))
+
+    # set rewrites without a host wait (include/bfhip_nupc.h)
+    def reserve_update(self):
+        """before finalize: finalize then allocates what update_coeff_async needs"""
+        self._chk(lib().bfhip_nupc_reserve_update(self.h))
+
+    def update_buffer(self):
+        """the pinned staging buffer as a numpy view of `taps` reals; None without a reservation"""
+        p = lib().bfhip_nupc_update_buffer(self.h)
+        if not p:
+            return None
+        ct = C.c_float if self.rs == 4 else C.c_double
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(self.taps,))
+
+    def update_coeff_async(self, filt, coeff, taps):
+        """enqueue the rewrite of an idle set and return; taps may be update_buffer() or a leading
+        slice of it (no copy)"""
+        if not (isinstance(taps, np.ndarray) and taps.dtype == self.dt and taps.flags.c_contiguous):
+            taps = np.ascontiguousarray(taps, self.dt)
+        self._chk(lib().bfhip_nupc_update_coeff_async(self.h, filt, coeff, _ptr(taps), len(taps)))
+
+    def update_coeff_dev_async(self, filt, coeff, taps_dev, n_taps, ready=None):
+        """the same from device memory (a torch tensor or an address); ready: a hipEvent_t handle
+        (torch.cuda.Event().cuda_event) the loader waits on, or None"""
+        self._chk(lib().bfhip_nupc_update_coeff_dev_async(self.h, filt, coeff, _ptr(taps_dev), n_taps,
+                                                          C.c_void_p(ready) if ready else None))
+
+    def update_busy(self):
+        return bool(self._chk(lib().bfhip_nupc_update_busy(self.h)))
+
+    def update_result(self):
+        """result of the last completed rewrite (raises on a non-finite tap, and while busy)"""
+        return self._chk(lib().bfhip_nupc_update_result(self.h))
+
+    def update_wait(self):
+        """blocks until the rewrite is done; not for the audio thread"""
+        return self._chk(lib().bfhip_nupc_update_wait(self.h))
 
     def set_output_gain(self, ch, gain):
         self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))

@@ -31,6 +31,7 @@
 
 #include "../../include/bfhip.h"
 #include "alloc.h"
+#include "coeff_async.h"
 #include "conv_shared.h"
 #include "dither_init.h"
 #include "kernels.h"
@@ -2977,6 +2978,57 @@ int bfhip_engine_update_coeff_block(bfhip_engine *e, int coeff, int block, const
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     return e->rs == 4 ? stream_refresh_block<float>(e, e->coeffs[coeff].d_H, block)
                       : stream_refresh_block<double>(e, e->coeffs[coeff].d_H, block);
+}
+
+// ---- rewrite of a whole resident set without a host wait (coeff_async.h; bfhip_nupc_update_coeff_async)
+
+// scratch the asynchronous rewrite needs, allocated now instead of lazily: the big-FFT buffers for a
+// whole set's partitions.  (The rewrite reads its taps straight from the caller's device buffer, so it
+// needs no d_taps.)  May wait and allocate: not for the audio path.
+int bfhip_internal_engine_reserve_update(bfhip_engine *e) {
+    if (!e || !e->finalized) return fail(BFHIP_ESTATE, "reserve_update: engine not finalized");
+    { const int ro = check_owner(e); if (ro != BFHIP_OK) return ro; }
+    HIPCHK(hipSetDevice(e->device));
+    if (e->big) { int rr = big_reserve(e, (size_t)e->N); if (rr != BFHIP_OK) return rr; }
+    return BFHIP_OK;
+}
+
+// Partitions [0, n_blocks) of resident set `coeff` from n_taps reals in device memory (zero-padded),
+// prepared by K7 on the engine's own stream, in order with its blocks: no host wait, no allocation,
+// no blocking copy.  The set must not be read by a block handed in after this call until a filter is
+// pointed at it again (the caller's state rules see to that); the stream-ordered copy and the long-window
+// layout forget that they hold it, as update_coeff_block makes them when no copy is in force, so the next
+// plan build lays it out from the new data.  Behind the preparation the engine's non-finite flag is
+// copied to *bad_host (pinned) and cleared; the caller records its own event behind this call.
+int bfhip_internal_engine_update_coeff_dev_async(bfhip_engine *e, int coeff, const void *taps_dev, int n_taps,
+                                                 int n_blocks, int *bad_host) {
+    if (!e || coeff < 0 || coeff >= (int)e->coeffs.size() || !taps_dev || n_taps < 0 || n_blocks < 1 ||
+        n_blocks > e->coeffs[coeff].n_blocks || !bad_host)
+        return fail(BFHIP_EINVAL, "update_coeff_dev_async: bad argument");
+    if (!e->finalized) return fail(BFHIP_ESTATE, "update_coeff_dev_async: engine not finalized");
+    { const int ro = check_owner(e); if (ro != BFHIP_OK) return ro; }
+    Coeff &c = e->coeffs[coeff];
+    if (c.d_H == nullptr) return fail(BFHIP_ESTATE, "update_coeff_dev_async: set %d is not on the device", coeff);
+    if (e->big && (size_t)n_blocks > e->big_cap)
+        return fail(BFHIP_ESTATE, "update_coeff_dev_async: no scratch reserved for %d partitions", n_blocks);
+    HIPCHK(hipSetDevice(e->device));
+    if ((long)n_taps > (long)n_blocks * e->L) n_taps = n_blocks * e->L;
+    HIPCHK(hipMemsetAsync(e->d_bad, 0, sizeof(int), e->stream));
+    hipError_t err = hipSuccess;
+    if (e->big) DISPATCH_BIG(launch_coeff_prep_big, e, taps_dev, n_taps, 1.0, c.d_H, n_blocks, &err);
+    else DISPATCH(launch_coeff_prep, e, taps_dev, n_taps, 1.0, c.d_H, n_blocks, &err);
+    if (err != hipSuccess) return fail(BFHIP_EHIP, "coeff_prep launch: %s", hipGetErrorString(err));
+    HIPCHK(hipMemcpyAsync(bad_host, e->d_bad, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemsetAsync(e->d_bad, 0, sizeof(int), e->stream));
+    // the layouts compare sets by pointer, which an in-place rewrite does not change
+    bool held = false;
+    for (auto &k : e->stream_keys)
+        for (int j = 0; j < OG; j++) if (k[j] == c.d_H) { k[j] = STREAM_KEY_STALE; held = true; }
+    for (auto &k : e->lkeys)
+        for (int j = 0; j < OG; j++) if (k[j] == c.d_H) { k[j] = STREAM_KEY_STALE; held = true; }
+    // a layout in force that holds the set: build the plan again before the next block reads it
+    if (held && (e->hstream.base != nullptr || e->lw_active)) e->plan_dirty = true;
+    return BFHIP_OK;
 }
 
 int bfhip_engine_add_filter(bfhip_engine *e,

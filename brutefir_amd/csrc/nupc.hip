@@ -34,6 +34,7 @@
 
 #include "../../include/bfhip_nupc.h"
 #include "alloc.h"
+#include "coeff_async.h"
 #include "dither_init.h"
 #include "kernels.h"
 #include "subdelay_filter.h"
@@ -457,6 +458,7 @@ struct Seg {
     void *d_z = nullptr;        // spectra between the split-phase MAC and output calls
     std::vector<int> eng_set;   // per filter: the set the engine's filter runs now
     std::vector<std::vector<int>> n_blocks;   // [filter][set]: partitions the set has in this engine
+    hipEvent_t ev_upd = nullptr;   // background segment with a reservation: its share of a rewrite is done
 };
 
 }  // namespace
@@ -527,6 +529,20 @@ struct bfhip_nupc {
     void *d_sd_hist[2] = {nullptr, nullptr};   // [channels][sd_bs] reals: unfiltered history
     DevFormat *d_fmt_in = nullptr;         // input formats for the conversion kernel
     uint8_t *d_in_real = nullptr;          // [in_frames][n_in] reals: the ring the engines read instead of d_in
+    // asynchronous set rewrite (bfhip_nupc_reserve_update / _update_coeff_async): everything is
+    // allocated at finalize; one rewrite in flight at a time
+    bool upd_reserve = false;              // asked for before finalize
+    uint8_t *h_upd = nullptr;              // pinned staging: taps() reals (bfhip_nupc_update_buffer)
+    uint8_t *d_upd = nullptr;              // device staging: the segment engines prepare out of their slices
+    hipStream_t upd_stream = nullptr;      // loader: low priority, uploads the background segments' slices
+    hipEvent_t ev_upd_load = nullptr;      // the loader's upload is done
+    hipEvent_t ev_upd_main = nullptr;      // the main-stream segments' share is done
+    int *h_upd_bad = nullptr;              // pinned, one word per segment: the engine's non-finite flag
+    bool upd_inflight = false;
+    bool upd_failed = false;               // enqueuing it failed part-way: the set's contents are unknown
+    int upd_filter = -1, upd_set = -1;     // the set being rewritten / rewritten last
+    int upd_result = BFHIP_OK;             // result of the last completed rewrite
+    std::vector<std::vector<char>> upd_bad;   // [filter][set]: the last rewrite ended non-finite
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
@@ -586,8 +602,10 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     (void)hipSetDevice(n->device);
     if (n->stream) (void)hipStreamSynchronize(n->stream);
     for (auto &s : n->seg) if (s.stream) (void)hipStreamSynchronize(s.stream);
+    if (n->upd_stream) (void)hipStreamSynchronize(n->upd_stream);
     for (auto &s : n->seg) {
         if (s.eng) bfhip_engine_destroy(s.eng);
+        if (s.ev_upd) (void)hipEventDestroy(s.ev_upd);
         if (s.d_out) (void)hipFree(s.d_out);
         if (s.d_out2) (void)hipFree(s.d_out2);
         if (s.d_z) (void)hipFree(s.d_z);
@@ -605,6 +623,12 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     if (n->h_out) (void)hipHostFree(n->h_out);
     if (n->h_over) (void)hipHostFree(n->h_over);
     if (n->h_inv) (void)hipHostFree(n->h_inv);
+    if (n->h_upd) (void)hipHostFree(n->h_upd);
+    if (n->h_upd_bad) (void)hipHostFree(n->h_upd_bad);
+    if (n->d_upd) (void)hipFree(n->d_upd);
+    if (n->ev_upd_load) (void)hipEventDestroy(n->ev_upd_load);
+    if (n->ev_upd_main) (void)hipEventDestroy(n->ev_upd_main);
+    if (n->upd_stream) (void)hipStreamDestroy(n->upd_stream);
     if (n->ev_gain) (void)hipEventDestroy(n->ev_gain);
     if (n->ev_in) (void)hipEventDestroy(n->ev_in);
     if (n->stream) (void)hipStreamDestroy(n->stream);
@@ -888,6 +912,25 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
             NCHK(bfhip_internal_dev_alloc((void **)&s.d_z, (size_t)((n->n_out + 7) / 8 * 8) * s.L * 2 * n->rs));
         }
     }
+    if (n->upd_reserve) {
+        // everything the asynchronous rewrite touches, so that it allocates nothing on the audio path
+        const size_t bytes = (size_t)bfhip_nupc_taps(n) * n->rs;
+        NCHK(bfhip_internal_pin_alloc((void **)&n->h_upd, bytes, hipHostMallocDefault));
+        memset(n->h_upd, 0, bytes);
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_upd, bytes));
+        NCHK(hipMemset(n->d_upd, 0, bytes));
+        NCHK(bfhip_internal_pin_alloc((void **)&n->h_upd_bad, n->seg.size() * sizeof(int), hipHostMallocDefault));
+        memset(n->h_upd_bad, 0, n->seg.size() * sizeof(int));
+        NCHK(hipStreamCreateWithPriority(&n->upd_stream, hipStreamNonBlocking, prio_least));
+        NCHK(hipEventCreateWithFlags(&n->ev_upd_load, hipEventDisableTiming));
+        NCHK(hipEventCreateWithFlags(&n->ev_upd_main, hipEventDisableTiming));
+        for (auto &s : n->seg) {
+            if (s.delay_steps > 0) NCHK(hipEventCreateWithFlags(&s.ev_upd, hipEventDisableTiming));
+            ECHK(bfhip_internal_engine_reserve_update(s.eng));
+        }
+        n->upd_bad.resize(n->coeff.size());
+        for (size_t f = 0; f < n->coeff.size(); f++) n->upd_bad[f].assign(n->coeff[f].size(), 0);
+    }
     n->finalized = true;
     return BFHIP_OK;
 }
@@ -1056,6 +1099,112 @@ bool nupc_switch_left(const bfhip_nupc *n, unsigned long long end) {
     return false;
 }
 
+// ---- asynchronous set rewrite
+
+// has every piece of the rewrite in flight completed?  hipEventQuery only: never blocks.  On
+// completion the segment engines' non-finite flags (pinned, written behind each preparation)
+// become the rewrite's result.
+int upd_poll(bfhip_nupc *n) {
+    if (!n->upd_inflight) return BFHIP_OK;
+    NCHK(hipSetDevice(n->device));
+    for (size_t k = 0; k < n->seg.size() + 2; k++) {
+        const hipEvent_t ev = k == 0 ? n->ev_upd_load : k == 1 ? n->ev_upd_main : n->seg[k - 2].ev_upd;
+        if (!ev) continue;                                        // a main-stream segment: ev_upd_main covers it
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); return BFHIP_OK; }
+        if (e != hipSuccess) return nfail(BFHIP_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
+    }
+    int bad = 0;
+    for (size_t k = 0; k < n->seg.size(); k++) bad |= ((volatile int *)n->h_upd_bad)[k];
+    n->upd_result = bad ? BFHIP_EINVAL : n->upd_failed ? BFHIP_EHIP : BFHIP_OK;
+    n->upd_bad[n->upd_filter][n->upd_set] = bad || n->upd_failed ? 1 : 0;
+    n->upd_inflight = false;
+    return BFHIP_OK;
+}
+
+// enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
+// no allocation.  Host source: `taps` is the pinned staging buffer or is copied into it.  Device
+// source: the loader (and the main stream, for its own slices) waits on ready_event.
+int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event);
+int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size() ||
+        !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: bad argument");
+    if (!n->finalized || !n->upd_reserve)
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: needs bfhip_nupc_reserve_update before finalize, and finalize");
+    if (coeff == n->live[filter] || coeff == n->queued[filter] || (n->sw && coeff == n->sw_old[filter]))
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: the set is live or part of a queued / in-flight switch");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: a rewrite is in flight (bfhip_nupc_update_busy)");
+    // set 0 keeps the partitions add_filter gave it: taps past them must be zero (a device source
+    // cannot be looked at without a wait: it must not reach past them at all)
+    for (const Seg &s : n->seg) {
+        const long covered = s.off + (long)s.n_blocks[filter][coeff] * s.L;
+        const long from = std::min(covered, n_taps), to = std::min(s.off + (long)s.L * s.N, n_taps);
+        bool past = on_device && from < to;
+        if (!on_device)
+            for (long i = from; i < to && !past; i++)
+                past = n->rs == 4 ? ((const float *)taps)[i] != 0.0f : ((const double *)taps)[i] != 0.0;
+        if (past) return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: set 0 of this filter is shorter than these taps (add_filter's length)");
+    }
+    if (!on_device && taps != (const void *)n->h_upd) memcpy(n->h_upd, taps, (size_t)n_taps * n->rs);
+    NCHK(hipSetDevice(n->device));
+    // from here on work may be enqueued: a failure leaves the set's contents unknown
+    n->upd_inflight = true;
+    n->upd_filter = filter; n->upd_set = coeff;
+    n->upd_bad[filter][coeff] = 1;
+    n->upd_failed = false;
+    const int r = upd_enqueue(n, filter, coeff, taps, on_device, n_taps, ready_event);
+    if (r < 0) n->upd_failed = true;
+    return r;
+}
+
+int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event) {
+    const size_t rs = (size_t)n->rs;
+    const uint8_t *src = on_device ? (const uint8_t *)taps : n->h_upd;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    bool main_waits = false;
+    if (on_device && ready_event) NCHK(hipStreamWaitEvent(n->upd_stream, (hipEvent_t)ready_event, 0));
+    // upload: a segment that runs on the main stream gets its own slice there (the high-priority
+    // stream never waits for the whole upload); the rest goes through the loader, adjacent slices
+    // in one copy
+    long run_from = -1, run_to = -1;
+    auto flush = [&]() -> hipError_t {
+        if (run_from < 0 || run_to <= run_from) { run_from = run_to = -1; return hipSuccess; }
+        const hipError_t e = hipMemcpyAsync(n->d_upd + (size_t)run_from * rs, src + (size_t)run_from * rs,
+                                            (size_t)(run_to - run_from) * rs, kind, n->upd_stream);
+        run_from = run_to = -1;
+        return e;
+    };
+    for (const Seg &s : n->seg) {
+        const long from = s.off, to = std::min(s.off + (long)s.L * s.N, n_taps);
+        if (to <= from) continue;
+        if (s.delay_steps > 0) {
+            if (run_to != from) { NCHK(flush()); run_from = from; }
+            run_to = to;
+            continue;
+        }
+        if (on_device && ready_event && !main_waits) { NCHK(hipStreamWaitEvent(n->stream, (hipEvent_t)ready_event, 0)); main_waits = true; }
+        NCHK(hipMemcpyAsync(n->d_upd + (size_t)from * rs, src + (size_t)from * rs, (size_t)(to - from) * rs, kind, n->stream));
+    }
+    NCHK(flush());
+    NCHK(hipEventRecord(n->ev_upd_load, n->upd_stream));
+    // preparation: one launch per segment engine on the engine's own stream, in order with its blocks
+    for (size_t k = 0; k < n->seg.size(); k++) {
+        Seg &s = n->seg[k];
+        const long cap = (long)s.L * s.N;
+        const long left = std::max(0L, std::min(n_taps - s.off, cap));
+        if (s.delay_steps > 0) NCHK(hipStreamWaitEvent(s.stream, n->ev_upd_load, 0));
+        ECHK(bfhip_internal_engine_update_coeff_dev_async(s.eng, n->coeff[filter][coeff], n->d_upd + (size_t)s.off * rs,
+                                                          (int)left, s.n_blocks[filter][coeff], n->h_upd_bad + k));
+        if (s.delay_steps > 0) NCHK(hipEventRecord(s.ev_upd, s.stream));
+    }
+    NCHK(hipEventRecord(n->ev_upd_main, n->stream));
+    return BFHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1215,6 +1364,13 @@ int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff) {
         return nfail(BFHIP_EINVAL, "nupc_set_coeff: bad filter or set");
     if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_coeff before finalize");
     if (n->sw) return nfail(BFHIP_ESTATE, "nupc_set_coeff: the previous switch is still in flight (bfhip_nupc_switch_busy)");
+    if (n->upd_reserve) {
+        { const int r = upd_poll(n); if (r < 0) return r; }
+        if (n->upd_inflight && filter == n->upd_filter && coeff == n->upd_set)
+            return nfail(BFHIP_ESTATE, "nupc_set_coeff: a rewrite of this set is in flight (bfhip_nupc_update_busy)");
+        if (n->upd_bad[filter][coeff])
+            return nfail(BFHIP_ESTATE, "nupc_set_coeff: the last rewrite of this set found a NaN or Inf value among its coefficients");
+    }
     n->queued[filter] = coeff;
     return BFHIP_OK;
 }
@@ -1238,6 +1394,10 @@ int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *ta
     if (coeff == n->live[filter] || coeff == n->queued[filter] || (n->sw && coeff == n->sw_old[filter]))
         return nfail(BFHIP_ESTATE, "nupc_update_coeff: the set is live or part of a queued / in-flight switch");
     OWNER(n);
+    if (n->upd_reserve && n->finalized) {
+        { const int r = upd_poll(n); if (r < 0) return r; }
+        if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_update_coeff: an asynchronous rewrite is in flight (bfhip_nupc_update_busy)");
+    }
     // set 0 keeps the partitions add_filter gave it: taps past them must be zero
     const unsigned char *t = (const unsigned char *)taps;
     auto nonzero = [&](long from, long to) {
@@ -1261,7 +1421,61 @@ int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *ta
             ECHK(bfhip_engine_update_coeff_block(s.eng, n->coeff[filter][coeff], p, part.data()));
         }
     }
+    if (n->upd_reserve && n->finalized) n->upd_bad[filter][coeff] = 0;
     return BFHIP_OK;
+}
+
+// ---- run-time control: asynchronous set rewrite ---------------------------------------------
+
+int bfhip_nupc_reserve_update(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_update after finalize");
+    n->upd_reserve = true;
+    return BFHIP_OK;
+}
+
+void *bfhip_nupc_update_buffer(bfhip_nupc *n) { return n && n->finalized ? n->h_upd : nullptr; }
+
+int bfhip_nupc_update_coeff_async(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps) {
+    return upd_start(n, filter, coeff, taps, false, n_taps, nullptr);
+}
+
+int bfhip_nupc_update_coeff_dev_async(bfhip_nupc *n, int filter, int coeff, const void *taps_dev, long n_taps,
+                                      void *ready_event) {
+    return upd_start(n, filter, coeff, taps_dev, true, n_taps, ready_event);
+}
+
+int bfhip_nupc_update_busy(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd_reserve) return 0;
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    return n->upd_inflight ? 1 : 0;
+}
+
+int bfhip_nupc_update_result(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd_reserve) return nfail(BFHIP_ESTATE, "nupc_update_result: no reservation (bfhip_nupc_reserve_update)");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_update_result: the rewrite is still in flight (bfhip_nupc_update_busy)");
+    if (n->upd_result == BFHIP_EHIP) return nfail(BFHIP_EHIP, "nupc_update_result: the rewrite could not be enqueued completely");
+    if (n->upd_result != BFHIP_OK) return nfail(n->upd_result, "NaN or Inf value among coefficients.");
+    return BFHIP_OK;
+}
+
+// blocks: not for the audio thread
+int bfhip_nupc_update_wait(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd_reserve) return nfail(BFHIP_ESTATE, "nupc_update_wait: no reservation (bfhip_nupc_reserve_update)");
+    OWNER(n);
+    if (n->upd_inflight) {
+        NCHK(hipSetDevice(n->device));
+        NCHK(hipEventSynchronize(n->ev_upd_load));
+        NCHK(hipEventSynchronize(n->ev_upd_main));
+        for (auto &s : n->seg) if (s.ev_upd) NCHK(hipEventSynchronize(s.ev_upd));
+    }
+    return bfhip_nupc_update_result(n);
 }
 
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain) {

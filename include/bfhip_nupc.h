@@ -108,6 +108,58 @@ int bfhip_nupc_switch_busy(const bfhip_nupc *n);
    by add_coeff cover the whole schedule; set 0 keeps add_filter's length, and taps past it must
    be zero (BFHIP_EINVAL).  Synchronous: waits for the segment engines' pending blocks. */
 int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps);
+/* ---- run-time control: set rewrites that never stall the audio thread ----------------------
+ * bfhip_nupc_update_coeff above waits for every segment engine three times per partition and
+ * copies synchronously: fine offline, not in the thread that owes a block every period.  The
+ * calls below rewrite an idle set with no host wait and no allocation on the audio path:
+ *
+ *     reserve_update (before finalize)       everything is allocated at finalize
+ *     render taps into update_buffer()       pinned staging of bfhip_nupc_taps() reals
+ *     update_coeff_async(filter, set, ...)   enqueues the upload and the preparation, returns
+ *     ... block calls ... update_busy() == 0 polled with hipEventQuery
+ *     update_result() == BFHIP_OK            then set_coeff(filter, set) as usual
+ *
+ * Upload: host staging -> device staging on a low-priority loader stream of its own; a segment
+ * that runs on the main stream (zero slack, or all of them with BFHIP_NUPC_BACKGROUND=0) has its
+ * own slice copied on the main stream instead, so the main stream never waits for the whole
+ * upload.  Preparation: one coefficient-preparation launch per segment engine for the segment's
+ * whole slice, on the engine's own stream, in order with the engine's blocks (it shares their
+ * FFT scratch above 8192).  Per partition it is the arithmetic of bfhip_nupc_update_coeff: the
+ * prepared set, and the output after a switch onto it, have the same bits.
+ * Exactness: a rewrite of an idle set changes no output byte until a switch onto the set; the
+ * state rules are those of bfhip_nupc_update_coeff.  One rewrite is in flight at a time.
+ * A convolver that never calls reserve_update allocates nothing more, makes the same launches
+ * and changes no byte.
+ * Cost: DESIGN.md section 4 and profiles/nupc_rewrite_latency.jsonl.
+ */
+/* before finalize (BFHIP_ESTATE after) */
+int bfhip_nupc_reserve_update(bfhip_nupc *n);
+/* the pinned staging buffer (bfhip_nupc_taps() reals, realsize wide) after finalize; NULL without a
+   reservation.  The caller may write it while no rewrite is in flight. */
+void *bfhip_nupc_update_buffer(bfhip_nupc *n);
+/* arguments and state rules of bfhip_nupc_update_coeff; BFHIP_ESTATE without a reservation, and
+   while bfhip_nupc_update_busy is 1 (nothing changes; bfhip_nupc_update_coeff answers the same
+   then).  taps may be the staging buffer itself (no copy); else one host memcpy into it.  Makes
+   no stream, device or event wait, no blocking copy and no allocation, and no later block call
+   makes one on its behalf. */
+int bfhip_nupc_update_coeff_async(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps);
+/* the same from device memory.  ready_event: a hipEvent_t or NULL, as in bfhip_engine_block_dev_ev;
+   the loader stream waits on it, and so does the main stream before it copies its own slices, so
+   the host does not.  The buffer is the caller's again when bfhip_nupc_update_busy returns 0.
+   The taps-past-set-0 rule cannot look at device memory: n_taps itself must not reach past set 0's
+   partitions (BFHIP_EINVAL). */
+int bfhip_nupc_update_coeff_dev_async(bfhip_nupc *n, int filter, int coeff, const void *taps_dev, long n_taps,
+                                      void *ready_event);
+/* 1 until every piece of the rewrite has completed on the device, then 0; never blocks */
+int bfhip_nupc_update_busy(bfhip_nupc *n);
+/* result of the last completed rewrite, without blocking: BFHIP_OK, or BFHIP_EINVAL with the
+   reference's "NaN or Inf value among coefficients." if a tap was not finite; BFHIP_ESTATE while
+   busy.  bfhip_nupc_set_coeff onto a set answers BFHIP_ESTATE while a rewrite of it is in flight
+   and after a non-finite one, until a later rewrite of the set succeeds. */
+int bfhip_nupc_update_result(bfhip_nupc *n);
+/* blocks until the rewrite is done and returns its result: for tests and offline use, NOT for the
+   audio thread */
+int bfhip_nupc_update_wait(bfhip_nupc *n);
 /* per-output gain applied at the emit step, exact from the first frame of the next block call's
    output; 0.0 mutes; default 1.0 (folded into the 1/scale factor: exact) */
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);

@@ -9,12 +9,19 @@ bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, ne
 uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
+                                  [--rewrite | --rewrite-sync] [--dump-output FILE]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
 outputs a maxdelay of 48 000 frames and new delays (seeded, up to 48 000) every 300 periods;
 --subdelay gives both inputs and both outputs a sub-sample delay filter (sdf_length 31) and new
-values (seeded, in (-100, 100)) every 300 periods."""
+values (seeded, in (-100, 100)) every 300 periods.  --rewrite gives every filter a second set and,
+every 300 periods, rewrites the idle set of each of the four filters asynchronously out of the
+staging buffer (bfhip_nupc_update_coeff_async), one after the other as busy clears, then switches
+to them; --rewrite-sync does the same with the synchronous bfhip_nupc_update_coeff.  Both report
+the host duration of each rewrite call, the periods from call to busy == 0, and step_ms split into
+periods with a rewrite in flight and without.  --dump-output writes the raw output of all timed
+and untimed periods to FILE (to compare two builds byte for byte)."""
 import argparse
 import json
 import os
@@ -36,6 +43,9 @@ def main():
     ap.add_argument("--dither", action="store_true")
     ap.add_argument("--delay", action="store_true")
     ap.add_argument("--subdelay", action="store_true")
+    ap.add_argument("--rewrite", action="store_true")
+    ap.add_argument("--rewrite-sync", action="store_true")
+    ap.add_argument("--dump-output")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
     seg_len, k = [], L0
@@ -60,12 +70,26 @@ def main():
         for io in (bf.IN, bf.OUT):
             for c in range(2):
                 nu.set_subdelay(io, c, 37 - 62 * c)
+    assert not (a.rewrite and a.rewrite_sync)
+    rewriting = a.rewrite or a.rewrite_sync
+    if a.rewrite:
+        nu.reserve_update()
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
             h = rng.standard_normal(1048576) * np.exp(-np.arange(1048576) / 2e5) / 2000.0
             nu.add_filter(i, o, h)
+            if rewriting:
+                nu.add_coeff(2 * o + i, h[:nu.taps] * 0.5)
     nu.finalize()
+    # two impulse responses to render alternately into the idle set (a render costs what it costs
+    # the caller: here one numpy copy into the staging buffer, or nothing for the synchronous call)
+    renders = [rng.standard_normal(nu.taps) * np.exp(-np.arange(nu.taps) / 2e5) / 2000.0 for _ in range(2)] if rewriting else []
+    staging = nu.update_buffer() if a.rewrite else None
+    live_set, todo, round_no, due = 0, [], 0, False
+    call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
+    in_flight = []                     # per period: a rewrite was in flight (or made) during it
+    dump = []
     x = rng.standard_normal((8, L0, 2)) * 0.1
     import gc
     gc.disable()                       # the timed loop allocates one small array per period
@@ -82,11 +106,61 @@ def main():
                 for c in range(2):
                     nu.set_subdelay(io, c, int(drng.integers(-99, 100)))
             n_sd_changes += 1
+        flying = False
+        if rewriting:
+            due = due or s % 300 == 299
+            if due and not todo and started_at is None and not nu.switch_busy():
+                todo, due = [0, 1, 2, 3], False
+                round_no += 1
+            if started_at is not None and not nu.update_busy():
+                busy_periods.append(s - started_at)
+                started_at = None
+                assert nu.update_result() == 0
+                if not todo:                                   # all four are in: switch to them
+                    for f in range(4):
+                        nu.set_coeff(f, 1 - live_set)
+                    live_set = 1 - live_set
+            if todo and started_at is None:
+                f = todo.pop(0)
+                src = renders[round_no & 1]
+                if a.rewrite:
+                    # even rounds render into the staging buffer outside the timed call (zero-copy),
+                    # odd rounds hand in a separate array (one memcpy inside the call)
+                    zero_copy = round_no % 2 == 0
+                    if zero_copy:
+                        staging[:] = src
+                    t0 = time.perf_counter()
+                    nu.update_coeff_async(f, 1 - live_set, staging if zero_copy else src)
+                    (call_ms if zero_copy else call_copy_ms).append((time.perf_counter() - t0) * 1e3)
+                    started_at = s
+                else:
+                    t0 = time.perf_counter()
+                    nu.update_coeff(f, 1 - live_set, src)
+                    call_ms.append((time.perf_counter() - t0) * 1e3)
+                    if not todo:
+                        for g in range(4):
+                            nu.set_coeff(g, 1 - live_set)
+                        live_set = 1 - live_set
+                flying = True
+            flying = flying or started_at is not None
+        in_flight.append(flying)
         t0 = time.perf_counter()
-        st, _ = nu.block(x[s & 7])
+        st, raw = nu.block(x[s & 7])
         ts.append(time.perf_counter() - t0)
         assert st == 0
+        if a.dump_output:
+            dump.append(raw)
+    if a.dump_output:
+        np.concatenate(dump).tofile(a.dump_output)
     ts = np.array(ts[256:]) * 1e3
+    fl = np.array(in_flight[256:], bool)
+
+    def dist(v):
+        v = np.asarray(v, float)
+        if len(v) == 0:
+            return None
+        return {"n": int(len(v)), "median": round(float(np.median(v)), 4), "p99": round(float(np.percentile(v, 99)), 4),
+                "max": round(float(v.max()), 4)}
     # the periods in which every segment has a block to launch (the schedule's worst case), as
     # opposed to the rare host-side hiccups that land anywhere
     ratio = seg_len[-1] // L0
@@ -97,6 +171,11 @@ def main():
         "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
         "subdelay": {"sdf_length": 31, "inputs": [0, 1], "outputs": [0, 1], "changes_every_periods": 300,
                      "changes": n_sd_changes} if a.subdelay else None,
+        "rewrite": {"mode": "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+                    "taps_per_set": int(nu.taps), "rounds": round_no,
+                    "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
+                    "periods_to_idle": dist(busy_periods),
+                    "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
