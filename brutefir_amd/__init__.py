@@ -191,6 +191,9 @@ def lib():
     L.bfhip_nupc_update_busy.argtypes = [vp]
     L.bfhip_nupc_update_result.argtypes = [vp]
     L.bfhip_nupc_update_wait.argtypes = [vp]
+    L.bfhip_nupc_reserve_eq.argtypes = [vp, C.c_long]
+    L.bfhip_nupc_render_eq_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp]
+    L.bfhip_nupc_render_eq.argtypes = [vp, C.c_long, ci, dp, dp, dp, vp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -691,6 +694,26 @@ class Nupc:
     def update_wait(self):
         """blocks until the rewrite is done; not for the audio thread"""
         return self._chk(lib().bfhip_nupc_update_wait(self.h))
+
+    # equaliser curves rendered on the device (include/bfhip_nupc.h)
+    def reserve_eq(self, max_taps):
+        """before finalize, after reserve_update: finalize then allocates what the renders need"""
+        self._chk(lib().bfhip_nupc_reserve_eq(self.h, max_taps))
+
+    def render_eq_async(self, filt, coeff, taps, freq, mag, phase):
+        """render the curve (bands: normalised frequency 0 .. 0.5, linear magnitude, phase in radians)
+        into `taps` reals on the device and rewrite an idle set with them; returns at once"""
+        assert len(freq) == len(mag) == len(phase)
+        self._chk(lib().bfhip_nupc_render_eq_async(self.h, filt, coeff, taps, len(freq), _darr(list(freq)),
+                                                   _darr(list(mag)), _darr(list(phase))))
+
+    def render_eq(self, taps, freq, mag, phase):
+        """the render alone, synchronous: a numpy array of `taps` reals"""
+        assert len(freq) == len(mag) == len(phase)
+        out = np.zeros(max(int(taps), 0), self.dt)
+        self._chk(lib().bfhip_nupc_render_eq(self.h, taps, len(freq), _darr(list(freq)), _darr(list(mag)),
+                                             _darr(list(phase)), _ptr(out)))
+        return out
 
     def set_output_gain(self, ch, gain):
         self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))

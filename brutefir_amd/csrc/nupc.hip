@@ -36,6 +36,7 @@
 #include "alloc.h"
 #include "coeff_async.h"
 #include "dither_init.h"
+#include "eq_render.h"
 #include "kernels.h"
 #include "subdelay_filter.h"
 
@@ -543,6 +544,11 @@ struct bfhip_nupc {
     int upd_filter = -1, upd_set = -1;     // the set being rewritten / rewritten last
     int upd_result = BFHIP_OK;             // result of the last completed rewrite
     std::vector<std::vector<char>> upd_bad;   // [filter][set]: the last rewrite ended non-finite
+    // equaliser render (bfhip_nupc_reserve_eq / _render_eq_async, eq_render.h): a producer in front of
+    // the rewrite, on the loader stream; everything is allocated at finalize
+    long eq_reserve = 0;                   // max_taps asked for before finalize, 0 = none
+    EqRender eq;
+    hipEvent_t ev_eq = nullptr;            // the render into eq.taps is done
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
 
@@ -626,6 +632,8 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     if (n->h_upd) (void)hipHostFree(n->h_upd);
     if (n->h_upd_bad) (void)hipHostFree(n->h_upd_bad);
     if (n->d_upd) (void)hipFree(n->d_upd);
+    eq_render_free(n->eq);
+    if (n->ev_eq) (void)hipEventDestroy(n->ev_eq);
     if (n->ev_upd_load) (void)hipEventDestroy(n->ev_upd_load);
     if (n->ev_upd_main) (void)hipEventDestroy(n->ev_upd_main);
     if (n->upd_stream) (void)hipStreamDestroy(n->upd_stream);
@@ -931,6 +939,10 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
         n->upd_bad.resize(n->coeff.size());
         for (size_t f = 0; f < n->coeff.size(); f++) n->upd_bad[f].assign(n->coeff[f].size(), 0);
     }
+    if (n->eq_reserve) {
+        NCHK(eq_render_alloc(n->eq, n->rs, n->eq_reserve));
+        NCHK(hipEventCreateWithFlags(&n->ev_eq, hipEventDisableTiming));
+    }
     n->finalized = true;
     return BFHIP_OK;
 }
@@ -1125,8 +1137,11 @@ int upd_poll(bfhip_nupc *n) {
 // enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
 // no allocation.  Host source: `taps` is the pinned staging buffer or is copied into it.  Device
 // source: the loader (and the main stream, for its own slices) waits on ready_event.
+// eq: the taps are rendered from this curve into eq.taps on the loader stream first, and ev_eq is
+// the ready event (the caller passes taps = eq.taps, on_device).
 int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event);
-int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event) {
+int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event,
+              const EqBands *eq = nullptr) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size() ||
         !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
@@ -1151,6 +1166,13 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
     }
     if (!on_device && taps != (const void *)n->h_upd) memcpy(n->h_upd, taps, (size_t)n_taps * n->rs);
     NCHK(hipSetDevice(n->device));
+    if (eq) {
+        // a failure here has touched eq.taps only: the set is as it was
+        NCHK(n->rs == 4 ? eq_render_launch<float>(n->eq, *eq, n_taps, n->upd_stream)
+                        : eq_render_launch<double>(n->eq, *eq, n_taps, n->upd_stream));
+        NCHK(hipEventRecord(n->ev_eq, n->upd_stream));
+        ready_event = n->ev_eq;
+    }
     // from here on work may be enqueued: a failure leaves the set's contents unknown
     n->upd_inflight = true;
     n->upd_filter = filter; n->upd_set = coeff;
@@ -1461,6 +1483,62 @@ int bfhip_nupc_update_result(bfhip_nupc *n) {
     if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_update_result: the rewrite is still in flight (bfhip_nupc_update_busy)");
     if (n->upd_result == BFHIP_EHIP) return nfail(BFHIP_EHIP, "nupc_update_result: the rewrite could not be enqueued completely");
     if (n->upd_result != BFHIP_OK) return nfail(n->upd_result, "NaN or Inf value among coefficients.");
+    return BFHIP_OK;
+}
+
+// ---- run-time control: equaliser curves rendered on the device ------------------------------
+
+int bfhip_nupc_reserve_eq(bfhip_nupc *n, long max_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq after finalize");
+    if (!n->upd_reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq: needs bfhip_nupc_reserve_update first");
+    if (max_taps < 8 || (max_taps & (max_taps - 1)) || max_taps > std::min(bfhip_nupc_taps(n), 1L << (kEqMaxLog2H + 1)))
+        return nfail(BFHIP_EINVAL, "nupc_reserve_eq: max_taps must be a power of two, 8 .. min(taps, 1048576)");
+    n->eq_reserve = max_taps;
+    return BFHIP_OK;
+}
+
+// state and curve checks shared by the two render calls; fills the kernel-argument copy of the bands
+static int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                    const double phase[], EqBands *b) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->eq_reserve)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq: needs bfhip_nupc_reserve_eq before finalize, and finalize");
+    if (taps < 8 || (taps & (taps - 1)) || taps > n->eq_reserve)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: taps must be a power of two, 8 .. max_taps");
+    if (!freq || !mag || !phase || n_bands < 2 || n_bands > kEqMaxBands)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: 2 .. 130 bands");
+    if (freq[0] != 0.0 || freq[n_bands - 1] != 0.5)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: the first band must be at 0 and the last at 0.5");
+    for (int i = 0; i < n_bands; i++) {
+        if (i > 0 && !(freq[i] > freq[i - 1])) return nfail(BFHIP_EINVAL, "nupc_render_eq: band frequencies must ascend");
+        if (!std::isfinite(mag[i]) || mag[i] < 0.0 || !std::isfinite(phase[i]))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq: magnitudes must be finite and >= 0, phases finite");
+        b->freq[i] = freq[i]; b->mag[i] = mag[i]; b->phase[i] = phase[i];
+    }
+    b->n = n_bands;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
+                               const double mag[], const double phase[]) {
+    EqBands b;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, &b); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.taps, true, taps, nullptr, &b);
+}
+
+int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                         const double phase[], void *taps_out) {
+    EqBands b;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, &b); if (r < 0) return r; }
+    if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq: null buffer");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq: a rewrite is in flight (bfhip_nupc_update_busy)");
+    NCHK(hipSetDevice(n->device));
+    NCHK(n->rs == 4 ? eq_render_launch<float>(n->eq, b, taps, n->upd_stream) : eq_render_launch<double>(n->eq, b, taps, n->upd_stream));
+    NCHK(hipMemcpyAsync(taps_out, n->eq.taps, (size_t)taps * n->rs, hipMemcpyDeviceToHost, n->upd_stream));
+    NCHK(hipStreamSynchronize(n->upd_stream));
     return BFHIP_OK;
 }
 

@@ -160,6 +160,44 @@ int bfhip_nupc_update_result(bfhip_nupc *n);
 /* blocks until the rewrite is done and returns its result: for tests and offline use, NOT for the
    audio thread */
 int bfhip_nupc_update_wait(bfhip_nupc *n);
+/* ---- run-time control: equaliser curves rendered on the device (bflogic_eq's "render into the
+ * inactive set, then switch") -----------------------------------------------------------------
+ * The producer in front of bfhip_nupc_update_coeff_dev_async: the host hands over the curve (at
+ * most 130 bands of three doubles), the device evaluates it, transforms it and rewrites the set,
+ * so a run-time equaliser needs no host FFT and uploads no taps.
+ *
+ * What is rendered is the reference's render_equaliser (rendereq.h:20-62) for taps = R.  With
+ *     ci(a1, a2, f1, f2, f) = (a1 - a2) 0.5 cos(pi (f - f1) / (f2 - f1)) + (a1 + a2) 0.5
+ * bin n = 1 .. R/2 - 1 at f = n / R, i the first band with f <= freq[i + 1], is
+ *     X[n] = (-1)^n  ci(mag[i], mag[i+1], freq[i], freq[i+1], f) / R  (cos phi + i sin phi),
+ *     phi  = ci(phase[i], phase[i+1], freq[i], freq[i+1], f),
+ * X[0] = mag[0] / R and X[R/2] = mag[n_bands-1] / R are real, and
+ *     taps[t] = X[0] + (-1)^t X[R/2] + 2 sum_n (Re X[n] cos(2 pi n t / R) - Im X[n] sin(2 pi n t / R))
+ * (FFTW's unnormalised HC2R).  mag is linear and phase in radians, converted as bflogic_eq.c:173-175
+ * does.  The reference writes the linear-phase term as cos(-R pi f + phi), which is (-1)^n cos phi
+ * in exact arithmetic; the sign form is computed here, in float64 for both precisions and rounded
+ * to the convolver's real type once, so the float32 build of the reference is not reproduced at
+ * long lengths.  A render is a pure function of its arguments: the same
+ * arguments give the same bytes.
+ */
+/* before finalize, after bfhip_nupc_reserve_update (BFHIP_ESTATE otherwise / after finalize).
+   max_taps: a power of two, 8 <= max_taps <= min(bfhip_nupc_taps(), 1048576) (BFHIP_EINVAL).
+   Everything the render needs is allocated at finalize. */
+int bfhip_nupc_reserve_eq(bfhip_nupc *n, long max_taps);
+/* render the curve into `taps` reals on the device and rewrite set `coeff` of `filter` with them
+   (taps beyond `taps` are zero).  State rules, busy/result/wait calls and the exactness contract
+   are those of bfhip_nupc_update_coeff_dev_async.  No host wait, no allocation, no blocking copy;
+   the bands are copied at the call.
+   taps: a power of two, 8 <= taps <= max_taps, and within set 0's partitions when coeff == 0.
+   n_bands 2..130; freq[0] == 0, freq[n_bands-1] == 0.5, strictly ascending; mag finite and >= 0;
+   phase finite: BFHIP_EINVAL otherwise and nothing changes.  Without bfhip_nupc_reserve_eq:
+   BFHIP_ESTATE. */
+int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands,
+                               const double freq[], const double mag[], const double phase[]);
+/* the same render alone, synchronous, `taps` reals (realsize wide) into host memory: for tests and
+   offline use.  BFHIP_ESTATE while a rewrite is in flight (it shares the scratch). */
+int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[],
+                         const double mag[], const double phase[], void *taps_out);
 /* per-output gain applied at the emit step, exact from the first frame of the next block call's
    output; 0.0 mutes; default 1.0 (folded into the 1/scale factor: exact) */
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);

@@ -9,7 +9,7 @@ bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, ne
 uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
-                                  [--rewrite | --rewrite-sync] [--dump-output FILE]
+                                  [--rewrite | --rewrite-sync | --eq] [--dump-output FILE]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
@@ -20,7 +20,11 @@ every 300 periods, rewrites the idle set of each of the four filters asynchronou
 staging buffer (bfhip_nupc_update_coeff_async), one after the other as busy clears, then switches
 to them; --rewrite-sync does the same with the synchronous bfhip_nupc_update_coeff.  Both report
 the host duration of each rewrite call, the periods from call to busy == 0, and step_ms split into
-periods with a rewrite in flight and without.  --dump-output writes the raw output of all timed
+periods with a rewrite in flight and without.  --eq is --rewrite with the taps rendered on the device:
+every 300 periods a new random equaliser curve (130 bands, +-12 dB) is rendered at 1 048 576 taps into
+the idle set of each filter (bfhip_nupc_render_eq_async), then switched to; it also reports the wall time
+of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wait) of 8 and of 1 048 576
+taps, made before the timed loop: an upper bound of the render's device time.  --dump-output writes the raw output of all timed
 and untimed periods to FILE (to compare two builds byte for byte)."""
 import argparse
 import json
@@ -45,6 +49,7 @@ def main():
     ap.add_argument("--subdelay", action="store_true")
     ap.add_argument("--rewrite", action="store_true")
     ap.add_argument("--rewrite-sync", action="store_true")
+    ap.add_argument("--eq", action="store_true")
     ap.add_argument("--dump-output")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
@@ -70,10 +75,12 @@ def main():
         for io in (bf.IN, bf.OUT):
             for c in range(2):
                 nu.set_subdelay(io, c, 37 - 62 * c)
-    assert not (a.rewrite and a.rewrite_sync)
-    rewriting = a.rewrite or a.rewrite_sync
-    if a.rewrite:
+    assert a.rewrite + a.rewrite_sync + a.eq <= 1
+    rewriting = a.rewrite or a.rewrite_sync or a.eq
+    if a.rewrite or a.eq:
         nu.reserve_update()
+    if a.eq:
+        nu.reserve_eq(1048576)
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -86,6 +93,20 @@ def main():
     # the caller: here one numpy copy into the staging buffer, or nothing for the synchronous call)
     renders = [rng.standard_normal(nu.taps) * np.exp(-np.arange(nu.taps) / 2e5) / 2000.0 for _ in range(2)] if rewriting else []
     staging = nu.update_buffer() if a.rewrite else None
+
+    def curve():
+        freq = np.concatenate([[0.0], np.sort(rng.uniform(0.0005, 0.4995, 128)), [0.5]])
+        return list(freq), list(10.0 ** (rng.uniform(-12, 12, 130) / 20) / 2000.0), list(rng.uniform(-3, 3, 130))
+    render_ms = []
+    if a.eq:
+        # a synchronous render of 8 taps is the call, the wait and a copy of 64 bytes; one of 1 048 576
+        # taps adds the long render and 8 MB of copy to pageable memory
+        c = curve()
+        for n_taps in (8, 1048576):
+            for _ in range(5):
+                t0 = time.perf_counter()
+                nu.render_eq(n_taps, *c)
+                render_ms.append((n_taps, (time.perf_counter() - t0) * 1e3))
     live_set, todo, round_no, due = 0, [], 0, False
     call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
     in_flight = []                     # per period: a rewrite was in flight (or made) during it
@@ -123,7 +144,13 @@ def main():
             if todo and started_at is None:
                 f = todo.pop(0)
                 src = renders[round_no & 1]
-                if a.rewrite:
+                if a.eq:
+                    c = curve()
+                    t0 = time.perf_counter()
+                    nu.render_eq_async(f, 1 - live_set, 1048576, *c)
+                    call_ms.append((time.perf_counter() - t0) * 1e3)
+                    started_at = s
+                elif a.rewrite:
                     # even rounds render into the staging buffer outside the timed call (zero-copy),
                     # odd rounds hand in a separate array (one memcpy inside the call)
                     zero_copy = round_no % 2 == 0
@@ -171,10 +198,12 @@ def main():
         "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
         "subdelay": {"sdf_length": 31, "inputs": [0, 1], "outputs": [0, 1], "changes_every_periods": 300,
                      "changes": n_sd_changes} if a.subdelay else None,
-        "rewrite": {"mode": "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+        "rewrite": {"mode": "eq" if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
                     "taps_per_set": int(nu.taps), "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
                     "periods_to_idle": dist(busy_periods),
+                    "render_eq_sync_ms": {str(k): dist([v for n_taps, v in render_ms if n_taps == k][1:])
+                                          for k in (8, 1048576)} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
