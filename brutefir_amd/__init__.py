@@ -183,6 +183,12 @@ def lib():
     L.bfhip_nupc_switch_busy.argtypes = [vp]
     L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
     L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_reserve_filter_gain.argtypes = [vp]
+    L.bfhip_nupc_set_filter_gain.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_get_filter_gain.restype = cd
+    L.bfhip_nupc_get_filter_gain.argtypes = [vp, ci]
+    L.bfhip_nupc_set_gain_ramp.argtypes = [vp, ci]
+    L.bfhip_nupc_reset_overflow.argtypes = [vp]
     L.bfhip_nupc_reserve_update.argtypes = [vp]
     L.bfhip_nupc_update_buffer.restype = vp
     L.bfhip_nupc_update_buffer.argtypes = [vp]
@@ -717,6 +723,31 @@ class Nupc:
 
     def set_output_gain(self, ch, gain):
         self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))
+
+    # per-filter gains and ramped output gain (include/bfhip_nupc.h)
+    def reserve_filter_gain(self):
+        """before finalize: finalize then allocates what a gain-only switch needs"""
+        self._chk(lib().bfhip_nupc_reserve_filter_gain(self.h))
+
+    def set_filter_gain(self, filt, gain):
+        """before finalize the filter's initial gain; after it part of the next switch, together
+        with the set_coeff calls made before the same block call"""
+        self._chk(lib().bfhip_nupc_set_filter_gain(self.h, filt, gain))
+
+    def get_filter_gain(self, filt):
+        """the gain of the newest committed assignment"""
+        g = lib().bfhip_nupc_get_filter_gain(self.h, filt)
+        if g != g:
+            raise BfhipError("get_filter_gain: bad argument")
+        return g
+
+    def set_gain_ramp(self, frames):
+        """ramp length of the set_output_gain calls made from now on; 0 = step"""
+        self._chk(lib().bfhip_nupc_set_gain_ramp(self.h, frames))
+
+    def reset_overflow(self):
+        """every output's overflow struct back to its initial value, in front of the next block call"""
+        self._chk(lib().bfhip_nupc_reset_overflow(self.h))
 
     def enable_dither(self, channels, sample_rate, max_size=0):
         """HP-TPDF dither on the listed (integer-format) outputs; before finalize"""

@@ -97,6 +97,42 @@ __device__ __forceinline__ void emit_hand_off(int *__restrict__ status, unsigned
     }
 }
 
+// ---- per-output factor: 1/scale of the format times the output gain, which may be on a ramp
+//
+// One record per output channel in device memory (bfhip_nupc_set_output_gain / _set_gain_ramp).
+// The gain of the frame `idx` frames after the ramp's first one is
+//     idx < len - 1:  a + (g - a) (idx + 1) / len        else g (len 0: a step, always g)
+// in float64 for both precisions; the factor handed to the sample is (T)(inv * gain).  The emit
+// step evaluates it per frame and advances `done` itself, so a ramp in progress needs no upload;
+// the host uploads the records only when a target changes (its mirror advances the same way).
+struct NupcGain {
+    double inv;                    // 1 / the output format's scale
+    double a, g;                   // gain of the last frame before the ramp, target
+    int done, len;                 // frames of the ramp emitted so far (saturates at len), ramp length
+};
+// what a thread of the emit step keeps of its channel's record for one period: at(n) is the factor
+// of the period's frame n, a pure function of n
+template <typename T> struct GainFactor {
+    T sc;                          // off the ramp
+    double inv, a, d, len;
+    int done, on;                  // frames n < on of this period are on the ramp
+    __device__ __forceinline__ void load(const NupcGain &r, int L0) {
+        sc = (T)(r.inv * r.g);
+        inv = r.inv; a = r.a; d = r.g - r.a; len = (double)r.len; done = r.done;
+        const int left = r.len - 1 - r.done;
+        on = left < 0 ? 0 : left < L0 ? left : L0;
+    }
+    __device__ __forceinline__ T at(int n) const {
+        if (n >= on) return sc;
+        return (T)(inv * (a + d * ((double)(done + n + 1) / len)));
+    }
+};
+// thread 0, after every thread of the workgroup has loaded the record: the period has been emitted
+__device__ __forceinline__ void gain_advance(NupcGain *__restrict__ r, int L0) {
+    const int done = r->done, len = r->len;
+    if (done < len) r->done = len - done < L0 ? len : done + L0;
+}
+
 // ---- per-channel sub-sample delay (subdelay: / sdf_length; delay.c:416-442 at a period of L0)
 //
 // What the reference computes per period is the causal FIR  y[t] = sum_k h[k] x[t - k]  over the
@@ -169,15 +205,15 @@ nupc_subdelay_in_kernel(const uint8_t *__restrict__ raw, const DevFormat *__rest
                      [&](int n, T y) { real[(size_t)n * n_in + ch] = y; });
 }
 
-// output block b: L_0 frames out of the ring (emit_take), scaled into output units (output gain
-// folded into inv_scale), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114),
+// output block b: L_0 frames out of the ring (emit_take), scaled into output units (1/scale times
+// the output gain of the frame, GainFactor), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114),
 // ring region cleared.  One workgroup per output channel.  SD: the output side uses sub-delay; a
 // channel that has a filter runs the FIR over the scaled reals -- the values it would have been
 // quantised from -- and quantises the result (sd_fir_period); the others take the plain path.
 template <typename T, bool SD>
 __global__ __launch_bounds__(256) void
 nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
-                 long long rel0, int F, const DevFormat *__restrict__ fmt, const double *__restrict__ inv_scale,
+                 long long rel0, int F, const DevFormat *__restrict__ fmt, NupcGain *__restrict__ gain,
                  DevOverflow *__restrict__ over, uint8_t *__restrict__ raw, double safety_limit,
                  int *__restrict__ status, unsigned int *__restrict__ arrive, int *__restrict__ host_status,
                  const NupcSd<T> sd) {
@@ -187,20 +223,22 @@ nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long
     DevOverflow of = over[ch];
     uint8_t *base = raw + f.byte_offset;
     const size_t stride = (size_t)f.sample_spacing * f.bytes;
-    const T sc = (T)inv_scale[ch];
+    GainFactor<T> sc;
+    sc.load(gain[ch], L0);
     Quantiser<T> qz;
     qz.init(f, of, safety_limit);
     if (SD && sd.vals.v[ch] != -100)
         sd_fir_period<T>(sd_smem, sd, ch, L0,
-                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
                          [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
     else
         for (int n = tid; n < L0; n += 256)
-            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
+            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n), base + (size_t)n * stride);
     qz.reduce(tid, 256);
     if (tid == 0) {
         qz.commit(of);
         over[ch] = of;
+        gain_advance(gain + ch, L0);
         if (qz.st) atomicOr(status, qz.st);
         emit_hand_off(status, arrive, host_status);
     }
@@ -217,7 +255,7 @@ template <typename T, bool SD>
 __global__ __launch_bounds__(256) void
 nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out,
                         int L0, long long rel0, int F, const DevFormat *__restrict__ fmt,
-                        const double *__restrict__ inv_scale, DevOverflow *__restrict__ over, uint8_t *__restrict__ raw,
+                        NupcGain *__restrict__ gain, DevOverflow *__restrict__ over, uint8_t *__restrict__ raw,
                         double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
                         int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
                         DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
@@ -227,7 +265,8 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
     const int ch = blockIdx.x, tid = threadIdx.x;
     const int slot = dslot[ch];
     const DevFormat f = fmt[ch];
-    const T sc = (T)inv_scale[ch];
+    GainFactor<T> sc;
+    sc.load(gain[ch], L0);
     const bool fir = SD && sd.vals.v[ch] != -100;
     if (slot < 0) {
         DevOverflow of = over[ch];
@@ -237,15 +276,16 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
         qz.init(f, of, safety_limit);
         if (fir)
             sd_fir_period<T>(sd_smem, sd, ch, L0,
-                             [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                             [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
                              [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
         else
             for (int n = tid; n < L0; n += 256)
-                qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc, base + (size_t)n * stride);
+                qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n), base + (size_t)n * stride);
         qz.reduce(tid, 256);
         if (tid == 0) {
             qz.commit(of);
             over[ch] = of;
+            gain_advance(gain + ch, L0);
             if (qz.st) atomicOr(status, qz.st);
             emit_hand_off(status, arrive, host_status);
         }
@@ -254,15 +294,18 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
     T *x = stage + (size_t)slot * L0;
     if (fir)
         sd_fir_period<T>(sd_smem, sd, ch, L0,
-                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc; },
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
                          [&](int n, T y) { x[n] = y; });
     else
-        for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc;
+        for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n);
     for (int i = tid; i < 512; i += 256) rmap[i] = randmap[i - 256];
     __syncthreads();                  // the staged samples are visible to wave 0 (same workgroup)
     if (tid < 64) {
         dither_chain<T>(x, dstate + slot, table, table_size, rmap, f, over + ch, raw, L0, safety_limit, status, tid);
-        if (tid == 0) emit_hand_off(status, arrive, host_status);
+        if (tid == 0) {
+            gain_advance(gain + ch, L0);               // behind the barrier: every thread has its copy
+            emit_hand_off(status, arrive, host_status);
+        }
     }
 }
 
@@ -441,6 +484,22 @@ int nfail(int code, const std::string &msg) { n_err = msg; if (code == BFHIP_EHI
         if (_r < 0) return nfail(_r, std::string(#expr) + ": " + bfhip_last_error());       \
     } while (0)
 
+// what a filter runs under: an assignment is one of these per filter.  gain multiplies the filter's
+// out_scale; `set` < 0 / a NaN gain in a queued request mean "not asked for"
+struct Asg {
+    int set = 0;
+    double gain = 1.0;
+    bool operator==(const Asg &o) const { return set == o.set && gain == o.gain; }
+};
+
+// an output's overflow struct before its first sample (bf_reset_peak)
+DevOverflow over_initial(const bfhip_format &f) {
+    DevOverflow o;
+    memset(&o, 0, sizeof(o));
+    o.max = f.isfloat ? 1.0 : (double)((uint64_t)1 << ((f.sbytes << 3) - 1)) - 1;
+    return o;
+}
+
 struct Seg {
     int L = 0, N = 0;
     long off = 0;               // first tap this segment covers
@@ -457,7 +516,7 @@ struct Seg {
     // coefficient switches (only allocated when some filter has more than one set)
     void *d_out2 = nullptr;     // [L][n_out]: the second assignment's output of a block run under both
     void *d_z = nullptr;        // spectra between the split-phase MAC and output calls
-    std::vector<int> eng_set;   // per filter: the set the engine's filter runs now
+    std::vector<Asg> eng_set;   // per filter: the set and gain the engine's filter runs now
     std::vector<std::vector<int>> n_blocks;   // [filter][set]: partitions the set has in this engine
     hipEvent_t ev_upd = nullptr;   // background segment with a reservation: its share of a rewrite is done
 };
@@ -486,28 +545,35 @@ struct bfhip_nupc {
     size_t frame_bytes[2] = {0, 0};        // interleaved raw frame size in / out
     uint8_t *d_rawout = nullptr;
     DevFormat *d_fmt_out = nullptr;
-    double *d_inv_scale = nullptr;
+    NupcGain *d_gain = nullptr;            // [n_out]: 1/scale, output gain and its ramp (the emit step advances it)
     DevOverflow *d_over = nullptr;
     int *d_status = nullptr;
     // coefficient sets and switches (filters numbered in add_filter order; set j of filter f is
     // engine coefficient coeff[f][j] in every segment engine)
     std::vector<std::vector<int>> coeff;
-    std::vector<int> live;                 // per filter: the set of the newest committed assignment
-    std::vector<int> queued;               // per filter: requested set, -1 = none
+    std::vector<double> out_scale;         // per filter: add_filter's, multiplied by the assignment's gain
+    std::vector<Asg> live;                 // per filter: the newest committed assignment
+    std::vector<Asg> queued;               // per filter: requested set (-1 = none) and gain (NaN = none)
     int crossfade = 0;                     // frames for the next switch (default L0)
-    bool can_switch = false;               // some filter has a second set: the spare ring exists
+    bool gain_reserve = false;             // bfhip_nupc_reserve_filter_gain: gain-only switches need the spare ring
+    bool can_switch = false;               // some filter has a second set, or gain_reserve: the spare ring exists
     void *d_acc2 = nullptr;                // the spare ring
     int cur = 0;                           // ring of the live assignment: 0 = d_acc, 1 = d_acc2
     bool sw = false;                       // a committed switch has old-assignment work or fade frames left
     long long t_sw = -1;                   // its switch frame (-1: none committed yet)
     int sw_F = 0;                          // its fade length
     long long old_hi = 0;                  // end of the frames the old assignment has written
-    std::vector<int> sw_old;               // the old assignment (the new one is `live`)
-    // output gain, folded into the emit step's 1/scale
+    std::vector<Asg> sw_old;               // the old assignment (the new one is `live`)
+    // output gain: `gain` is the value asked for last, gain_len the ramp length in force at that
+    // call; a block call that finds gain != ramp.g starts a ramp (or steps) from the gain of the last
+    // emitted frame.  `ramp` mirrors the device records: they are a pure function of the calls.
     std::vector<double> gain;
+    std::vector<int> gain_len;
+    std::vector<NupcGain> ramp;
+    int gain_ramp = 0;                     // bfhip_nupc_set_gain_ramp: for the set_output_gain calls from now on
     bool gain_dirty = false;
-    double *h_inv = nullptr;               // pinned staging of the per-channel factors
-    hipEvent_t ev_gain = nullptr;          // the last upload out of h_inv has been done
+    NupcGain *h_gain = nullptr;            // pinned staging of the records
+    hipEvent_t ev_gain = nullptr;          // the last upload out of h_gain has been done
     // HP-TPDF dither (dither.c; bfhip_nupc_enable_dither): one slot per dithered output, in
     // ascending channel order; the table walk advances L0 per block call
     std::vector<int> dither_ch;            // output channel of each slot
@@ -595,6 +661,7 @@ bfhip_nupc *bfhip_nupc_create(int device, int realsize, int n_in, int n_out, int
     }
     n->crossfade = seg_length[0];          // the reference's one-block fade
     n->gain.assign(n_out, 1.0);
+    n->gain_len.assign(n_out, 0);
     n->dl[0].resize(n_in);
     n->dl[1].resize(n_out);
     n->sd[0].assign(n_in, BFHIP_UNDEFINED_SUBDELAY);
@@ -619,7 +686,7 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
         if (s.ev_consumed) (void)hipEventDestroy(s.ev_consumed);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
-    void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_inv_scale, n->d_over, n->d_status, n->d_arrive,
+    void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_gain, n->d_over, n->d_status, n->d_arrive,
                  n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage,
                  n->d_sd_bank, n->d_sd_hist[0], n->d_sd_hist[1], n->d_fmt_in, n->d_in_real};
     for (void *q : p) if (q) (void)hipFree(q);
@@ -628,7 +695,7 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     if (n->h_in) (void)hipHostFree(n->h_in);
     if (n->h_out) (void)hipHostFree(n->h_out);
     if (n->h_over) (void)hipHostFree(n->h_over);
-    if (n->h_inv) (void)hipHostFree(n->h_inv);
+    if (n->h_gain) (void)hipHostFree(n->h_gain);
     if (n->h_upd) (void)hipHostFree(n->h_upd);
     if (n->h_upd_bad) (void)hipHostFree(n->h_upd_bad);
     if (n->d_upd) (void)hipFree(n->d_upd);
@@ -699,15 +766,16 @@ int bfhip_nupc_add_filter(bfhip_nupc *n, int in_ch, int out_ch, const void *taps
         if (c < 0) return nfail(c, std::string("nupc_add_filter: ") + bfhip_last_error());
         if (set0 >= 0 && c != set0) return nfail(BFHIP_EINVAL, "nupc_add_filter: the segment engines disagree on coefficient numbering");
         set0 = c;
-        s.eng_set.push_back(0);
+        s.eng_set.push_back(Asg());
         s.n_blocks.push_back({take == 0 ? 1 : (int)((take + s.L - 1) / s.L)});
         // the engines emit plain reals: the output format's 1/scale is applied at the emit step
         const int r = bfhip_engine_add_filter(s.eng, 1, &in_ch, &in_scale, 0, nullptr, nullptr, 1, &out_ch, &out_scale, c, 0, 0);
         if (r < 0) return nfail(r, std::string("nupc_add_filter: ") + bfhip_last_error());
     }
     n->coeff.push_back({set0});
-    n->live.push_back(0);
-    n->queued.push_back(-1);
+    n->out_scale.push_back(out_scale);
+    n->live.push_back(Asg());
+    n->queued.push_back(Asg{-1, NAN});
     return BFHIP_OK;
 }
 
@@ -738,6 +806,7 @@ int bfhip_nupc_add_coeff(bfhip_nupc *n, int filter, const void *taps, long n_tap
 }
 
 static int nupc_finalize_impl(bfhip_nupc *n);
+namespace { int seg_assign(Seg &s, const bfhip_nupc *n, const std::vector<Asg> &asg); }
 
 int bfhip_nupc_finalize(bfhip_nupc *n) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
@@ -804,20 +873,19 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(bfhip_internal_dev_alloc((void **)&n->d_rawout, (size_t)L0 * n->frame_bytes[1]));
     NCHK(hipMemset(n->d_rawout, 0, (size_t)L0 * n->frame_bytes[1]));
     std::vector<DevFormat> df(n->n_out);
-    std::vector<double> inv(n->n_out);
+    n->ramp.resize(n->n_out);
     std::vector<DevOverflow> ov(n->n_out);
     for (int ch = 0; ch < n->n_out; ch++) {
         const bfhip_format &f = n->fmt[1][ch];
         df[ch].isfloat = f.isfloat; df[ch].swap = f.swap; df[ch].bytes = f.bytes; df[ch].sbytes = f.sbytes;
         df[ch].sample_spacing = f.sample_spacing; df[ch].byte_offset = f.byte_offset; df[ch].alt = nullptr;
-        inv[ch] = 1.0 / f.scale * n->gain[ch];                           // bfrun.c:1850
-        memset(&ov[ch], 0, sizeof(DevOverflow));
-        ov[ch].max = f.isfloat ? 1.0 : (double)((uint64_t)1 << ((f.sbytes << 3) - 1)) - 1;
+        n->ramp[ch] = NupcGain{1.0 / f.scale, n->gain[ch], n->gain[ch], 0, 0};   // bfrun.c:1850: inv * g
+        ov[ch] = over_initial(f);
     }
     NCHK(bfhip_internal_dev_alloc((void **)&n->d_fmt_out, df.size() * sizeof(DevFormat)));
     NCHK(hipMemcpy(n->d_fmt_out, df.data(), df.size() * sizeof(DevFormat), hipMemcpyHostToDevice));
-    NCHK(bfhip_internal_dev_alloc((void **)&n->d_inv_scale, inv.size() * sizeof(double)));
-    NCHK(hipMemcpy(n->d_inv_scale, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
+    NCHK(bfhip_internal_dev_alloc((void **)&n->d_gain, n->ramp.size() * sizeof(NupcGain)));
+    NCHK(hipMemcpy(n->d_gain, n->ramp.data(), n->ramp.size() * sizeof(NupcGain), hipMemcpyHostToDevice));
     NCHK(bfhip_internal_dev_alloc((void **)&n->d_over, ov.size() * sizeof(DevOverflow)));
     NCHK(hipMemcpy(n->d_over, ov.data(), ov.size() * sizeof(DevOverflow), hipMemcpyHostToDevice));
     NCHK(bfhip_internal_dev_alloc((void **)&n->d_status, sizeof(int)));
@@ -829,7 +897,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_out, (size_t)L0 * n->frame_bytes[1], hipHostMallocDefault));
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_over, (size_t)n->n_out * sizeof(DevOverflow), hipHostMallocDefault));
     *n->h_status = 0;
-    NCHK(bfhip_internal_pin_alloc((void **)&n->h_inv, (size_t)n->n_out * sizeof(double), hipHostMallocDefault));
+    NCHK(bfhip_internal_pin_alloc((void **)&n->h_gain, (size_t)n->n_out * sizeof(NupcGain), hipHostMallocDefault));
     NCHK(hipEventCreateWithFlags(&n->ev_gain, hipEventDisableTiming));
     NCHK(hipEventRecord(n->ev_gain, n->stream));
     n->gain_dirty = false;
@@ -879,6 +947,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
         NCHK(bfhip_internal_dev_alloc((void **)&n->d_in_real, (size_t)n->in_frames * n->n_in * n->rs));
         NCHK(hipMemset(n->d_in_real, 0, (size_t)n->in_frames * n->n_in * n->rs));
     }
+    n->can_switch = n->gain_reserve;
     for (auto &c : n->coeff) n->can_switch = n->can_switch || c.size() > 1;
     if (n->can_switch) {
         NCHK(bfhip_internal_dev_alloc((void **)&n->d_acc2, (size_t)A * n->n_out * n->rs));
@@ -901,6 +970,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
             f.sample_spacing = n->n_out; f.byte_offset = ch * n->rs;
             ECHK(bfhip_engine_set_format(s.eng, BFHIP_OUT, ch, &f));
         }
+        { const int r = seg_assign(s, n, n->live); if (r < 0) return r; }   // initial gains other than 1
         ECHK(bfhip_engine_set_overlap(s.eng, 0));          // a segment's kernels are ordered on ONE stream
         ECHK(bfhip_engine_finalize(s.eng));
         const long slack = s.off - ((long)s.L - L0);       // >= 0, checked at create
@@ -1034,21 +1104,24 @@ void nupc_emit_launch(bfhip_nupc *n, void *acc_old, void *acc_new, unsigned long
     const size_t smem = SD ? nupc_sd_smem(n, 1) : 0;
     if (!n->dither_ch.empty())
         hipLaunchKernelGGL((nupc_emit_dither_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old,
-                           (T *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale,
+                           (T *)acc_new, opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_gain,
                            n->d_over, (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status,
                            n->d_dither_slot, (T *)n->d_dither_stage, (DitherState<T> *)n->d_dither_state,
                            n->d_dither_table, (int)n->dither_table.size(), (const T *)n->d_randmap + 256, sd);
     else
         hipLaunchKernelGGL((nupc_emit_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old, (T *)acc_new,
-                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_inv_scale, n->d_over,
+                           opos, n->A, n->n_out, L0, rel0, n->sw_F, n->d_fmt_out, n->d_gain, n->d_over,
                            (uint8_t *)rawout_dev, n->safety_limit, n->d_status, n->d_arrive, n->h_status, sd);
 }
 
 // point a segment engine's filters at an assignment (a plan rebuild at its next call if any moved)
-int seg_assign(Seg &s, const bfhip_nupc *n, const std::vector<int> &asg) {
+int seg_assign(Seg &s, const bfhip_nupc *n, const std::vector<Asg> &asg) {
     for (size_t f = 0; f < asg.size(); f++) {
         if (s.eng_set[f] == asg[f]) continue;
-        ECHK(bfhip_engine_set_coeff(s.eng, (int)f, n->coeff[f][asg[f]]));
+        if (s.eng_set[f].set != asg[f].set) ECHK(bfhip_engine_set_coeff(s.eng, (int)f, n->coeff[f][asg[f].set]));
+        // an output scale dirties the plan only (no private ring); out_scale * 1.0 is out_scale
+        if (s.eng_set[f].gain != asg[f].gain)
+            ECHK(bfhip_engine_set_scale(s.eng, (int)f, BFHIP_OUT, 0, n->out_scale[f] * asg[f].gain));
         s.eng_set[f] = asg[f];
     }
     return BFHIP_OK;
@@ -1059,7 +1132,7 @@ int seg_assign(Seg &s, const bfhip_nupc *n, const std::vector<int> &asg) {
 // d_out2.  The engine keeps whichever assignment it ran last, so a run of dual blocks costs one
 // plan rebuild each, not two.
 int seg_run(bfhip_nupc *n, Seg &s, const uint8_t *in, int mode /* 0 old, 1 new, 2 both */) {
-    const std::vector<int> &old_asg = n->sw ? n->sw_old : n->live;
+    const std::vector<Asg> &old_asg = n->sw ? n->sw_old : n->live;
     if (mode != 2) {
         { const int r = seg_assign(s, n, mode == 0 ? old_asg : n->live); if (r < 0) return r; }
         ECHK(bfhip_engine_block_dev(s.eng, in, s.d_out));
@@ -1079,9 +1152,12 @@ int seg_run(bfhip_nupc *n, Seg &s, const uint8_t *in, int mode /* 0 old, 1 new, 
 
 // the queued requests become one switch whose first output block is the one starting at t_req
 void nupc_commit(bfhip_nupc *n, unsigned long long t_req) {
-    std::vector<int> asg = n->live;
-    for (size_t f = 0; f < asg.size(); f++) if (n->queued[f] >= 0) asg[f] = n->queued[f];
-    std::fill(n->queued.begin(), n->queued.end(), -1);
+    std::vector<Asg> asg = n->live;
+    for (size_t f = 0; f < asg.size(); f++) {
+        if (n->queued[f].set >= 0) asg[f].set = n->queued[f].set;
+        if (!std::isnan(n->queued[f].gain)) asg[f].gain = n->queued[f].gain;
+    }
+    std::fill(n->queued.begin(), n->queued.end(), Asg{-1, NAN});
     if (asg == n->live) return;                                   // nothing changes
     const unsigned long long L0 = (unsigned long long)n->seg[0].L;
     long long t_sw = (long long)t_req;
@@ -1148,7 +1224,7 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
         return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: bad argument");
     if (!n->finalized || !n->upd_reserve)
         return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: needs bfhip_nupc_reserve_update before finalize, and finalize");
-    if (coeff == n->live[filter] || coeff == n->queued[filter] || (n->sw && coeff == n->sw_old[filter]))
+    if (coeff == n->live[filter].set || coeff == n->queued[filter].set || (n->sw && coeff == n->sw_old[filter].set))
         return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: the set is live or part of a queued / in-flight switch");
     OWNER(n);
     { const int r = upd_poll(n); if (r < 0) return r; }
@@ -1249,11 +1325,24 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     // sub-delay on the input side: convert (and filter) the slot once, in front of all segments
     if (n->sd_use[0]) { const int r = nupc_subdelay_in(n, n->d_in + wpos * n->frame_bytes[0], wpos); if (r < 0) return r; }
     if (n->gain_dirty) {
-        // output gains set since the last block: in force from this block's first frame
-        NCHK(hipEventSynchronize(n->ev_gain));                    // the previous upload has read h_inv
-        for (int ch = 0; ch < n->n_out; ch++) n->h_inv[ch] = 1.0 / n->fmt[1][ch].scale * n->gain[ch];
-        NCHK(hipMemcpyAsync(n->d_inv_scale, n->h_inv, (size_t)n->n_out * sizeof(double), hipMemcpyHostToDevice, n->stream));
-        NCHK(hipEventRecord(n->ev_gain, n->stream));
+        // output gains set since the last block: this block's first frame is the first of the step
+        // or ramp, which starts from the gain of the last emitted frame.  Every record goes up as
+        // the mirror has it: where the other channels' ramps are now.
+        bool changed = false;
+        for (int ch = 0; ch < n->n_out; ch++) {
+            NupcGain &r = n->ramp[ch];
+            if (n->gain[ch] == r.g) continue;
+            const double prev = r.done >= r.len ? r.g : r.a + (r.g - r.a) * ((double)r.done / (double)r.len);
+            r.a = n->gain_len[ch] ? prev : n->gain[ch];
+            r.g = n->gain[ch]; r.done = 0; r.len = n->gain_len[ch];
+            changed = true;
+        }
+        if (changed) {
+            NCHK(hipEventSynchronize(n->ev_gain));                // the previous upload has read h_gain
+            std::copy(n->ramp.begin(), n->ramp.end(), n->h_gain);
+            NCHK(hipMemcpyAsync(n->d_gain, n->h_gain, (size_t)n->n_out * sizeof(NupcGain), hipMemcpyHostToDevice, n->stream));
+            NCHK(hipEventRecord(n->ev_gain, n->stream));
+        }
         n->gain_dirty = false;
     }
     if (!n->sw) nupc_commit(n, end - L0);
@@ -1311,6 +1400,7 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
         else nupc_emit_launch<double, false>(n, acc_old, acc_new, opos, rel0, rawout_dev);
     }
     NCHK(hipGetLastError());
+    for (NupcGain &r : n->ramp) if (r.done < r.len) r.done = r.len - r.done < L0 ? r.len : r.done + L0;   // gain_advance's mirror
     // output delay and mute on the quantised block (block() copies it out behind this)
     { const int r = nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev); if (r < 0) return r; }
     n->block++;
@@ -1393,7 +1483,7 @@ int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff) {
         if (n->upd_bad[filter][coeff])
             return nfail(BFHIP_ESTATE, "nupc_set_coeff: the last rewrite of this set found a NaN or Inf value among its coefficients");
     }
-    n->queued[filter] = coeff;
+    n->queued[filter].set = coeff;
     return BFHIP_OK;
 }
 
@@ -1413,7 +1503,7 @@ int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *ta
     if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size() ||
         !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
         return nfail(BFHIP_EINVAL, "nupc_update_coeff: bad argument");
-    if (coeff == n->live[filter] || coeff == n->queued[filter] || (n->sw && coeff == n->sw_old[filter]))
+    if (coeff == n->live[filter].set || coeff == n->queued[filter].set || (n->sw && coeff == n->sw_old[filter].set))
         return nfail(BFHIP_ESTATE, "nupc_update_coeff: the set is live or part of a queued / in-flight switch");
     OWNER(n);
     if (n->upd_reserve && n->finalized) {
@@ -1559,7 +1649,52 @@ int bfhip_nupc_update_wait(bfhip_nupc *n) {
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (out_ch < 0 || out_ch >= n->n_out || !std::isfinite(gain)) return nfail(BFHIP_EINVAL, "nupc_set_output_gain: bad argument");
-    if (n->gain[out_ch] != gain) { n->gain[out_ch] = gain; n->gain_dirty = true; }
+    if (n->gain[out_ch] != gain) { n->gain[out_ch] = gain; n->gain_len[out_ch] = n->gain_ramp; n->gain_dirty = true; }
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_gain_ramp(bfhip_nupc *n, int frames) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (frames < 0 || frames > 1048576) return nfail(BFHIP_EINVAL, "nupc_set_gain_ramp: 0 (step) or 1 .. 1048576 frames");
+    n->gain_ramp = frames;
+    return BFHIP_OK;
+}
+
+// ---- run-time control: per-filter gain as part of a switch ----------------------------------
+
+int bfhip_nupc_reserve_filter_gain(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_filter_gain after finalize");
+    n->gain_reserve = true;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_set_filter_gain(bfhip_nupc *n, int filter, double gain) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (filter < 0 || filter >= (int)n->coeff.size() || !std::isfinite(gain))
+        return nfail(BFHIP_EINVAL, "nupc_set_filter_gain: bad filter, or a gain that is not finite");
+    if (!n->finalized) { n->live[filter].gain = gain; return BFHIP_OK; }     // the initial gain
+    if (!n->gain_reserve) return nfail(BFHIP_ESTATE, "nupc_set_filter_gain: needs bfhip_nupc_reserve_filter_gain before finalize");
+    if (n->sw) return nfail(BFHIP_ESTATE, "nupc_set_filter_gain: the previous switch is still in flight (bfhip_nupc_switch_busy)");
+    n->queued[filter].gain = gain;
+    return BFHIP_OK;
+}
+
+double bfhip_nupc_get_filter_gain(const bfhip_nupc *n, int filter) {
+    if (!n || filter < 0 || filter >= (int)n->coeff.size()) { nfail(BFHIP_EINVAL, "nupc_get_filter_gain: bad argument"); return NAN; }
+    return n->live[filter].gain;
+}
+
+// bf_reset_peak(): the initial structs go up behind the periods handed in so far and in front of
+// the next one, through block()'s pinned staging (idle between block() calls; a second reset
+// writes the same bytes into it); no host wait
+int bfhip_nupc_reset_overflow(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc not finalized");
+    OWNER(n);
+    NCHK(hipSetDevice(n->device));
+    for (int ch = 0; ch < n->n_out; ch++) n->h_over[ch] = over_initial(n->fmt[1][ch]);
+    NCHK(hipMemcpyAsync(n->d_over, n->h_over, (size_t)n->n_out * sizeof(DevOverflow), hipMemcpyHostToDevice, n->stream));
     return BFHIP_OK;
 }
 

@@ -198,9 +198,63 @@ int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, 
    offline use.  BFHIP_ESTATE while a rewrite is in flight (it shares the scratch). */
 int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[],
                          const double mag[], const double phase[], void *taps_out);
-/* per-output gain applied at the emit step, exact from the first frame of the next block call's
-   output; 0.0 mutes; default 1.0 (folded into the 1/scale factor: exact) */
+/* per-output gain applied at the emit step, in force from the first frame of the next block call's
+   output (a step, or the start of a ramp: bfhip_nupc_set_gain_ramp below); 0.0 mutes; default 1.0
+   (multiplied into the 1/scale factor in float64: exact) */
 int bfhip_nupc_set_output_gain(bfhip_nupc *n, int out_ch, double gain);
+
+/* ---- run-time control: per-filter gains (cffa / cfoa) and ramped output gain ----------------
+ * Per-filter gain.  An assignment is, per filter, a pair (set, gain), not a set alone: under an
+ * assignment filter f contributes  in_scale * out_scale * gain_f * (x_in * taps_set).  A gain
+ * change is a switch like any other -- t_sw, y_old / y_new as full-history convolutions, the
+ * linear ramp of bfhip_nupc_set_crossfade, then output gain, 1/scale and quantisation, all as
+ * defined above -- so it is click-free through the cross-fade and exact in the sense a set switch
+ * is.  In a 2x2 crossbar that is the balance, the crossfeed amount and the polarity of one path.
+ * All bfhip_nupc_set_coeff and bfhip_nupc_set_filter_gain calls made before the next block call
+ * form ONE switch; a group that changes neither a set nor a gain commits none (switch_frame, the
+ * launches and the output bytes stay as they were).  A per-filter change takes effect up to
+ * max_k off_k frames after the request, as a set switch does, and costs what a switch window
+ * costs (dual segment blocks, one plan rebuild each); the output gain below is the knob for
+ * immediate changes.  The gain multiplies the segment engines' output scale (out_scale * 1.0 is
+ * out_scale: gain 1.0 changes no bit); the state rules of the set rewrites refer to sets only.
+ * A convolver that neither reserves nor has a second set allocates nothing more, makes the same
+ * launches and changes no byte.
+ *
+ * Output gain ramp, per output channel.  g_prev is the gain applied to the last emitted frame
+ * (before the first frame: the channel's gain at finalize), g_tgt the current target.  A call
+ * set_output_gain(ch, g) with g == g_tgt changes nothing and does not restart a running ramp.
+ * Otherwise, with t0 the first frame of the next block call, R the ramp length in force at the
+ * call and a = g_prev at t0 - 1:
+ *     R == 0   g(t) = g for t >= t0 (a step: the bits of a convolver that never set a ramp)
+ *     R >= 1   g(t0 + j) = a + (g - a) (j + 1) / R   for 0 <= j < R - 1,   g exactly for j >= R - 1
+ * across as many periods as it takes.  A new target during a ramp starts a new ramp from the value
+ * of the last emitted frame; of several calls for a channel before one block call the last counts.
+ * g is evaluated in float64 for both precisions and the sample is multiplied by
+ * (real)((1 / scale) * g); everything behind the factor -- the sub-delay FIR's input, the dither
+ * chain's input, the quantiser, the overflow accounting -- is as before, so the FIR filters the
+ * ramped values and a gain ramped to 0 gives dithered silence.  The emit step evaluates the factor
+ * per frame and advances the ramp on the device: a ramp in progress needs no upload, no launch and
+ * no host wait; only a new target uploads the channels' records (32 bytes each).
+ * Cost: DESIGN.md section 4.
+ */
+/* gain-only switches need the spare accumulator ring and the second segment output buffers, which
+   otherwise exist only when some filter has a second set: before finalize (BFHIP_ESTATE after) */
+int bfhip_nupc_reserve_filter_gain(bfhip_nupc *n);
+/* gain: finite (BFHIP_EINVAL otherwise), negative flips the polarity, 0.0 silences the filter (its
+   contribution is exact zeros).  Before finalize: the filter's initial gain (default 1.0; needs no
+   reservation).  After finalize: queued like bfhip_nupc_set_coeff; BFHIP_ESTATE without the
+   reservation, and while bfhip_nupc_switch_busy (nothing changes) */
+int bfhip_nupc_set_filter_gain(bfhip_nupc *n, int filter, double gain);
+/* the gain of the newest committed assignment: the new value once the block call that committed
+   the switch has returned, the old one before.  NaN on a bad handle / filter */
+double bfhip_nupc_get_filter_gain(const bfhip_nupc *n, int filter);
+/* ramp length in frames for the bfhip_nupc_set_output_gain calls made from now on, at any time:
+   0 = step (default), 1 .. 1048576; else BFHIP_EINVAL */
+int bfhip_nupc_set_gain_ramp(bfhip_nupc *n, int frames);
+/* bf_reset_peak (bfhip_engine_reset_overflow's counterpart): every output's overflow struct back
+   to its initial value, stream-ordered in front of the next block call; no host wait.  Status bits
+   are not touched */
+int bfhip_nupc_reset_overflow(bfhip_nupc *n);
 
 /* ---- run-time control: per-channel integer delay and mute (delay: / maxdelay:, cid / cod,
  * cmi / cmo) -------------------------------------------------------------------------------

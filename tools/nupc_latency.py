@@ -9,7 +9,7 @@ bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, ne
 uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
-                                  [--rewrite | --rewrite-sync | --eq] [--dump-output FILE]
+                                  [--gain-ramp] [--rewrite | --rewrite-sync | --eq] [--dump-output FILE]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
@@ -24,7 +24,10 @@ periods with a rewrite in flight and without.  --eq is --rewrite with the taps r
 every 300 periods a new random equaliser curve (130 bands, +-12 dB) is rendered at 1 048 576 taps into
 the idle set of each filter (bfhip_nupc_render_eq_async), then switched to; it also reports the wall time
 of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wait) of 8 and of 1 048 576
-taps, made before the timed loop: an upper bound of the render's device time.  --dump-output writes the raw output of all timed
+taps, made before the timed loop: an upper bound of the render's device time.  --gain-ramp sets an
+output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
+0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
+--dump-output writes the raw output of all timed
 and untimed periods to FILE (to compare two builds byte for byte)."""
 import argparse
 import json
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--dither", action="store_true")
     ap.add_argument("--delay", action="store_true")
     ap.add_argument("--subdelay", action="store_true")
+    ap.add_argument("--gain-ramp", action="store_true")
     ap.add_argument("--rewrite", action="store_true")
     ap.add_argument("--rewrite-sync", action="store_true")
     ap.add_argument("--eq", action="store_true")
@@ -116,8 +120,17 @@ def main():
     gc.disable()                       # the timed loop allocates one small array per period
     ts = []
     drng = np.random.default_rng(9)
-    n_changes = n_sd_changes = 0
+    n_changes = n_sd_changes = n_ramps = 0
+    ramp_periods, ramp_left, ramping = 5, 0, []
+    if a.gain_ramp:
+        nu.set_gain_ramp(ramp_periods * L0)
     for s in range(steps + 256):
+        if a.gain_ramp and s % 300 == 299:
+            for o in range(2):
+                nu.set_output_gain(o, float(drng.uniform(0.0, 2.0)))
+            n_ramps, ramp_left = n_ramps + 1, ramp_periods
+        ramping.append(ramp_left > 0)
+        ramp_left = max(ramp_left - 1, 0)
         if a.delay and s % 300 == 299:
             for o in range(2):
                 nu.set_delay(bf.OUT, o, int(drng.integers(0, 48001)))
@@ -181,6 +194,7 @@ def main():
         np.concatenate(dump).tofile(a.dump_output)
     ts = np.array(ts[256:]) * 1e3
     fl = np.array(in_flight[256:], bool)
+    rp = np.array(ramping[256:], bool)
 
     def dist(v):
         v = np.asarray(v, float)
@@ -198,6 +212,9 @@ def main():
         "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
         "subdelay": {"sdf_length": 31, "inputs": [0, 1], "outputs": [0, 1], "changes_every_periods": 300,
                      "changes": n_sd_changes} if a.subdelay else None,
+        "gain_ramp": {"ramp_frames": ramp_periods * L0, "outputs": [0, 1], "new_target_every_periods": 300,
+                      "ramps": n_ramps, "step_ms_ramp_in_progress": dist(ts[rp]),
+                      "step_ms_no_ramp": dist(ts[~rp])} if a.gain_ramp else None,
         "rewrite": {"mode": "eq" if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
                     "taps_per_set": int(nu.taps), "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),

@@ -9,7 +9,13 @@ Periods are split into switch-window periods (a switch is committed by the call 
 flight when it starts: segment blocks run under both assignments, segment engines rebuild
 their plans) and steady periods (no switch in flight).  Prints one JSON line: median / p99.9 /
 max milliseconds per bfhip_nupc_block call for both, against the period at 48 kHz.  Compare the
-steady line with tools/nupc_latency.py, which never switches."""
+steady line with tools/nupc_latency.py, which never switches.
+
+    python3 tools/nupc_switch_latency.py [L0 [steps]] [--gain]
+
+--gain: the switches are gain-only (bfhip_nupc_set_filter_gain on every filter, alternating between
+two gain presets; one set per filter and bfhip_nupc_reserve_filter_gain): the same window mechanism
+without a second set of coefficients."""
 import json
 import os
 import sys
@@ -28,8 +34,10 @@ def stats(ts):
 
 def main():
     import brutefir_amd as bf
-    L0 = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
+    argv = [v for v in sys.argv[1:] if v != "--gain"]
+    gain = "--gain" in sys.argv[1:]
+    L0 = int(argv[0]) if len(argv) > 0 else 64
+    steps = int(argv[1]) if len(argv) > 1 else 4096
     seg_len, k = [], L0
     while k < 8192:
         seg_len.append(k)
@@ -45,8 +53,12 @@ def main():
     for f in range(4):
         h = [rng.standard_normal(1048576) * np.exp(-np.arange(1048576) / 2e5) / 2000.0 for _ in range(2)]
         nu.add_filter(f % 2, f // 2, h[0])
-        nu.add_coeff(f, h[1])
+        if not gain:
+            nu.add_coeff(f, h[1])
+    if gain:
+        nu.reserve_filter_gain()
     nu.finalize()
+    presets = [[1.0, 1.0, 1.0, 1.0], [0.7, -0.4, 0.25, 1.3]]
     x = rng.standard_normal((8, L0, 2)) * 0.1
     import gc
     gc.disable()                       # the timed loop allocates one small array per period
@@ -55,7 +67,10 @@ def main():
         in_window = nu.switch_busy()
         if not in_window and s >= 256 + steps // 2:
             for f in range(4):
-                nu.set_coeff(f, target)
+                if gain:
+                    nu.set_filter_gain(f, presets[target][f])
+                else:
+                    nu.set_coeff(f, target)
             target, in_window, switches = 1 - target, True, switches + 1
         t0 = time.perf_counter()
         st, _ = nu.block(x[s & 7])
@@ -65,8 +80,10 @@ def main():
     ts = np.array(ts[256:]) * 1e3
     window = np.array(window[256:])
     print(json.dumps({
-        "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s, two sets per filter, "
-                    "back-to-back switches with a %d-frame cross-fade" % (nu.taps, seg_len, seg_blk, L0),
+        "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s, %s, "
+                    "back-to-back switches with a %d-frame cross-fade"
+                    % (nu.taps, seg_len, seg_blk, "one set per filter, gain-only" if gain else "two sets per filter", L0),
+        "switch_kind": "gain" if gain else "coeff",
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0, "switches": switches,
         "switch_window_ms": stats(ts[window]), "steady_ms": stats(ts[~window]),
         "slowest_periods": [[int(i) + 256, round(float(ts[i]), 3), bool(window[i])] for i in np.argsort(ts)[::-1][:4]],
