@@ -139,6 +139,7 @@ def lib():
     L.bfhip_engine_uses_stream_layout.argtypes = [vp]
     L.bfhip_engine_uses_diag_mac.argtypes = [vp]
     L.bfhip_engine_window_blocks.argtypes = [vp]
+    L.bfhip_engine_lookahead_blocks.argtypes = [vp]
     L.bfhip_engine_enable_pairs.argtypes = [vp, ci]
     L.bfhip_engine_block_pair_dev.argtypes = [vp, vp, vp, vp, vp]
     L.bfhip_engine_pair_launches.argtypes = [vp]
@@ -525,6 +526,11 @@ class Engine:
     def window_blocks(self):
         """4: the plan in force runs long-window overlap-save (4-block windows); 2: standard"""
         return _check(lib().bfhip_engine_window_blocks(self.h))
+
+    @property
+    def lookahead_blocks(self):
+        """3: the long plan in force runs the look-ahead MAC (tails of the next 3 blocks per call); 0: not"""
+        return _check(lib().bfhip_engine_lookahead_blocks(self.h))
 
     @property
     def ring_depth(self):

@@ -463,6 +463,20 @@ struct bfhip_engine {
     size_t lwhere_cap = 0;
     std::vector<std::array<const void *, OG + 1>> lkeys;     // per long entry: its sets and (delay, length)
     bool zp_long[3] = {false, false, false};                   // d_Zp[i] holds long partial spectra
+    // look-ahead long MAC (kernels.h, mac_la_*): call t computes the tails (partitions >= 1) of one slice
+    // of entries for blocks t+1 .. t+3 into the ahead buffers d_ahead[block mod 4][slice]; the block's own
+    // MAC is then the head pass (partition 0 on top of its three ahead buffers).  la_active: the plan
+    // built last may run it (build_long_layout).  The validity table names, per ahead buffer, the block
+    // (blocks_done when it runs) it was computed for and the epoch; anything that can change a product
+    // already stored bumps the epoch, and a block whose three buffers are not all current runs the full
+    // long MAC instead.
+    bool la_active = false;
+    void *d_ahead = nullptr;       // [4][3][n_out_padded][2L] complex
+    size_t ahead_cap = 0;
+    unsigned long long la_epoch = 1;
+    unsigned long long la_for[4][3] = {};
+    unsigned long long la_at[4][3] = {};       // epoch 0: never written
+    unsigned long long n_la_head = 0, n_la_full = 0;
 
     // real-time mode (bfhip_engine_rt_*): pinned host double buffer, the block's launch
     // sequence replayed from a HIP graph, completion signalled through pinned memory
@@ -848,6 +862,59 @@ void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
     *err = hipGetLastError();
 }
 
+// the look-ahead passes (kernels.h): ahead buffer of (block mod 4, slice)
+c2<float> *la_buffer(bfhip_engine *e, unsigned long long block, int slice) {
+    const size_t one = (size_t)e->n_out_padded * 2 * e->L;
+    return (c2<float> *)e->d_ahead + ((size_t)(block & 3ull) * 3 + (size_t)slice) * one;
+}
+void launch_mac_la_head(bfhip_engine *e, void *Zp, hipError_t *err) {
+    const int n_tc = e->lw_tiles;
+    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
+    const unsigned long long T = e->blocks_done;
+    const unsigned long long age64 = std::min<unsigned long long>(T + 1, (unsigned long long)e->N);
+    hipLaunchKernelGGL(mac_la_head_kernel<float>, dim3(grid), dim3(256), 0, e->ls,
+                       (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,
+                       (const c2<float> *)la_buffer(e, T, 0), (const c2<float> *)la_buffer(e, T, 1),
+                       (const c2<float> *)la_buffer(e, T, 2), 2 * e->L, e->n_groups, n_tc, e->blockcounter, (int)age64,
+                       e->lstream);
+    *err = hipGetLastError();
+}
+void launch_mac_la_tail(bfhip_engine *e, hipError_t *err) {
+    const int n_tc = e->lw_tiles;
+    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
+    const unsigned long long T = e->blocks_done;
+    const int slice = (int)(T % 3ull);
+    int age[3];
+    for (int k = 1; k <= 3; k++) age[k - 1] = (int)std::min<unsigned long long>(T + 1 + k, (unsigned long long)e->N);
+    hipLaunchKernelGGL(mac_la_tail_kernel<float>, dim3(grid), dim3(256), 0, e->ls,
+                       (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks,
+                       la_buffer(e, T + 1, slice), la_buffer(e, T + 2, slice), la_buffer(e, T + 3, slice),
+                       2 * e->L, e->n_groups, n_tc, e->blockcounter, age[0], age[1], age[2], slice, e->lstream);
+    *err = hipGetLastError();
+    if (*err != hipSuccess) return;
+    for (int k = 1; k <= 3; k++) {
+        e->la_for[(T + k) & 3ull][slice] = T + k;
+        e->la_at[(T + k) & 3ull][slice] = e->la_epoch;
+    }
+}
+// No block has been processed (or prewarm has just declared the zero-initialised rings N blocks of
+// silence): every window the tails of the next three blocks read is silence, so their ahead buffers
+// are zeros.  Store that instead of running three full MACs first.
+int la_prime(bfhip_engine *e) {
+    if (!e->la_active || e->d_ahead == nullptr) return BFHIP_OK;
+    HIPCHK(hipMemsetAsync(e->d_ahead, 0, e->ahead_cap, e->stream));
+    for (unsigned long long T = e->blocks_done; T < e->blocks_done + 3; T++)
+        for (int j = 0; j < 3; j++) { e->la_for[T & 3ull][j] = T; e->la_at[T & 3ull][j] = e->la_epoch; }
+    return BFHIP_OK;
+}
+// are the three ahead buffers of the block about to run current?
+bool la_block_valid(const bfhip_engine *e) {
+    const unsigned long long T = e->blocks_done;
+    for (int j = 0; j < 3; j++)
+        if (e->la_for[T & 3ull][j] != T || e->la_at[T & 3ull][j] != e->la_epoch) return false;
+    return true;
+}
+
 // [long K3 of `count` outputs from the long partial sums Zp | long K1 of this block's inputs (inputs)]
 constexpr int LW_LOG2 = 14;        // the 4B-point real transform of B = 8192: 2^14 complex points
 void launch_io_long(bfhip_engine *e, const void *Zp, int count, uint8_t *rawout, bool inputs, hipError_t *err) {
@@ -1083,6 +1150,7 @@ int derive_long(bfhip_engine *e, int p_first, int n_p, int n_which) {
 // standard partition `block` of set H changed in place: long partition block / 3 of every long entry
 // that uses H (or, with no long plan in force now, forget that those entries hold H)
 int long_refresh_block(bfhip_engine *e, const void *H, int block) {
+    e->la_epoch++;                 // products of the rewritten partition may be stored ahead
     if (e->lkeys.empty()) return BFHIP_OK;
     std::vector<int> hit;
     for (size_t i = 0; i < e->lkeys.size(); i++)
@@ -1212,6 +1280,8 @@ struct LongWhole { bool ok = false; int E = 0, P = 0; std::vector<int> wpos; };
 int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat, const std::vector<ChunkRange> &chunks, int S,
                       const LongWhole &lwh) {
     e->lw_active = false;
+    e->la_active = false;
+    e->la_epoch++;                 // a new plan: other sets, scales, delays or lengths than the stored products used
     if (!lwh.ok || flat.empty() || e->mac_diag || !e->mac_nt || e->mac_unroll != 0 || e->mac_threads != 256)
         return BFHIP_OK;
     const size_t L = e->L, LL = 2 * L;
@@ -1307,13 +1377,38 @@ int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat,
     HIPCHK(hipMemcpy(e->d_lchunks, lchunks.data(), cb, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_lwhere, where.data(), wb, hipMemcpyHostToDevice));
     e->lw_chunks = SL; e->lw_P = PL; e->lw_tiles = tiles; e->lw_Pstd = P;
-    e->lstream = StreamLayout{(const unsigned char *)e->d_lstream, slice, (unsigned int)entry_bytes, chunk};
+    e->lstream = StreamLayout{(const unsigned char *)e->d_lstream, slice, (unsigned int)entry_bytes, chunk,
+                              (unsigned int)E_here * OG * chunk};
     if (!changed.empty()) {
         HIPCHK(hipMemcpy(e->d_lwhich, changed.data(), changed.size() * sizeof(int), hipMemcpyHostToDevice));
         const int r = derive_long(e, 0, PL, (int)changed.size());
         if (r != BFHIP_OK) { e->lkeys.clear(); return r; }
     }
     e->lw_active = true;
+    // look-ahead: the whole plan is this engine's, one chunk per group, no tail partition reaches a block
+    // younger than t - 3 (the shifted last partition does when it is p = 1), and the coefficients are
+    // large enough to be worth three ahead buffers per block (BFHIP_LOOKAHEAD=1 / 0: always / never)
+    int want = -1;
+    if (const char *env = getenv("BFHIP_LOOKAHEAD")) want = atoi(env) != 0 ? 1 : 0;
+    double vol = 0;
+    for (auto &c : e->coeffs) vol += (double)c.n_blocks * (double)L * (double)sizeof(c2<float>);
+    bool la = want != 0 && (want == 1 || vol >= 1073741824.0) && SL == 1 && !e->sharded && !e->pairs &&
+              flat.size() == (size_t)e->n_groups * (size_t)lwh.E;
+    for (size_t i = 0; i < lflat.size() && la; i++) {
+        const MacEntry<float> &en = lflat[i];
+        la = en.dense == 1 && en.p0 == 0 && (en.maxP < 2 || 3 * (en.maxP - 1) - en.shift + en.delay >= 3);
+    }
+    if (la) {
+        const size_t ab = (size_t)4 * 3 * e->n_out_padded * LL * sizeof(c2<float>);
+        if (ab > e->ahead_cap) {
+            if (e->d_ahead) (void)hipFree(e->d_ahead);
+            e->d_ahead = nullptr; e->ahead_cap = 0;
+            if (dev_alloc(&e->d_ahead, ab) != hipSuccess) { (void)hipGetLastError(); la = false; }
+            else e->ahead_cap = ab;
+        }
+    }
+    e->la_active = la;
+    if (la && e->blocks_done == 0) return la_prime(e);
     return BFHIP_OK;
 }
 
@@ -1768,6 +1863,8 @@ int build_plan_t(bfhip_engine *e) {
         if (r != BFHIP_OK) return r;
     }
     e->lw_active = false;
+    e->la_active = false;
+    e->la_epoch++;
     if constexpr (std::is_same<T, float>::value) {
         const int r = build_long_layout(e, flat, chunks, S, lwh);
         if (r != BFHIP_OK) return r;
@@ -2178,9 +2275,20 @@ int do_mac(bfhip_engine *e, void *Zp, bool may_long = true) {
     const int zi = zp_index(e, Zp);
     const bool lng = e->lw_active && zi >= 0 && may_long;
     if (zi >= 0) e->zp_long[zi] = lng;
-    if (lng) launch_mac_long(e, Zp, &err);
+    // look-ahead (not under a captured graph or in real-time mode, whose launch arguments are frozen):
+    // the head pass when the block's three ahead buffers are current, else the full long MAC; either way
+    // the tail pass of this call's slice for the next three blocks behind it
+    const bool la = lng && e->la_active && e->bs_arg == nullptr && !e->rt.on;
+    if (la && la_block_valid(e)) { launch_mac_la_head(e, Zp, &err); e->n_la_head++; }
+    else if (lng) { launch_mac_long(e, Zp, &err); if (la) e->n_la_full++; }
     else if (e->rs == 4) launch_mac<float>(e, Zp, &err); else launch_mac<double>(e, Zp, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "mac launch: %s", hipGetErrorString(err));
+    if (la) {
+        launch_mac_la_tail(e, &err);
+        if (err != hipSuccess) return fail(BFHIP_EHIP, "look-ahead mac launch: %s", hipGetErrorString(err));
+    } else {
+        e->la_epoch++;             // a block without a tail pass: what is stored ahead no longer lines up
+    }
     return BFHIP_OK;
 }
 
@@ -2581,7 +2689,7 @@ void bfhip_engine_destroy(bfhip_engine *e) {
                     e->d_big[0], e->d_big[1], e->d_big[2], e->d_tw13, e->d_tww,
                     e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc, e->d_stream, e->d_where,
                     e->d_planar[0], e->d_planar[1], e->d_phys_skip,
-                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere};
+                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere, e->d_ahead};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto ev : e->ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -3575,9 +3683,11 @@ int bfhip_engine_set_fscale(bfhip_engine *e, int filter, int index, double scale
 static int lw_drop(bfhip_engine *e) {
     if (!e->lw_struct) return BFHIP_OK;
     { const int r = sync_all(e); if (r != BFHIP_OK) return r; }
-    e->lw_struct = e->lw_active = false;
-    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    e->lw_struct = e->lw_active = e->la_active = false;
+    e->la_epoch++;
+    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream, &e->d_ahead}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     e->lstream_cap = 0;
+    e->ahead_cap = 0;
     e->lstream = StreamLayout{nullptr, 0, 0, 0};
     e->lkeys.clear();
     for (bool &z : e->zp_long) z = false;
@@ -4081,6 +4191,8 @@ int bfhip_engine_prewarm(bfhip_engine *e) {
     // move the block counter past the point where (blockcounter - p - delay) would wrap
     e->blocks_done = (unsigned long long)e->N;
     e->blockcounter = (unsigned int)e->R;
+    e->la_epoch++;
+    { const int rp = la_prime(e); if (rp != BFHIP_OK) return rp; }
     e->rt.bs_synced = false;
     return BFHIP_OK;
 }
@@ -4144,6 +4256,10 @@ int bfhip_engine_uses_diag_mac(const bfhip_engine *e) { return e && e->mac_diag 
 int bfhip_engine_window_blocks(const bfhip_engine *e) {
     if (!e) return fail(BFHIP_EINVAL, "window_blocks: null engine");
     return e->lw_active ? 4 : 2;
+}
+int bfhip_engine_lookahead_blocks(const bfhip_engine *e) {
+    if (!e) return fail(BFHIP_EINVAL, "lookahead_blocks: null engine");
+    return e->lw_active && e->la_active && !e->rt.on ? 3 : 0;
 }
 int bfhip_engine_ring_depth(const bfhip_engine *e) { return e ? e->R : 0; }
 

@@ -80,6 +80,11 @@ struct StreamLayout {
     unsigned long long slice;       // bytes per workgroup
     unsigned int entry_bytes;       // P * OG * chunk
     unsigned int chunk;             // bytes of one tile of one set: blockDim.x * 16
+    // The long-window stream (ring step 3) keeps partition 0 of all of a workgroup's entries in front of
+    // the others: head region [q][j] (`head` = entries * OG * chunk bytes), then [q][p >= 1][j].  The
+    // look-ahead passes (mac_la_kernel) then read one sequential range each: the head pass the head
+    // region, the tail pass of a slice (a contiguous range of entries) its part of the rest.  0: as above.
+    unsigned int head;
 };
 
 // Per-block counters in device memory, for launch sequences replayed from a HIP graph (their
@@ -723,19 +728,29 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             // where partition p of term j starts for this lane: Hs[j] + p * hstep + hlane
             unsigned int hstep = (unsigned int)L * (unsigned int)sizeof(c2<T>);
             unsigned int hlane = (unsigned int)k0 * (unsigned int)sizeof(c2<T>);
+            // split long stream (StreamLayout::head): partition 0 and the others of an entry start at
+            // different places of the workgroup's slice -- hoff = (p == 0 ? hb0 : hbT + p * hstep) + hlane
+            unsigned int hb0 = 0u, hbT = 0u;
             if (UNROLL == 0 && sl.base != nullptr) {
-                const unsigned char *wg = sl.base + (unsigned long long)bid * sl.slice + (unsigned int)(e - cr.begin) * sl.entry_bytes;
-#pragma unroll
-                for (int j = 0; j < OG; j++) Hs[j] = (const c2<T> *)(wg + (unsigned int)j * sl.chunk);
+                const unsigned int q = (unsigned int)(e - cr.begin);
+                const unsigned char *wg = sl.base + (unsigned long long)bid * sl.slice;
                 hstep = (unsigned int)OG * sl.chunk;
                 hlane = (unsigned int)threadIdx.x * 16u;
+                if (PSTEP != 1 && sl.head != 0u) {
+                    hb0 = q * hstep;
+                    hbT = sl.head + q * (sl.entry_bytes - hstep) - hstep;
+                } else {
+                    wg += q * sl.entry_bytes;
+                }
+#pragma unroll
+                for (int j = 0; j < OG; j++) Hs[j] = (const c2<T> *)(wg + (unsigned int)j * sl.chunk);
             }
             if (mask != 0xffu) {
 #pragma unroll 2
                 for (int p = p0; p < maxP; p++) {
                     const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                     const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                    const unsigned int hoff = (unsigned int)p * hstep + hlane;     // set-major: (p * L + k0) * sizeof
+                    const unsigned int hoff = (PSTEP == 1 ? (unsigned int)p * hstep : (p == 0 ? hb0 : hbT + (unsigned int)p * hstep)) + hlane;     // set-major: (p * L + k0) * sizeof
                     c2<T> x[V], h[OG][V];
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), x);
 #pragma unroll
@@ -764,7 +779,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
                 auto issue = [&](Stage &st, int p) {
                     const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
                     const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                    const unsigned int hoff = (unsigned int)p * hstep + hlane;
+                    const unsigned int hoff = (PSTEP == 1 ? (unsigned int)p * hstep : (p == 0 ? hb0 : hbT + (unsigned int)p * hstep)) + hlane;
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), st.x);
 #pragma unroll
                     for (int j = 0; j < OG; j++) Load16<T, NT>::get((const c2<T> *)((const char *)Hs[j] + hoff), st.h[j]);
@@ -922,6 +937,233 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             zp[(size_t)j * L] = mk<T>(acc[j][0], acc[j][1]);
         }
     }
+}
+
+// ---- look-ahead long-window MAC ("look-ahead") ------------------------------------------
+// On the long plan every partition p >= 1 of block s multiplies ring blocks s - 3 and older: at call t
+// the ring holds all that the tails (p >= 1) of blocks t+1, t+2 and t+3 need, so one pass over a tail
+// coefficient tile feeds three output blocks.  The entries of a group are cut into three slices
+// (contiguous ranges: n/3 each, the first n%3 one more); call t runs slice t mod 3 and STORES its three
+// partial tails into the ahead buffers of blocks t+1 .. t+3, each (block, slice) buffer written exactly
+// once.  The head pass of block t starts from the three ahead buffers of block t (slice order 0, 1, 2)
+// and adds partition 0 of every entry, in entry order: the order of summation does not depend on
+// t mod 3.  Plain uniform crossbars only (every entry dense == 1, p0 == 0, one chunk per group), split
+// long stream (StreamLayout::head); products are formed exactly as mac_xbar_kernel forms them.
+struct LaSlice { int begin, end; };
+__device__ __forceinline__ LaSlice la_slice(ChunkRange cr, int j) {
+    const int n = cr.end - cr.begin, b = n / 3, r = n % 3;
+    const int first = cr.begin + j * b + (j < r ? j : r);
+    return LaSlice{first, first + b + (j < r ? 1 : 0)};
+}
+
+// head pass: Zp[o] = A0[o] + A1[o] + A2[o] + sum over entries of scale * W_(t + shift0 - delay) * G_(e, 0)
+template <typename T>
+__global__ __launch_bounds__(256) void
+mac_la_head_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__restrict__ chunks,
+                   c2<T> *__restrict__ Zp, const c2<T> *__restrict__ A0, const c2<T> *__restrict__ A1,
+                   const c2<T> *__restrict__ A2, int L, int n_groups, int n_tc, unsigned int t, int age,
+                   StreamLayout sl) {
+    static_assert(sizeof(T) == 4, "float32 only");
+    constexpr int V = 2;
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, local = bid >> 3;
+    const int group = local % n_groups;
+    const int tile = (local / n_groups) * 8 + xcd;
+    if (tile >= n_tc) return;
+    const int k0 = (tile * 256 + (int)threadIdx.x) * V;
+    if (k0 >= L) return;
+    const bool dc = (k0 == 0);
+    const T am = dc ? (T)0 : (T)1;
+    const size_t zoff = (size_t)group * OG * L + k0;
+
+    T acc[OG][2 * V];
+#pragma unroll
+    for (int j = 0; j < OG; j++) {
+        c2<T> a0[V], a1[V], a2[V];
+        Load16<T, false>::get(A0 + zoff + (size_t)j * L, a0);
+        Load16<T, false>::get(A1 + zoff + (size_t)j * L, a1);
+        Load16<T, false>::get(A2 + zoff + (size_t)j * L, a2);
+        acc[j][0] = (a0[0].x + a1[0].x) + a2[0].x; acc[j][1] = (a0[0].y + a1[0].y) + a2[0].y;
+        acc[j][2] = (a0[1].x + a1[1].x) + a2[1].x; acc[j][3] = (a0[1].y + a1[1].y) + a2[1].y;
+    }
+
+    const ChunkRange cr = chunks[group];
+    const unsigned char *wg = sl.base + (unsigned long long)bid * sl.slice;
+    const unsigned int hstep = (unsigned int)OG * sl.chunk, hlane = (unsigned int)threadIdx.x * 16u;
+    // one load pipeline over the entries: three of them (ring tile + OG coefficient tiles each) in flight
+    struct Stage { c2<T> x[V]; c2<T> h[OG][V]; T sc[OG]; bool on; };
+    auto issue = [&](Stage &st, int q) {
+        const MacEntry<T> *E = &entries[cr.begin + q];
+        const int delay = E->delay;
+        st.on = age - delay > 0 && E->maxP > 0;           // partition 0 exists yet (procblocks)
+#pragma unroll
+        for (int j = 0; j < OG; j++) st.sc[j] = E->term[j].scale;
+        if (!st.on) return;
+        const int back = E->maxP == 1 ? -E->shift : 0;    // a one-partition entry: its only window is the shifted last one
+        const unsigned int slot = (t - (unsigned int)back - (unsigned int)delay) % (unsigned int)E->R;
+        const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+        const unsigned int hoff = (unsigned int)q * hstep + hlane;
+        Load16<T, false>::get((const c2<T> *)((const char *)E->ring + xoff), st.x);
+#pragma unroll
+        for (int j = 0; j < OG; j++) Load16<T, true>::get((const c2<T> *)(wg + (unsigned int)j * sl.chunk + hoff), st.h[j]);
+    };
+    auto consume = [&](const Stage &st) {
+        if (!st.on) return;
+#pragma unroll
+        for (int j = 0; j < OG; j++) {
+            {
+                const T xr = st.x[0].x * st.sc[j], xi = st.x[0].y * st.sc[j];
+                cmac_first(acc[j][0], acc[j][1], xr, xi, st.h[j][0], am, dc);
+            }
+            {
+                const T xr = st.x[1].x * st.sc[j], xi = st.x[1].y * st.sc[j];
+                cmac(acc[j][2], acc[j][3], xr, xi, st.h[j][1]);
+            }
+        }
+    };
+    const int n = cr.end - cr.begin;
+    Stage s0, s1, s2;
+    s0.on = s1.on = s2.on = false;
+    if (n >= 1) issue(s0, 0);
+    if (n >= 2) issue(s1, 1);
+    if (n >= 3) issue(s2, 2);
+    int i = 0;
+    for (; i + 6 <= n; i += 3) {
+        consume(s0); issue(s0, i + 3);
+        consume(s1); issue(s1, i + 4);
+        consume(s2); issue(s2, i + 5);
+    }
+    for (; i + 3 <= n; i += 3) {
+        consume(s0); if (i + 3 < n) issue(s0, i + 3);
+        consume(s1); if (i + 4 < n) issue(s1, i + 4);
+        consume(s2); if (i + 5 < n) issue(s2, i + 5);
+    }
+    if (i < n) consume(s0);
+    if (i + 1 < n) consume(s1);
+
+    c2<T> *zp = Zp + zoff;
+#pragma unroll
+    for (int j = 0; j < OG; j++)
+        *reinterpret_cast<float4 *>(zp + (size_t)j * L) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+}
+
+// tail pass of slice `slice`: Zk[o] = sum over the slice's entries and p >= 1 of
+// scale * W_(t + k - 3p + shift_p - delay) * G_(e, p) for k = 1, 2, 3 (agek: the age block t + k will have)
+template <typename T>
+__global__ __launch_bounds__(256) void
+mac_la_tail_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__restrict__ chunks,
+                   c2<T> *__restrict__ Z1, c2<T> *__restrict__ Z2, c2<T> *__restrict__ Z3,
+                   int L, int n_groups, int n_tc, unsigned int t, int age1, int age2, int age3, int slice,
+                   StreamLayout sl) {
+    static_assert(sizeof(T) == 4, "float32 only");
+    constexpr int V = 2, NB = 3;
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, local = bid >> 3;
+    const int group = local % n_groups;
+    const int tile = (local / n_groups) * 8 + xcd;
+    if (tile >= n_tc) return;
+    const int k0 = (tile * 256 + (int)threadIdx.x) * V;
+    if (k0 >= L) return;
+    const bool dc = (k0 == 0);
+    const T am = dc ? (T)0 : (T)1;
+
+    T acc[NB][OG][2 * V];
+#pragma unroll
+    for (int k = 0; k < NB; k++)
+#pragma unroll
+        for (int j = 0; j < OG; j++)
+#pragma unroll
+            for (int v = 0; v < 2 * V; v++) acc[k][j][v] = (T)0;
+
+    const ChunkRange cr = chunks[group];
+    const LaSlice ls = la_slice(cr, slice);
+    const unsigned char *wg = sl.base + (unsigned long long)bid * sl.slice;
+    const unsigned int hstep = (unsigned int)OG * sl.chunk, hlane = (unsigned int)threadIdx.x * 16u;
+    const int ages[NB] = {age1, age2, age3};
+    for (int e = ls.begin; e < ls.end; e++) {
+        const MacEntry<T> *E = &entries[e];
+        const c2<T> *ring = E->ring;
+        const int R = E->R, delay = E->delay;
+        const int lastP = E->maxP - 1, shift = E->shift;
+        int pm[NB];
+#pragma unroll
+        for (int k = 0; k < NB; k++) {
+            const int avail = ages[k] - delay > 0 ? (ages[k] - delay + 2) / 3 : 0;
+            pm[k] = E->maxP < avail ? E->maxP : avail;
+        }
+        T sc[OG];
+#pragma unroll
+        for (int j = 0; j < OG; j++) sc[j] = E->term[j].scale;
+        const unsigned int hbT = sl.head + (unsigned int)(e - cr.begin) * (sl.entry_bytes - hstep) - hstep;
+        struct Stage { c2<T> x[NB][V]; c2<T> h[OG][V]; };
+        auto issue = [&](Stage &st, int p) {
+            // slot of block t + 3 - (3p - shift_p) - delay; those of t + 2 and t + 1 are the one and two before it
+            unsigned int slot = (t + 3u - (unsigned int)(3 * p - (p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
+            const unsigned int hoff = hbT + (unsigned int)p * hstep + hlane;
+#pragma unroll
+            for (int k = NB - 1; k >= 0; k--) {
+                const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+                Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), st.x[k]);
+                slot = slot == 0u ? (unsigned int)R - 1u : slot - 1u;
+            }
+#pragma unroll
+            for (int j = 0; j < OG; j++) Load16<T, true>::get((const c2<T> *)(wg + (unsigned int)j * sl.chunk + hoff), st.h[j]);
+        };
+        auto consume_k = [&](const Stage &st, int k) {
+#pragma unroll
+            for (int j = 0; j < OG; j++) {
+                {
+                    const T xr = st.x[k][0].x * sc[j], xi = st.x[k][0].y * sc[j];
+                    cmac_first(acc[k][j][0], acc[k][j][1], xr, xi, st.h[j][0], am, dc);
+                }
+                {
+                    const T xr = st.x[k][1].x * sc[j], xi = st.x[k][1].y * sc[j];
+                    cmac(acc[k][j][2], acc[k][j][3], xr, xi, st.h[j][1]);
+                }
+            }
+        };
+        if (pm[0] != pm[2]) {
+            // warm-up: the three blocks do not have the same partitions yet (pm[0] <= pm[1] <= pm[2])
+            for (int p = 1; p < pm[2]; p++) {
+                Stage st;
+                issue(st, p);
+#pragma unroll
+                for (int k = 0; k < NB; k++) if (p < pm[k]) consume_k(st, k);
+            }
+            continue;
+        }
+        auto consume = [&](const Stage &st) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) consume_k(st, k);
+        };
+        // the rotating three-stage pipeline of mac_xbar_kernel over p = 1 .. pm - 1
+        const int n = pm[2] - 1;
+        Stage s0, s1, s2;
+        if (n >= 1) issue(s0, 1);
+        if (n >= 2) issue(s1, 2);
+        if (n >= 3) issue(s2, 3);
+        int i = 0;
+        for (; i + 6 <= n; i += 3) {
+            consume(s0); issue(s0, i + 4);
+            consume(s1); issue(s1, i + 5);
+            consume(s2); issue(s2, i + 6);
+        }
+        for (; i + 3 <= n; i += 3) {
+            consume(s0); if (i + 3 < n) issue(s0, i + 4);
+            consume(s1); if (i + 4 < n) issue(s1, i + 5);
+            consume(s2); if (i + 5 < n) issue(s2, i + 6);
+        }
+        if (i < n) consume(s0);
+        if (i + 1 < n) consume(s1);
+    }
+    c2<T> *const Z[NB] = {Z1, Z2, Z3};
+    const size_t zoff = (size_t)group * OG * L + k0;
+#pragma unroll
+    for (int k = 0; k < NB; k++)
+#pragma unroll
+        for (int j = 0; j < OG; j++)
+            *reinterpret_cast<float4 *>(Z[k] + zoff + (size_t)j * L) =
+                make_float4(acc[k][j][0], acc[k][j][1], acc[k][j][2], acc[k][j][3]);
 }
 
 // K2 over TWO consecutive blocks in one pass over the coefficients (uniform crossbars only: every
@@ -2023,9 +2265,14 @@ coeff_long_kernel(const MacEntry<T> *__restrict__ entries, const StreamWhere *__
         const int tile = k / TB;
         const int tc = tile * n_chunks + w.chunk;
         const unsigned long long bid = (unsigned long long)((tc >> 3) * n_groups + w.group) * 8ull + (unsigned long long)(tc & 7);
-        c2<T> *dst = reinterpret_cast<c2<T> *>(const_cast<unsigned char *>(sl.base) + bid * sl.slice +
-                                               (unsigned long long)w.q * sl.entry_bytes +
-                                               ((unsigned long long)p * OG + (unsigned long long)j) * sl.chunk);
+        // where (q, p) starts inside the workgroup's slice: the split long stream (StreamLayout::head)
+        // keeps partition 0 of every entry in front
+        const unsigned long long hstep = (unsigned long long)OG * sl.chunk;
+        const unsigned long long at = sl.head == 0u ? (unsigned long long)w.q * sl.entry_bytes + (unsigned long long)p * hstep
+                                    : p == 0       ? (unsigned long long)w.q * hstep
+                                                   : sl.head + (unsigned long long)w.q * (sl.entry_bytes - hstep) + (unsigned long long)(p - 1) * hstep;
+        c2<T> *dst = reinterpret_cast<c2<T> *>(const_cast<unsigned char *>(sl.base) + bid * sl.slice + at +
+                                               (unsigned long long)j * sl.chunk);
         dst[k % TB] = mk<T>(x.x * inv, x.y * inv);
     };
     if (tid == 0) put(0, mk<T>(s[0].x + s[0].y, s[0].x - s[0].y));

@@ -407,6 +407,11 @@ int bfhip_engine_uses_diag_mac(const bfhip_engine *e);
    taps: f32 uniform crossbars at L = 8192 with >= 1 GiB of coefficients, BFHIP_LONG_WINDOW=0/1 to
    force); 2: the standard windows of 2 blocks.  < 0 on a NULL handle */
 int bfhip_engine_window_blocks(const bfhip_engine *e);
+/* 3: the long-window plan in force runs the look-ahead MAC -- a call reads one third of the tail
+   partitions (p >= 1) once for the next three blocks and partition 0 for its own (no shard, no
+   real-time mode, >= 1 GiB of coefficients, BFHIP_LOOKAHEAD=0/1 to force); 0: it does not.
+   < 0 on a NULL handle */
+int bfhip_engine_lookahead_blocks(const bfhip_engine *e);
 /* depth of the input spectrum rings (n_blocks, plus one spare slot when the block is pipelined) */
 int bfhip_engine_ring_depth(const bfhip_engine *e);
 
