@@ -15,6 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libbfhip.so")
 
 IN, OUT = 0, 1
+EQ_LINEAR, EQ_MINIMUM = 0, 1                       # include/bfhip_nupc.h: BFHIP_EQ_*
+EQ_MODES = {"linear": EQ_LINEAR, "minimum": EQ_MINIMUM}
 RT_SPIN, RT_NO_GRAPH, RT_COPY_ENGINE, RT_OVERLAP = 1, 2, 4, 8      # bfhip_engine_rt_begin flags
 COEFF_WATCH, COEFF_LAZY = 1, 2                                       # bfhip_engine_add_coeff_processed_blocks flags
 ST_NONFINITE, ST_SAFETY = 1, 2
@@ -201,6 +203,9 @@ def lib():
     L.bfhip_nupc_reserve_eq.argtypes = [vp, C.c_long]
     L.bfhip_nupc_render_eq_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp]
     L.bfhip_nupc_render_eq.argtypes = [vp, C.c_long, ci, dp, dp, dp, vp]
+    L.bfhip_nupc_reserve_eq_minimum.argtypes = [vp]
+    L.bfhip_nupc_render_eq_mode_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp, ci]
+    L.bfhip_nupc_render_eq_mode.argtypes = [vp, C.c_long, ci, dp, dp, dp, ci, vp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -712,19 +717,29 @@ class Nupc:
         """before finalize, after reserve_update: finalize then allocates what the renders need"""
         self._chk(lib().bfhip_nupc_reserve_eq(self.h, max_taps))
 
-    def render_eq_async(self, filt, coeff, taps, freq, mag, phase):
-        """render the curve (bands: normalised frequency 0 .. 0.5, linear magnitude, phase in radians)
-        into `taps` reals on the device and rewrite an idle set with them; returns at once"""
-        assert len(freq) == len(mag) == len(phase)
-        self._chk(lib().bfhip_nupc_render_eq_async(self.h, filt, coeff, taps, len(freq), _darr(list(freq)),
-                                                   _darr(list(mag)), _darr(list(phase))))
+    def reserve_eq_minimum(self):
+        """before finalize, after reserve_eq: finalize then also allocates what mode="minimum" needs"""
+        self._chk(lib().bfhip_nupc_reserve_eq_minimum(self.h))
 
-    def render_eq(self, taps, freq, mag, phase):
+    @staticmethod
+    def _eq_mode(mode):
+        return EQ_MODES[mode] if isinstance(mode, str) else int(mode)
+
+    def render_eq_async(self, filt, coeff, taps, freq, mag, phase, mode="linear"):
+        """render the curve (bands: normalised frequency 0 .. 0.5, linear magnitude, phase in radians)
+        into `taps` reals on the device and rewrite an idle set with them; returns at once.
+        mode: "linear" (the reference's render, R/2 frames of delay) or "minimum" (minimum phase, no
+        delay; needs reserve_eq_minimum and magnitudes > 0)"""
+        assert len(freq) == len(mag) == len(phase)
+        self._chk(lib().bfhip_nupc_render_eq_mode_async(self.h, filt, coeff, taps, len(freq), _darr(list(freq)),
+                                                        _darr(list(mag)), _darr(list(phase)), self._eq_mode(mode)))
+
+    def render_eq(self, taps, freq, mag, phase, mode="linear"):
         """the render alone, synchronous: a numpy array of `taps` reals"""
         assert len(freq) == len(mag) == len(phase)
         out = np.zeros(max(int(taps), 0), self.dt)
-        self._chk(lib().bfhip_nupc_render_eq(self.h, taps, len(freq), _darr(list(freq)), _darr(list(mag)),
-                                             _darr(list(phase)), _ptr(out)))
+        self._chk(lib().bfhip_nupc_render_eq_mode(self.h, taps, len(freq), _darr(list(freq)), _darr(list(mag)),
+                                                  _darr(list(phase)), self._eq_mode(mode), _ptr(out)))
         return out
 
     def set_output_gain(self, ch, gain):

@@ -24,7 +24,7 @@ DEVICE = ["kernels.h", "fft_lds.h", "fft_wave.h", "bigfft.h"] + PUBLIC
 UNITS = {
     "bfhip.hip": DEVICE + ["conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],
     "convolver_abi.hip": DEVICE + ["conv_shared.h"],
-    "nupc.hip": DEVICE + ["alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h", "eq_render.h"],
+    "nupc.hip": DEVICE + ["alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h", "eq_render.h", "eq_minphase.h"],
     "host_ops.cpp": ["host_fft.h", "conv_shared.h"] + PUBLIC,
 }
 

@@ -48,15 +48,21 @@ __device__ __forceinline__ double eq_ci(double a1, double a2, double f1, double 
     return (a1 - a2) * 0.5 * cos(M_PI * (f - f1) / (f2 - f1)) + (a1 + a2) * 0.5;
 }
 
-// X[n], 1 <= n < R/2
-template <typename T>
-__device__ __forceinline__ c2<T> eq_bin(const double *lb, int n_bands, int n, int R) {
-    const double f = (double)n / (double)R;                // exact: R is a power of two
+// the first band i with f <= freq[i + 1], 0 < f < 0.5
+__device__ __forceinline__ int eq_band(const double *lb, int n_bands, double f) {
     int lo = 0, hi = n_bands - 2;                          // f < 0.5 = freq[n_bands - 1]: there is one
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if (f <= lb[mid + 1]) hi = mid; else lo = mid + 1;
     }
+    return lo;
+}
+
+// X[n], 1 <= n < R/2
+template <typename T>
+__device__ __forceinline__ c2<T> eq_bin(const double *lb, int n_bands, int n, int R) {
+    const double f = (double)n / (double)R;                // exact: R is a power of two
+    const int lo = eq_band(lb, n_bands, f);
     const double f1 = lb[lo], f2 = lb[lo + 1];
     const double *mag = lb + kEqMaxBands, *phase = lb + 2 * kEqMaxBands;
     double m = eq_ci(mag[lo], mag[lo + 1], f1, f2, f) / (double)R;

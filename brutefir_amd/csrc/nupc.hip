@@ -36,6 +36,7 @@
 #include "alloc.h"
 #include "coeff_async.h"
 #include "dither_init.h"
+#include "eq_minphase.h"
 #include "eq_render.h"
 #include "kernels.h"
 #include "subdelay_filter.h"
@@ -614,6 +615,7 @@ struct bfhip_nupc {
     // the rewrite, on the loader stream; everything is allocated at finalize
     long eq_reserve = 0;                   // max_taps asked for before finalize, 0 = none
     EqRender eq;
+    EqMinphase eq_min;                     // bfhip_nupc_reserve_eq_minimum (eq_minphase.h)
     hipEvent_t ev_eq = nullptr;            // the render into eq.taps is done
     void *ring(int i) const { return i ? d_acc2 : d_acc; }
 };
@@ -700,6 +702,7 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     if (n->h_upd_bad) (void)hipHostFree(n->h_upd_bad);
     if (n->d_upd) (void)hipFree(n->d_upd);
     eq_render_free(n->eq);
+    eq_minphase_free(n->eq_min);
     if (n->ev_eq) (void)hipEventDestroy(n->ev_eq);
     if (n->ev_upd_load) (void)hipEventDestroy(n->ev_upd_load);
     if (n->ev_upd_main) (void)hipEventDestroy(n->ev_upd_main);
@@ -1011,6 +1014,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     }
     if (n->eq_reserve) {
         NCHK(eq_render_alloc(n->eq, n->rs, n->eq_reserve));
+        if (n->eq_min.reserved) NCHK(eq_minphase_alloc(n->eq_min, n->eq));
         NCHK(hipEventCreateWithFlags(&n->ev_eq, hipEventDisableTiming));
     }
     n->finalized = true;
@@ -1213,11 +1217,17 @@ int upd_poll(bfhip_nupc *n) {
 // enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
 // no allocation.  Host source: `taps` is the pinned staging buffer or is copied into it.  Device
 // source: the loader (and the main stream, for its own slices) waits on ready_event.
-// eq: the taps are rendered from this curve into eq.taps on the loader stream first, and ev_eq is
-// the ready event (the caller passes taps = eq.taps, on_device).
+// eq: the taps are rendered from this curve (in mode eq_mode) into eq.taps on the loader stream first,
+// and ev_eq is the ready event (the caller passes taps = eq.taps, on_device).
 int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event);
+static hipError_t eq_launch(const bfhip_nupc *n, const EqBands &b, long taps, int mode) {
+    if (mode == BFHIP_EQ_MINIMUM)
+        return n->rs == 4 ? eq_minphase_launch<float>(n->eq, n->eq_min, b, taps, n->upd_stream)
+                          : eq_minphase_launch<double>(n->eq, n->eq_min, b, taps, n->upd_stream);
+    return n->rs == 4 ? eq_render_launch<float>(n->eq, b, taps, n->upd_stream) : eq_render_launch<double>(n->eq, b, taps, n->upd_stream);
+}
 int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event,
-              const EqBands *eq = nullptr) {
+              const EqBands *eq = nullptr, int eq_mode = BFHIP_EQ_LINEAR) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (filter < 0 || filter >= (int)n->coeff.size() || coeff < 0 || coeff >= (int)n->coeff[filter].size() ||
         !taps || n_taps < 1 || n_taps > bfhip_nupc_taps(n))
@@ -1244,8 +1254,7 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
     NCHK(hipSetDevice(n->device));
     if (eq) {
         // a failure here has touched eq.taps only: the set is as it was
-        NCHK(n->rs == 4 ? eq_render_launch<float>(n->eq, *eq, n_taps, n->upd_stream)
-                        : eq_render_launch<double>(n->eq, *eq, n_taps, n->upd_stream));
+        NCHK(eq_launch(n, *eq, n_taps, eq_mode));
         NCHK(hipEventRecord(n->ev_eq, n->upd_stream));
         ready_event = n->ev_eq;
     }
@@ -1588,12 +1597,24 @@ int bfhip_nupc_reserve_eq(bfhip_nupc *n, long max_taps) {
     return BFHIP_OK;
 }
 
-// state and curve checks shared by the two render calls; fills the kernel-argument copy of the bands
+int bfhip_nupc_reserve_eq_minimum(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_minimum after finalize");
+    if (!n->eq_reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_minimum: needs bfhip_nupc_reserve_eq first");
+    n->eq_min.reserved = true;
+    return BFHIP_OK;
+}
+
+// state and curve checks shared by the render calls; fills the kernel-argument copy of the bands
 static int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
-                    const double phase[], EqBands *b) {
+                    const double phase[], int mode, EqBands *b) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (!n->finalized || !n->eq_reserve)
         return nfail(BFHIP_ESTATE, "nupc_render_eq: needs bfhip_nupc_reserve_eq before finalize, and finalize");
+    if (mode != BFHIP_EQ_LINEAR && mode != BFHIP_EQ_MINIMUM)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: mode must be BFHIP_EQ_LINEAR or BFHIP_EQ_MINIMUM");
+    if (mode == BFHIP_EQ_MINIMUM && !n->eq_min.reserved)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq: minimum phase needs bfhip_nupc_reserve_eq_minimum before finalize");
     if (taps < 8 || (taps & (taps - 1)) || taps > n->eq_reserve)
         return nfail(BFHIP_EINVAL, "nupc_render_eq: taps must be a power of two, 8 .. max_taps");
     if (!freq || !mag || !phase || n_bands < 2 || n_bands > kEqMaxBands)
@@ -1604,32 +1625,44 @@ static int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double fr
         if (i > 0 && !(freq[i] > freq[i - 1])) return nfail(BFHIP_EINVAL, "nupc_render_eq: band frequencies must ascend");
         if (!std::isfinite(mag[i]) || mag[i] < 0.0 || !std::isfinite(phase[i]))
             return nfail(BFHIP_EINVAL, "nupc_render_eq: magnitudes must be finite and >= 0, phases finite");
+        if (mode == BFHIP_EQ_MINIMUM && !(mag[i] > 0.0))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq: minimum phase needs every magnitude > 0");
         b->freq[i] = freq[i]; b->mag[i] = mag[i]; b->phase[i] = phase[i];
     }
     b->n = n_bands;
     return BFHIP_OK;
 }
 
-int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
-                               const double mag[], const double phase[]) {
+int bfhip_nupc_render_eq_mode_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
+                                    const double mag[], const double phase[], int mode) {
     EqBands b;
-    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, &b); if (r < 0) return r; }
-    return upd_start(n, filter, coeff, n->eq.taps, true, taps, nullptr, &b);
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.taps, true, taps, nullptr, &b, mode);
 }
 
-int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
-                         const double phase[], void *taps_out) {
+int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
+                               const double mag[], const double phase[]) {
+    return bfhip_nupc_render_eq_mode_async(n, filter, coeff, taps, n_bands, freq, mag, phase, BFHIP_EQ_LINEAR);
+}
+
+int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                              const double phase[], int mode, void *taps_out) {
     EqBands b;
-    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, &b); if (r < 0) return r; }
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
     if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq: null buffer");
     OWNER(n);
     { const int r = upd_poll(n); if (r < 0) return r; }
     if (n->upd_inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq: a rewrite is in flight (bfhip_nupc_update_busy)");
     NCHK(hipSetDevice(n->device));
-    NCHK(n->rs == 4 ? eq_render_launch<float>(n->eq, b, taps, n->upd_stream) : eq_render_launch<double>(n->eq, b, taps, n->upd_stream));
+    NCHK(eq_launch(n, b, taps, mode));
     NCHK(hipMemcpyAsync(taps_out, n->eq.taps, (size_t)taps * n->rs, hipMemcpyDeviceToHost, n->upd_stream));
     NCHK(hipStreamSynchronize(n->upd_stream));
     return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                         const double phase[], void *taps_out) {
+    return bfhip_nupc_render_eq_mode(n, taps, n_bands, freq, mag, phase, BFHIP_EQ_LINEAR, taps_out);
 }
 
 // blocks: not for the audio thread

@@ -198,6 +198,39 @@ int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, 
    offline use.  BFHIP_ESTATE while a rewrite is in flight (it shares the scratch). */
 int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[],
                          const double mag[], const double phase[], void *taps_out);
+/* ---- minimum-phase render (an extension: bflogic_eq has no such mode) --------------------------
+ * The linear render above carries (-1)^n: a flat curve of R taps is a unit pulse at tap R/2, and
+ * every curve rendered with it adds R/2 frames of delay.  BFHIP_EQ_MINIMUM renders the same
+ * magnitude curve with minimum phase (the homomorphic method): the energy sits at the first taps and
+ * the equaliser adds no delay.  With R = taps, ci and the band search as above, n = 0 .. R/2:
+ *     M[0] = mag[0],  M[R/2] = mag[n_bands-1],  M[n] = ci(mag[i], mag[i+1], freq[i], freq[i+1], n/R)
+ *     phi[0] = phi[R/2] = 0,                    phi[n] = ci(phase[i], ...)        (1 <= n < R/2)
+ *     c    = irfft(log M, R)                    the real cepstrum, R values (normalised inverse)
+ *     c^[0] = c[0], c^[t] = 2 c[t] (1 <= t < R/2), c^[R/2] = c[R/2], c^[t] = 0 (t > R/2)
+ *     S[k] = sum_t c^[t] exp(-2 pi i k t / R)
+ *     X[k] = M[k] / R  (cos(Im S[k] + phi[k]) + i sin(Im S[k] + phi[k])),  X[0] and X[R/2] real
+ *     taps = the unnormalised HC2R of X, as above; there is no (-1)^n term
+ * (Re S[k] = log M[k] in exact arithmetic: the magnitude is taken from M[k] itself.)  phase[] is
+ * excess phase on top of the minimum phase; all zeros give the minimum-phase response.  Curve, log,
+ * sine and cosine are float64 for both precisions, the three transforms run in the convolver's real
+ * type.  A render is a pure function of its arguments. */
+#define BFHIP_EQ_LINEAR  0
+#define BFHIP_EQ_MINIMUM 1
+/* before finalize, after bfhip_nupc_reserve_eq (BFHIP_ESTATE otherwise / after finalize).  What the
+   minimum-phase render needs beyond the linear one (one more buffer of max_taps reals when
+   max_taps > 16384) is allocated at finalize.  A convolver that never calls this allocates nothing
+   more and behaves as before. */
+int bfhip_nupc_reserve_eq_minimum(bfhip_nupc *n);
+/* bfhip_nupc_render_eq_async / bfhip_nupc_render_eq with a mode.  BFHIP_EQ_LINEAR gives the bytes of
+   those calls and needs bfhip_nupc_reserve_eq only.  BFHIP_EQ_MINIMUM needs
+   bfhip_nupc_reserve_eq_minimum (BFHIP_ESTATE without it) and every mag finite and > 0.  Any other
+   mode, or a magnitude <= 0 in minimum mode: BFHIP_EINVAL and nothing changes.  All other argument
+   and state rules, and the "no host wait, no allocation, no blocking copy" contract of the
+   asynchronous call, are those of the two calls above. */
+int bfhip_nupc_render_eq_mode_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands,
+                                    const double freq[], const double mag[], const double phase[], int mode);
+int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const double freq[],
+                              const double mag[], const double phase[], int mode, void *taps_out);
 /* per-output gain applied at the emit step, in force from the first frame of the next block call's
    output (a step, or the start of a ramp: bfhip_nupc_set_gain_ramp below); 0.0 mutes; default 1.0
    (multiplied into the 1/scale factor in float64: exact) */

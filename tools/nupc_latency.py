@@ -9,7 +9,8 @@ bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, ne
 uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
-                                  [--gain-ramp] [--rewrite | --rewrite-sync | --eq] [--dump-output FILE]
+                                  [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum]]
+                                  [--dump-output FILE]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
@@ -23,8 +24,10 @@ the host duration of each rewrite call, the periods from call to busy == 0, and 
 periods with a rewrite in flight and without.  --eq is --rewrite with the taps rendered on the device:
 every 300 periods a new random equaliser curve (130 bands, +-12 dB) is rendered at 1 048 576 taps into
 the idle set of each filter (bfhip_nupc_render_eq_async), then switched to; it also reports the wall time
-of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wait) of 8 and of 1 048 576
-taps, made before the timed loop: an upper bound of the render's device time.  --gain-ramp sets an
+of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wait) of 8, of 16 384 and of
+1 048 576 taps, made before the timed loop: an upper bound of the render's device time.  --eq-mode minimum
+renders every curve with minimum phase (BFHIP_EQ_MINIMUM: no taps / 2 frames of delay; three transforms
+instead of one).  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
@@ -54,6 +57,7 @@ def main():
     ap.add_argument("--rewrite", action="store_true")
     ap.add_argument("--rewrite-sync", action="store_true")
     ap.add_argument("--eq", action="store_true")
+    ap.add_argument("--eq-mode", choices=["linear", "minimum"], default="linear")
     ap.add_argument("--dump-output")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
@@ -79,12 +83,14 @@ def main():
         for io in (bf.IN, bf.OUT):
             for c in range(2):
                 nu.set_subdelay(io, c, 37 - 62 * c)
-    assert a.rewrite + a.rewrite_sync + a.eq <= 1
+    assert a.rewrite + a.rewrite_sync + a.eq <= 1 and (a.eq or a.eq_mode == "linear")
     rewriting = a.rewrite or a.rewrite_sync or a.eq
     if a.rewrite or a.eq:
         nu.reserve_update()
     if a.eq:
         nu.reserve_eq(1048576)
+        if a.eq_mode == "minimum":
+            nu.reserve_eq_minimum()
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -106,10 +112,10 @@ def main():
         # a synchronous render of 8 taps is the call, the wait and a copy of 64 bytes; one of 1 048 576
         # taps adds the long render and 8 MB of copy to pageable memory
         c = curve()
-        for n_taps in (8, 1048576):
+        for n_taps in (8, 16384, 1048576):
             for _ in range(5):
                 t0 = time.perf_counter()
-                nu.render_eq(n_taps, *c)
+                nu.render_eq(n_taps, *c, mode=a.eq_mode)
                 render_ms.append((n_taps, (time.perf_counter() - t0) * 1e3))
     live_set, todo, round_no, due = 0, [], 0, False
     call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
@@ -160,7 +166,7 @@ def main():
                 if a.eq:
                     c = curve()
                     t0 = time.perf_counter()
-                    nu.render_eq_async(f, 1 - live_set, 1048576, *c)
+                    nu.render_eq_async(f, 1 - live_set, 1048576, *c, mode=a.eq_mode)
                     call_ms.append((time.perf_counter() - t0) * 1e3)
                     started_at = s
                 elif a.rewrite:
@@ -215,12 +221,12 @@ def main():
         "gain_ramp": {"ramp_frames": ramp_periods * L0, "outputs": [0, 1], "new_target_every_periods": 300,
                       "ramps": n_ramps, "step_ms_ramp_in_progress": dist(ts[rp]),
                       "step_ms_no_ramp": dist(ts[~rp])} if a.gain_ramp else None,
-        "rewrite": {"mode": "eq" if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+        "rewrite": {"mode": ("eq" if a.eq_mode == "linear" else "eq-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
                     "taps_per_set": int(nu.taps), "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
                     "periods_to_idle": dist(busy_periods),
                     "render_eq_sync_ms": {str(k): dist([v for n_taps, v in render_ms if n_taps == k][1:])
-                                          for k in (8, 1048576)} if a.eq else None,
+                                          for k in (8, 16384, 1048576)} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
