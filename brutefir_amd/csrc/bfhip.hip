@@ -785,17 +785,23 @@ void launch_io(bfhip_engine *e, const void *z, int first, int count, uint8_t *ra
     *err = hipGetLastError();
 }
 
+// the grid mac_decode (kernels.h) takes apart: n_tc (tile, chunk) pairs rounded up to the 8 XCDs, times the groups
+int mac_grid(int n_tc, int n_groups) { return ((n_tc + 7) / 8) * n_groups * 8; }
+// blocks the rings will hold of the block `ahead` after this one, itself included (procblocks, bfrun.c:1745)
+int block_age(const bfhip_engine *e, int ahead = 0) {
+    return (int)std::min<unsigned long long>(e->blocks_done + 1 + (unsigned long long)ahead, (unsigned long long)e->N);
+}
+
 template <typename T>
 void launch_mac(bfhip_engine *e, void *Zp, hipError_t *err) {
     const int n_tc = e->n_tiles * e->n_chunks;
-    const int tc8 = (n_tc + 7) / 8;
-    const int grid = tc8 * e->n_groups * 8;
-    const unsigned long long age64 = std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
+    const int grid = mac_grid(n_tc, e->n_groups);
+    const int age = block_age(e);
 #define BFHIP_LAUNCH_MAC(NTFLAG, U)                                                                   \
     hipLaunchKernelGGL((mac_xbar_kernel<T, NTFLAG, U>), dim3(grid), dim3(e->mac_threads), 0, e->ls,      \
                        (const MacEntry<T> *)e->d_entries, (const ChunkRange *)e->d_chunks,               \
                        (c2<T> *)Zp, e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc,               \
-                       e->blockcounter, (int)age64, (const BlockState *)e->bs_arg,                       \
+                       e->blockcounter, age, (const BlockState *)e->bs_arg,                              \
                        (NTFLAG && U == 0) ? e->hstream : StreamLayout{nullptr, 0, 0, 0})
     if (e->mac_diag) {
         const int n_jobs = e->n_chunks * e->n_out_padded;
@@ -813,7 +819,7 @@ void launch_mac(bfhip_engine *e, void *Zp, hipError_t *err) {
 #define BFHIP_LAUNCH_DIAG(NTFLAG, TL)                                                                                  \
         hipLaunchKernelGGL((mac_diag_kernel<T, NTFLAG, TL>), dim3(n_jobs * tsplit), dim3(256), 0, e->ls,               \
                            (const MacEntry<T> *)e->d_entries, e->d_diag_jobs, (c2<T> *)Zp, e->L, e->n_out_padded,      \
-                           e->blockcounter, (int)age64, (const BlockState *)e->bs_arg, tsplit)
+                           e->blockcounter, age, (const BlockState *)e->bs_arg, tsplit)
 #define BFHIP_DIAG_TILES(NTFLAG)                                              \
         switch (tiles) {                                                      \
         case 1: BFHIP_LAUNCH_DIAG(NTFLAG, 1); break;                          \
@@ -843,8 +849,7 @@ template <typename T>
 void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
     const int n_tc = e->n_tiles * e->n_chunks;
     e->zp_is_sum = false;
-    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
-    hipLaunchKernelGGL((mac_xbar2_kernel<T, true>), dim3(grid), dim3(e->mac_threads), 0, e->ls,
+    hipLaunchKernelGGL((mac_xbar2_kernel<T, true>), dim3(mac_grid(n_tc, e->n_groups)), dim3(e->mac_threads), 0, e->ls,
                        (const MacEntry<T> *)e->d_entries, (const ChunkRange *)e->d_chunks, (c2<T> *)Zp0, (c2<T> *)Zp1,
                        e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc, e->blockcounter, e->hstream);
     *err = hipGetLastError();
@@ -853,11 +858,9 @@ void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
 // the long-window MAC (kernels.h): the crossbar kernel over the long entries, ring step 3
 void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
     const int n_tc = e->lw_tiles * e->lw_chunks;
-    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
-    const unsigned long long age64 = std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
-    hipLaunchKernelGGL((mac_xbar_kernel<float, true, 0, 3>), dim3(grid), dim3(256), 0, e->ls,
+    hipLaunchKernelGGL((mac_xbar_kernel<float, true, 0, 3>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,
                        (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,
-                       2 * e->L, e->n_out_padded, e->n_groups, e->lw_chunks, n_tc, e->blockcounter, (int)age64,
+                       2 * e->L, e->n_out_padded, e->n_groups, e->lw_chunks, n_tc, e->blockcounter, block_age(e),
                        (const BlockState *)e->bs_arg, e->lstream);
     *err = hipGetLastError();
 }
@@ -869,27 +872,23 @@ c2<float> *la_buffer(bfhip_engine *e, unsigned long long block, int slice) {
 }
 void launch_mac_la_head(bfhip_engine *e, void *Zp, hipError_t *err) {
     const int n_tc = e->lw_tiles;
-    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
     const unsigned long long T = e->blocks_done;
-    const unsigned long long age64 = std::min<unsigned long long>(T + 1, (unsigned long long)e->N);
-    hipLaunchKernelGGL(mac_la_head_kernel<float>, dim3(grid), dim3(256), 0, e->ls,
+    hipLaunchKernelGGL(mac_la_head_kernel<float>, dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,
                        (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,
                        (const c2<float> *)la_buffer(e, T, 0), (const c2<float> *)la_buffer(e, T, 1),
-                       (const c2<float> *)la_buffer(e, T, 2), 2 * e->L, e->n_groups, n_tc, e->blockcounter, (int)age64,
+                       (const c2<float> *)la_buffer(e, T, 2), 2 * e->L, e->n_groups, n_tc, e->blockcounter, block_age(e),
                        e->lstream);
     *err = hipGetLastError();
 }
 void launch_mac_la_tail(bfhip_engine *e, hipError_t *err) {
     const int n_tc = e->lw_tiles;
-    const int grid = ((n_tc + 7) / 8) * e->n_groups * 8;
     const unsigned long long T = e->blocks_done;
     const int slice = (int)(T % 3ull);
-    int age[3];
-    for (int k = 1; k <= 3; k++) age[k - 1] = (int)std::min<unsigned long long>(T + 1 + k, (unsigned long long)e->N);
-    hipLaunchKernelGGL(mac_la_tail_kernel<float>, dim3(grid), dim3(256), 0, e->ls,
+    hipLaunchKernelGGL(mac_la_tail_kernel<float>, dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,
                        (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks,
                        la_buffer(e, T + 1, slice), la_buffer(e, T + 2, slice), la_buffer(e, T + 3, slice),
-                       2 * e->L, e->n_groups, n_tc, e->blockcounter, age[0], age[1], age[2], slice, e->lstream);
+                       2 * e->L, e->n_groups, n_tc, e->blockcounter, block_age(e, 1), block_age(e, 2), block_age(e, 3), slice,
+                       e->lstream);
     *err = hipGetLastError();
     if (*err != hipSuccess) return;
     for (int k = 1; k <= 3; k++) {
@@ -960,7 +959,7 @@ void launch_levels(bfhip_engine *e, hipError_t *err) {
     const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
     auto kf = ring_fill_kernel<T, LOG2L>;
     auto kx = crossfade_kernel<T, LOG2L>;
-    const unsigned long long age64 = std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
+    const int age = block_age(e);
     const unsigned char *base = (const unsigned char *)e->d_jobs;
     const int V = 16 / (int)sizeof(c2<T>);
     const int threads = e->mac_threads;
@@ -975,7 +974,7 @@ void launch_levels(bfhip_engine *e, hipError_t *err) {
         }
         if (lj.n_filt > 0) {
             hipLaunchKernelGGL(mac_filter_kernel<T>, dim3(tiles, lj.n_filt), dim3(threads), 0, e->ls,
-                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, (int)age64,
+                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, age,
                                (const BlockState *)e->bs_arg);
         }
         if (lj.n_fade > 0) {
@@ -1065,7 +1064,7 @@ void launch_ifft_out_big(bfhip_engine *e, const void *Zp, size_t chunk_stride, i
 
 template <typename T>
 void launch_levels_big(bfhip_engine *e, hipError_t *err) {
-    const unsigned long long age64 = std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
+    const int age = block_age(e);
     const unsigned char *base = (const unsigned char *)e->d_jobs;
     const int V = 16 / (int)sizeof(c2<T>);
     const int threads = e->mac_threads;
@@ -1088,7 +1087,7 @@ void launch_levels_big(bfhip_engine *e, hipError_t *err) {
         }
         if (lj.n_filt > 0) {
             hipLaunchKernelGGL(mac_filter_kernel<T>, dim3(tiles, lj.n_filt), dim3(threads), 0, e->ls,
-                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, (int)age64,
+                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, age,
                                (const BlockState *)e->bs_arg);
         }
         if (lj.n_fade > 0) {
@@ -4039,7 +4038,7 @@ int bfhip_engine_rt_submit(bfhip_engine *e, const void *rawin) {
         // blocks went through the other entry points (or this is the first period)
         BlockState bs;
         bs.t = e->blockcounter;
-        bs.age = (int)std::min<unsigned long long>(e->blocks_done + 1, (unsigned long long)e->N);
+        bs.age = block_age(e);
         bs.n_blocks = 0; bs.pad = 0;
         bs.wrap_at = e->wrap_at; bs.wrap_by = e->wrap_by;
         HIPCHK(hipMemcpyAsync(e->d_bs, &bs, sizeof(bs), hipMemcpyHostToDevice, e->stream));

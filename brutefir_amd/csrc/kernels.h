@@ -82,8 +82,8 @@ struct StreamLayout {
     unsigned int chunk;             // bytes of one tile of one set: blockDim.x * 16
     // The long-window stream (ring step 3) keeps partition 0 of all of a workgroup's entries in front of
     // the others: head region [q][j] (`head` = entries * OG * chunk bytes), then [q][p >= 1][j].  The
-    // look-ahead passes (mac_la_kernel) then read one sequential range each: the head pass the head
-    // region, the tail pass of a slice (a contiguous range of entries) its part of the rest.  0: as above.
+    // look-ahead passes then read one sequential range each: mac_la_head_kernel the head region,
+    // mac_la_tail_kernel of a slice (a contiguous range of entries) its part of the rest.  0: as above.
     unsigned int head;
 };
 
@@ -605,6 +605,28 @@ __global__ void reorder_kernel(const T *__restrict__ q, c2<T> *__restrict__ pack
     }
 }
 
+// The MAC grid (mac_xbar_kernel, mac_xbar2_kernel, the look-ahead passes): workgroup
+// bid = ((tc / 8) * n_groups + group) * 8 + tc % 8 with tc = tile * n_chunks + chunk, so that the output
+// groups that need the same ring tile get the same bid % 8 (one XCD, adjacent dispatch) and the ring
+// re-reads hit that XCD's L2.  mac_grid() on the host (bfhip.hip) is the matching grid size.
+// A kernel returns when tc >= n_tc (the grid is rounded up to 8 tiles) before it asks for more, and
+// when k0 >= L (the last tile may reach past the spectrum).
+struct MacTile {
+    int group, tc, n_chunks;
+    __device__ __forceinline__ int tile() const { return tc / n_chunks; }
+    __device__ __forceinline__ int chunk() const { return tc % n_chunks; }
+    // first of the V bins of this lane, for workgroups of `threads` lanes
+    template <int V> __device__ __forceinline__ int k0(int threads) const { return (tile() * threads + (int)threadIdx.x) * V; }
+};
+__device__ __forceinline__ MacTile mac_decode(int bid, int n_groups, int n_chunks) {
+    const int xcd = bid & 7, local = bid >> 3;
+    return MacTile{local % n_groups, (local / n_groups) * 8 + xcd, n_chunks};
+}
+__device__ __forceinline__ unsigned long long mac_encode(int group, int tile, int chunk, int n_groups, int n_chunks) {
+    const int tc = tile * n_chunks + chunk;
+    return (unsigned long long)((tc >> 3) * n_groups + group) * 8ull + (unsigned long long)(tc & 7);
+}
+
 // set-major coefficient partitions -> the stream-ordered copy (StreamLayout).  One workgroup per
 // (partition, tile, entry); where[] names the chunk slot of every entry: (group, chunk, q).
 struct StreamWhere { int group, chunk, q, pad; };
@@ -617,9 +639,7 @@ stream_relayout_kernel(const MacEntry<T> *__restrict__ entries, const StreamWher
     const int p = p_first + (int)blockIdx.x, tile = blockIdx.y;
     const int e = which ? which[blockIdx.z] : (int)blockIdx.z;
     const StreamWhere w = where[e];
-    // the MAC's own block decode, inverted: tc = tile * n_chunks + chunk, xcd = tc & 7
-    const int tc = tile * n_chunks + w.chunk;
-    const unsigned long long bid = (unsigned long long)((tc >> 3) * n_groups + w.group) * 8ull + (unsigned long long)(tc & 7);
+    const unsigned long long bid = mac_encode(w.group, tile, w.chunk, n_groups, n_chunks);
     const int P = (int)(sl.entry_bytes / ((unsigned int)OG * sl.chunk));
     if (p >= P) return;
     unsigned char *dst = const_cast<unsigned char *>(sl.base) + bid * sl.slice + (unsigned int)w.q * sl.entry_bytes +
@@ -657,7 +677,77 @@ __device__ __forceinline__ void cmac(T &re, T &im, T xr, T xi, c2<T> h) {
     im = fma_t(xr, h.y, im);
     im = fma_t(xi, h.x, im);
 }
+// one lane's product: acc[0 .. 2V) += (sc * x[v]) * h[v] over the lane's V bins, the first one by cmac_first
+template <typename T, int V>
+__device__ __forceinline__ void cmac_lane(T *acc, const c2<T> *x, T sc, const c2<T> *h, T am, bool dc) {
+    {
+        const T xr = x[0].x * sc, xi = x[0].y * sc;
+        cmac_first(acc[0], acc[1], xr, xi, h[0], am, dc);
+    }
+    if constexpr (V == 2) {
+        const T xr = x[1].x * sc, xi = x[1].y * sc;
+        cmac(acc[2], acc[3], xr, xi, h[1]);
+    }
+}
+// one workgroup's accumulators, acc[OG][2 * V]: cleared, and stored to rows zp[j * L] of 16 bytes per lane
+template <typename T, int V>
+__device__ __forceinline__ void acc_zero(T (*acc)[2 * V]) {
+#pragma unroll
+    for (int j = 0; j < OG; j++)
+#pragma unroll
+        for (int v = 0; v < 2 * V; v++) acc[j][v] = (T)0;
+}
+template <typename T, int V>
+__device__ __forceinline__ void acc_store(c2<T> *zp, int L, const T (*acc)[2 * V]) {
+#pragma unroll
+    for (int j = 0; j < OG; j++) {
+        if constexpr (V == 2) {
+            *reinterpret_cast<float4 *>(zp + (size_t)j * L) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+        } else {
+            zp[(size_t)j * L] = mk<T>(acc[j][0], acc[j][1]);
+        }
+    }
+}
 
+// Ring slot of the window that partition p of block t multiplies: block t - PSTEP * p - delay, and for
+// the last partition of a long entry (PSTEP 3) the window that ends `shift` blocks later.
+template <int PSTEP>
+__device__ __forceinline__ unsigned int ring_slot(unsigned int t, int p, int lastP, int shift, int delay, int R) {
+    return (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
+}
+// Byte offset of bin k0 of spectrum `row` in an array of [.][L] spectra.  Kept in 32 bits (N * L * 16 < 4 GiB)
+// so that the loads take the scalar-base + 32-bit lane-offset form.
+template <typename T>
+__device__ __forceinline__ unsigned int spec_off(unsigned int row, int L, int k0) {
+    return (row * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+}
+
+// Rotating three-stage load pipeline over items first .. first + n - 1: while one item's products are
+// accumulated the loads of the next two are in flight and the one after is being issued -- the memory
+// pipe never drains.  issue(Stage &, item) starts an item's loads, consume(const Stage &) uses them.
+// A macro, expanded in place, because as a function template taking the two lambdas (by value, by
+// reference, always_inline) it costs the pipelined kernels 6 to 49 VGPRs and mac_xbar2_kernel<double> a spill.
+#define MAC_PIPELINE3(Stage, first, n, issue, consume)                                  \
+    do {                                                                                \
+        const int f_ = (first), n_ = (n);                                               \
+        Stage s0, s1, s2;                                                               \
+        if (n_ >= 1) issue(s0, f_);                                                     \
+        if (n_ >= 2) issue(s1, f_ + 1);                                                 \
+        if (n_ >= 3) issue(s2, f_ + 2);                                                 \
+        int i = 0;                                                                      \
+        for (; i + 6 <= n_; i += 3) {                /* steady state: no conditions */  \
+            consume(s0); issue(s0, f_ + i + 3);                                         \
+            consume(s1); issue(s1, f_ + i + 4);                                         \
+            consume(s2); issue(s2, f_ + i + 5);                                         \
+        }                                                                               \
+        for (; i + 3 <= n_; i += 3) {                /* at most two trips */            \
+            consume(s0); if (i + 3 < n_) issue(s0, f_ + i + 3);                         \
+            consume(s1); if (i + 4 < n_) issue(s1, f_ + i + 4);                         \
+            consume(s2); if (i + 5 < n_) issue(s2, f_ + i + 5);                         \
+        }                                                                               \
+        if (i < n_) consume(s0);                                                        \
+        if (i + 1 < n_) consume(s1);                                                    \
+    } while (0)
 
 // Z[o][k] (+)= sum over entries (ring, delay) and partitions p of
 //              scale * ring[(t - p - delay) mod R][k] * H[p][k]
@@ -675,23 +765,16 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
                 int n_tc, unsigned int t, int age, const BlockState *__restrict__ bs, StreamLayout sl) {
     constexpr int V = 16 / sizeof(c2<T>);          // bins per lane: 2 (f32) / 1 (f64)
     if (bs) { t = bs->t; age = bs->age; }
-    // XCD-aware decode (blocks b and b+8 share an XCD)
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int group = local % n_groups;
-    const int tc = (local / n_groups) * 8 + xcd;
-    if (tc >= n_tc) return;
-    const int tile = tc / n_chunks, chunk = tc % n_chunks;
-    const int k0 = (tile * (int)blockDim.x + (int)threadIdx.x) * V;
+    const MacTile m = mac_decode(bid, n_groups, n_chunks);
+    if (m.tc >= n_tc) return;
+    const int group = m.group, chunk = m.chunk(), k0 = m.template k0<V>((int)blockDim.x);
     if (k0 >= L) return;
     const bool dc = (k0 == 0);
     const T am = dc ? (T)0 : (T)1;
 
     T acc[OG][2 * V];
-#pragma unroll
-    for (int j = 0; j < OG; j++)
-#pragma unroll
-        for (int v = 0; v < 2 * V; v++) acc[j][v] = (T)0;
+    acc_zero<T, V>(acc);
 
     const ChunkRange cr = chunks[group * n_chunks + chunk];
     for (int e = cr.begin; e < cr.end; e++) {
@@ -713,6 +796,8 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
         // powersave (bfrun.c:1541-1553, 1694-1770): every block this input still has in its ring
         // is silence -> nothing to add, nothing to read
         if (E->live != nullptr && *E->live == 0) continue;
+        // where this lane reads the ring for partition p
+        auto xoff_at = [&](int p) { return spec_off<T>(ring_slot<PSTEP>(t, p, lastP, shift, delay, R), L, k0); };
         if (E->dense == 1 || E->dense == 16) {
             const unsigned int mask = E->dense == 1 ? 0xffu : (unsigned int)E->mask;
             // The crossbar case: OG coefficient terms of equal length (or, for the last group of
@@ -745,100 +830,48 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
 #pragma unroll
                 for (int j = 0; j < OG; j++) Hs[j] = (const c2<T> *)(wg + (unsigned int)j * sl.chunk);
             }
+            auto hoff_at = [&](int p) {                     // set-major: (p * L + k0) * sizeof
+                return (PSTEP == 1 ? (unsigned int)p * hstep : (p == 0 ? hb0 : hbT + (unsigned int)p * hstep)) + hlane;
+            };
             if (mask != 0xffu) {
 #pragma unroll 2
                 for (int p = p0; p < maxP; p++) {
-                    const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
-                    const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                    const unsigned int hoff = (PSTEP == 1 ? (unsigned int)p * hstep : (p == 0 ? hb0 : hbT + (unsigned int)p * hstep)) + hlane;     // set-major: (p * L + k0) * sizeof
+                    const unsigned int xoff = xoff_at(p), hoff = hoff_at(p);
                     c2<T> x[V], h[OG][V];
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), x);
 #pragma unroll
                     for (int j = 0; j < OG; j++)
                         if (mask & (1u << j)) Load16<T, NT>::get((const c2<T> *)((const char *)Hs[j] + hoff), h[j]);
 #pragma unroll
-                    for (int j = 0; j < OG; j++) {
-                        if (!(mask & (1u << j))) continue;
-                        {
-                            const T xr = x[0].x * sc[j], xi = x[0].y * sc[j];
-                            cmac_first(acc[j][0], acc[j][1], xr, xi, h[j][0], am, dc);
-                        }
-                        if constexpr (V == 2) {
-                            const T xr = x[1].x * sc[j], xi = x[1].y * sc[j];
-                            cmac(acc[j][2], acc[j][3], xr, xi, h[j][1]);
-                        }
-                    }
+                    for (int j = 0; j < OG; j++)
+                        if (mask & (1u << j)) cmac_lane<T, V>(acc[j], x, sc[j], h[j], am, dc);
                 }
                 continue;
             }
             if constexpr (UNROLL == 0) {
-                // Rotating three-stage pipeline: while one partition's products are accumulated
-                // the loads of the next two are in flight and the one after is being issued --
-                // the memory pipe never drains inside an entry.
                 struct Stage { c2<T> x[V]; c2<T> h[OG][V]; };
                 auto issue = [&](Stage &st, int p) {
-                    const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
-                    const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                    const unsigned int hoff = (PSTEP == 1 ? (unsigned int)p * hstep : (p == 0 ? hb0 : hbT + (unsigned int)p * hstep)) + hlane;
+                    const unsigned int xoff = xoff_at(p), hoff = hoff_at(p);
                     Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), st.x);
 #pragma unroll
                     for (int j = 0; j < OG; j++) Load16<T, NT>::get((const c2<T> *)((const char *)Hs[j] + hoff), st.h[j]);
                 };
                 auto consume = [&](const Stage &st) {
 #pragma unroll
-                    for (int j = 0; j < OG; j++) {
-                        {
-                            const T xr = st.x[0].x * sc[j], xi = st.x[0].y * sc[j];
-                            cmac_first(acc[j][0], acc[j][1], xr, xi, st.h[j][0], am, dc);
-                        }
-                        if constexpr (V == 2) {
-                            const T xr = st.x[1].x * sc[j], xi = st.x[1].y * sc[j];
-                            cmac(acc[j][2], acc[j][3], xr, xi, st.h[j][1]);
-                        }
-                    }
+                    for (int j = 0; j < OG; j++) cmac_lane<T, V>(acc[j], st.x, sc[j], st.h[j], am, dc);
                 };
-                const int n = maxP - p0;
-                Stage s0, s1, s2;
-                if (n >= 1) issue(s0, p0);
-                if (n >= 2) issue(s1, p0 + 1);
-                if (n >= 3) issue(s2, p0 + 2);
-                int i = 0;
-                for (; i + 6 <= n; i += 3) {                 // steady state: no conditions
-                    consume(s0); issue(s0, p0 + i + 3);
-                    consume(s1); issue(s1, p0 + i + 4);
-                    consume(s2); issue(s2, p0 + i + 5);
-                }
-                for (; i + 3 <= n; i += 3) {                 // at most two trips
-                    consume(s0); if (i + 3 < n) issue(s0, p0 + i + 3);
-                    consume(s1); if (i + 4 < n) issue(s1, p0 + i + 4);
-                    consume(s2); if (i + 5 < n) issue(s2, p0 + i + 5);
-                }
-                if (i < n) consume(s0);
-                if (i + 1 < n) consume(s1);
+                MAC_PIPELINE3(Stage, p0, maxP - p0, issue, consume);
                 continue;
             }
 #pragma unroll UR
             for (int p = p0; p < maxP; p++) {
-                // byte offsets kept in 32 bits (N * L * 16 < 4 GiB) so that the loads take the
-                // scalar-base + 32-bit lane-offset form
-                const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
-                const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                const unsigned int hoff = ((unsigned int)p * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+                const unsigned int xoff = xoff_at(p), hoff = spec_off<T>((unsigned int)p, L, k0);
                 c2<T> x[V], h[OG][V];
                 Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), x);
 #pragma unroll
                 for (int j = 0; j < OG; j++) Load16<T, NT>::get((const c2<T> *)((const char *)Hs[j] + hoff), h[j]);
 #pragma unroll
-                for (int j = 0; j < OG; j++) {
-                    {
-                        const T xr = x[0].x * sc[j], xi = x[0].y * sc[j];
-                        cmac_first(acc[j][0], acc[j][1], xr, xi, h[j][0], am, dc);
-                    }
-                    if constexpr (V == 2) {
-                        const T xr = x[1].x * sc[j], xi = x[1].y * sc[j];
-                        cmac(acc[j][2], acc[j][3], xr, xi, h[j][1]);
-                    }
-                }
+                for (int j = 0; j < OG; j++) cmac_lane<T, V>(acc[j], x, sc[j], h[j], am, dc);
             }
             continue;
         }
@@ -854,20 +887,11 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             for (int v = 0; v < 2 * V; v++) ta[v] = (T)0;
 #pragma unroll 4
             for (int p = p0; p < maxP; p++) {
-                const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
-                const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                const unsigned int hoff = ((unsigned int)p * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+                const unsigned int xoff = xoff_at(p), hoff = spec_off<T>((unsigned int)p, L, k0);
                 c2<T> x[V], h[V];
                 Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), x);
                 Load16<T, false>::get((const c2<T> *)((const char *)H + hoff), h);
-                {
-                    const T xr = x[0].x * sc, xi = x[0].y * sc;
-                    cmac_first(ta[0], ta[1], xr, xi, h[0], am, dc);
-                }
-                if constexpr (V == 2) {
-                    const T xr = x[1].x * sc, xi = x[1].y * sc;
-                    cmac(ta[2], ta[3], xr, xi, h[1]);
-                }
+                cmac_lane<T, V>(ta, x, sc, h, am, dc);
             }
 #pragma unroll
             for (int j = 0; j < OG; j++)
@@ -878,7 +902,7 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
             continue;
         }
         for (int p = p0; p < maxP; p++) {
-            const unsigned int slot = (t - (unsigned int)(PSTEP * p - (PSTEP != 1 && p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
+            const unsigned int slot = ring_slot<PSTEP>(t, p, lastP, shift, delay, R);
             c2<T> x[V];
             {
                 const c2<T> *xp = ring + (size_t)slot * L + k0;
@@ -917,28 +941,12 @@ mac_xbar_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__res
                 }
                 // first bin of the lane: element 0 of the spectrum is (DC, Nyquist), a
                 // real*real product per component (fftw_convfuns.h:545-559)
-                {
-                    const T xr = x[0].x * sc, xi = x[0].y * sc;
-                    cmac_first(acc[j][0], acc[j][1], xr, xi, h[0], am, dc);
-                }
-                if constexpr (V == 2) {
-                    const T xr = x[1].x * sc, xi = x[1].y * sc;
-                    cmac(acc[j][2], acc[j][3], xr, xi, h[1]);
-                }
+                cmac_lane<T, V>(acc[j], x, sc, h, am, dc);
             }
         }
     }
-    c2<T> *zp = Zp + ((size_t)chunk * n_out_padded + (size_t)group * OG) * L + k0;
-#pragma unroll
-    for (int j = 0; j < OG; j++) {
-        if constexpr (V == 2) {
-            *reinterpret_cast<float4 *>(zp + (size_t)j * L) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
-        } else {
-            zp[(size_t)j * L] = mk<T>(acc[j][0], acc[j][1]);
-        }
-    }
+    acc_store<T, V>(Zp + ((size_t)chunk * n_out_padded + (size_t)group * OG) * L + k0, L, acc);
 }
-
 // ---- look-ahead long-window MAC ("look-ahead") ------------------------------------------
 // On the long plan every partition p >= 1 of block s multiplies ring blocks s - 3 and older: at call t
 // the ring holds all that the tails (p >= 1) of blocks t+1, t+2 and t+3 need, so one pass over a tail
@@ -966,11 +974,9 @@ mac_la_head_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
     static_assert(sizeof(T) == 4, "float32 only");
     constexpr int V = 2;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int group = local % n_groups;
-    const int tile = (local / n_groups) * 8 + xcd;
-    if (tile >= n_tc) return;
-    const int k0 = (tile * 256 + (int)threadIdx.x) * V;
+    const MacTile m = mac_decode(bid, n_groups, 1);
+    if (m.tc >= n_tc) return;
+    const int group = m.group, k0 = m.template k0<V>(256);
     if (k0 >= L) return;
     const bool dc = (k0 == 0);
     const T am = dc ? (T)0 : (T)1;
@@ -991,7 +997,7 @@ mac_la_head_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
     const unsigned char *wg = sl.base + (unsigned long long)bid * sl.slice;
     const unsigned int hstep = (unsigned int)OG * sl.chunk, hlane = (unsigned int)threadIdx.x * 16u;
     // one load pipeline over the entries: three of them (ring tile + OG coefficient tiles each) in flight
-    struct Stage { c2<T> x[V]; c2<T> h[OG][V]; T sc[OG]; bool on; };
+    struct Stage { c2<T> x[V]; c2<T> h[OG][V]; T sc[OG]; bool on = false; };
     auto issue = [&](Stage &st, int q) {
         const MacEntry<T> *E = &entries[cr.begin + q];
         const int delay = E->delay;
@@ -999,9 +1005,9 @@ mac_la_head_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
 #pragma unroll
         for (int j = 0; j < OG; j++) st.sc[j] = E->term[j].scale;
         if (!st.on) return;
-        const int back = E->maxP == 1 ? -E->shift : 0;    // a one-partition entry: its only window is the shifted last one
-        const unsigned int slot = (t - (unsigned int)back - (unsigned int)delay) % (unsigned int)E->R;
-        const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
+        // partition 0 is the last one (lastP = 0) of a one-partition entry only: its only window is the shifted one
+        const unsigned int slot = ring_slot<3>(t, 0, 0, E->maxP == 1 ? E->shift : 0, delay, E->R);
+        const unsigned int xoff = spec_off<T>(slot, L, k0);
         const unsigned int hoff = (unsigned int)q * hstep + hlane;
         Load16<T, false>::get((const c2<T> *)((const char *)E->ring + xoff), st.x);
 #pragma unroll
@@ -1010,41 +1016,11 @@ mac_la_head_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
     auto consume = [&](const Stage &st) {
         if (!st.on) return;
 #pragma unroll
-        for (int j = 0; j < OG; j++) {
-            {
-                const T xr = st.x[0].x * st.sc[j], xi = st.x[0].y * st.sc[j];
-                cmac_first(acc[j][0], acc[j][1], xr, xi, st.h[j][0], am, dc);
-            }
-            {
-                const T xr = st.x[1].x * st.sc[j], xi = st.x[1].y * st.sc[j];
-                cmac(acc[j][2], acc[j][3], xr, xi, st.h[j][1]);
-            }
-        }
+        for (int j = 0; j < OG; j++) cmac_lane<T, V>(acc[j], st.x, st.sc[j], st.h[j], am, dc);
     };
-    const int n = cr.end - cr.begin;
-    Stage s0, s1, s2;
-    s0.on = s1.on = s2.on = false;
-    if (n >= 1) issue(s0, 0);
-    if (n >= 2) issue(s1, 1);
-    if (n >= 3) issue(s2, 2);
-    int i = 0;
-    for (; i + 6 <= n; i += 3) {
-        consume(s0); issue(s0, i + 3);
-        consume(s1); issue(s1, i + 4);
-        consume(s2); issue(s2, i + 5);
-    }
-    for (; i + 3 <= n; i += 3) {
-        consume(s0); if (i + 3 < n) issue(s0, i + 3);
-        consume(s1); if (i + 4 < n) issue(s1, i + 4);
-        consume(s2); if (i + 5 < n) issue(s2, i + 5);
-    }
-    if (i < n) consume(s0);
-    if (i + 1 < n) consume(s1);
+    MAC_PIPELINE3(Stage, 0, cr.end - cr.begin, issue, consume);
 
-    c2<T> *zp = Zp + zoff;
-#pragma unroll
-    for (int j = 0; j < OG; j++)
-        *reinterpret_cast<float4 *>(zp + (size_t)j * L) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+    acc_store<T, V>(Zp + zoff, L, acc);
 }
 
 // tail pass of slice `slice`: Zk[o] = sum over the slice's entries and p >= 1 of
@@ -1058,22 +1034,16 @@ mac_la_tail_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
     static_assert(sizeof(T) == 4, "float32 only");
     constexpr int V = 2, NB = 3;
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int group = local % n_groups;
-    const int tile = (local / n_groups) * 8 + xcd;
-    if (tile >= n_tc) return;
-    const int k0 = (tile * 256 + (int)threadIdx.x) * V;
+    const MacTile m = mac_decode(bid, n_groups, 1);
+    if (m.tc >= n_tc) return;
+    const int group = m.group, k0 = m.template k0<V>(256);
     if (k0 >= L) return;
     const bool dc = (k0 == 0);
     const T am = dc ? (T)0 : (T)1;
 
     T acc[NB][OG][2 * V];
 #pragma unroll
-    for (int k = 0; k < NB; k++)
-#pragma unroll
-        for (int j = 0; j < OG; j++)
-#pragma unroll
-            for (int v = 0; v < 2 * V; v++) acc[k][j][v] = (T)0;
+    for (int k = 0; k < NB; k++) acc_zero<T, V>(acc[k]);
 
     const ChunkRange cr = chunks[group];
     const LaSlice ls = la_slice(cr, slice);
@@ -1098,12 +1068,11 @@ mac_la_tail_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
         struct Stage { c2<T> x[NB][V]; c2<T> h[OG][V]; };
         auto issue = [&](Stage &st, int p) {
             // slot of block t + 3 - (3p - shift_p) - delay; those of t + 2 and t + 1 are the one and two before it
-            unsigned int slot = (t + 3u - (unsigned int)(3 * p - (p == lastP ? shift : 0)) - (unsigned int)delay) % (unsigned int)R;
+            unsigned int slot = ring_slot<3>(t + 3u, p, lastP, shift, delay, R);
             const unsigned int hoff = hbT + (unsigned int)p * hstep + hlane;
 #pragma unroll
             for (int k = NB - 1; k >= 0; k--) {
-                const unsigned int xoff = (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>);
-                Load16<T, false>::get((const c2<T> *)((const char *)ring + xoff), st.x[k]);
+                Load16<T, false>::get((const c2<T> *)((const char *)ring + spec_off<T>(slot, L, k0)), st.x[k]);
                 slot = slot == 0u ? (unsigned int)R - 1u : slot - 1u;
             }
 #pragma unroll
@@ -1111,16 +1080,7 @@ mac_la_tail_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
         };
         auto consume_k = [&](const Stage &st, int k) {
 #pragma unroll
-            for (int j = 0; j < OG; j++) {
-                {
-                    const T xr = st.x[k][0].x * sc[j], xi = st.x[k][0].y * sc[j];
-                    cmac_first(acc[k][j][0], acc[k][j][1], xr, xi, st.h[j][0], am, dc);
-                }
-                {
-                    const T xr = st.x[k][1].x * sc[j], xi = st.x[k][1].y * sc[j];
-                    cmac(acc[k][j][2], acc[k][j][3], xr, xi, st.h[j][1]);
-                }
-            }
+            for (int j = 0; j < OG; j++) cmac_lane<T, V>(acc[k][j], st.x[k], sc[j], st.h[j], am, dc);
         };
         if (pm[0] != pm[2]) {
             // warm-up: the three blocks do not have the same partitions yet (pm[0] <= pm[1] <= pm[2])
@@ -1136,36 +1096,13 @@ mac_la_tail_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__
 #pragma unroll
             for (int k = 0; k < NB; k++) consume_k(st, k);
         };
-        // the rotating three-stage pipeline of mac_xbar_kernel over p = 1 .. pm - 1
-        const int n = pm[2] - 1;
-        Stage s0, s1, s2;
-        if (n >= 1) issue(s0, 1);
-        if (n >= 2) issue(s1, 2);
-        if (n >= 3) issue(s2, 3);
-        int i = 0;
-        for (; i + 6 <= n; i += 3) {
-            consume(s0); issue(s0, i + 4);
-            consume(s1); issue(s1, i + 5);
-            consume(s2); issue(s2, i + 6);
-        }
-        for (; i + 3 <= n; i += 3) {
-            consume(s0); if (i + 3 < n) issue(s0, i + 4);
-            consume(s1); if (i + 4 < n) issue(s1, i + 5);
-            consume(s2); if (i + 5 < n) issue(s2, i + 6);
-        }
-        if (i < n) consume(s0);
-        if (i + 1 < n) consume(s1);
+        MAC_PIPELINE3(Stage, 1, pm[2] - 1, issue, consume);             // p = 1 .. pm - 1
     }
     c2<T> *const Z[NB] = {Z1, Z2, Z3};
     const size_t zoff = (size_t)group * OG * L + k0;
 #pragma unroll
-    for (int k = 0; k < NB; k++)
-#pragma unroll
-        for (int j = 0; j < OG; j++)
-            *reinterpret_cast<float4 *>(Z[k] + zoff + (size_t)j * L) =
-                make_float4(acc[k][j][0], acc[k][j][1], acc[k][j][2], acc[k][j][3]);
+    for (int k = 0; k < NB; k++) acc_store<T, V>(Z[k] + zoff, L, acc[k]);
 }
-
 // K2 over TWO consecutive blocks in one pass over the coefficients (uniform crossbars only: every
 // entry OG coefficient terms of full length).  The MAC of a large crossbar is nothing but the
 // coefficient stream -- config C reads 8 GiB per block to produce 2 MiB -- so a host that has two
@@ -1181,12 +1118,9 @@ mac_xbar2_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__re
                  int n_tc, unsigned int t /* counter of the FIRST block; the rings hold t + 1 already */, StreamLayout sl) {
     constexpr int V = 16 / sizeof(c2<T>);
     const int bid = blockIdx.x;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int group = local % n_groups;
-    const int tc = (local / n_groups) * 8 + xcd;
-    if (tc >= n_tc) return;
-    const int tile = tc / n_chunks, chunk = tc % n_chunks;
-    const int k0 = (tile * (int)blockDim.x + (int)threadIdx.x) * V;
+    const MacTile m = mac_decode(bid, n_groups, n_chunks);
+    if (m.tc >= n_tc) return;
+    const int group = m.group, chunk = m.chunk(), k0 = m.template k0<V>((int)blockDim.x);
     if (k0 >= L) return;
     const bool dc = (k0 == 0);
     const T am = dc ? (T)0 : (T)1;
@@ -1217,56 +1151,31 @@ mac_xbar2_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__re
             hlane = (unsigned int)threadIdx.x * 16u;
         }
         struct Stage { c2<T> x[V]; c2<T> h[OG][V]; };
-        auto ring_at = [&](unsigned int blk, c2<T> *x) {              // X_blk: ring slot (blk - delay) mod R
-            const unsigned int slot = (blk - (unsigned int)delay) % (unsigned int)R;
-            Load16<T, false>::get((const c2<T> *)((const char *)ring + (slot * (unsigned int)L + (unsigned int)k0) * (unsigned int)sizeof(c2<T>)), x);
+        auto ring_at = [&](unsigned int blk, int p, c2<T> *x) {       // X_(blk - p): what block blk multiplies H_p with
+            Load16<T, false>::get((const c2<T> *)((const char *)ring + spec_off<T>(ring_slot<1>(blk, p, 0, 0, delay, R), L, k0)), x);
         };
         auto issue = [&](Stage &st, int p) {
-            ring_at(t - (unsigned int)p, st.x);
+            ring_at(t, p, st.x);
             const unsigned int hoff = (unsigned int)p * hstep + hlane;
 #pragma unroll
             for (int j = 0; j < OG; j++) Load16<T, NT>::get((const c2<T> *)((const char *)Hs[j] + hoff), st.h[j]);
         };
-        c2<T> xn[V];                                                    // X_(t+1-p): what block t+1 multiplies H_p with
+        c2<T> xn[V];                                                    // X_(t+1-p)
         auto consume = [&](const Stage &st) {
 #pragma unroll
             for (int j = 0; j < OG; j++) {
-                {
-                    const T xr = st.x[0].x * sc[j], xi = st.x[0].y * sc[j];
-                    cmac_first(acc0[j][0], acc0[j][1], xr, xi, st.h[j][0], am, dc);
-                    const T yr = xn[0].x * sc[j], yi = xn[0].y * sc[j];
-                    cmac_first(acc1[j][0], acc1[j][1], yr, yi, st.h[j][0], am, dc);
-                }
-                if constexpr (V == 2) {
-                    const T xr = st.x[1].x * sc[j], xi = st.x[1].y * sc[j];
-                    cmac(acc0[j][2], acc0[j][3], xr, xi, st.h[j][1]);
-                    const T yr = xn[1].x * sc[j], yi = xn[1].y * sc[j];
-                    cmac(acc1[j][2], acc1[j][3], yr, yi, st.h[j][1]);
-                }
+                cmac_lane<T, V>(acc0[j], st.x, sc[j], st.h[j], am, dc);
+                cmac_lane<T, V>(acc1[j], xn, sc[j], st.h[j], am, dc);
             }
 #pragma unroll
             for (int v = 0; v < V; v++) xn[v] = st.x[v];               // X_(t-p) is X_(t+1-(p+1))
         };
-        const int n = maxP - p0;
-        Stage s0, s1, s2;
-        if (n >= 1) { ring_at(t + 1u - (unsigned int)p0, xn); issue(s0, p0); }
-        if (n >= 2) issue(s1, p0 + 1);
-        if (n >= 3) issue(s2, p0 + 2);
-        int i = 0;
-        for (; i + 6 <= n; i += 3) {
-            consume(s0); issue(s0, p0 + i + 3);
-            consume(s1); issue(s1, p0 + i + 4);
-            consume(s2); issue(s2, p0 + i + 5);
-        }
-        for (; i + 3 <= n; i += 3) {
-            consume(s0); if (i + 3 < n) issue(s0, p0 + i + 3);
-            consume(s1); if (i + 4 < n) issue(s1, p0 + i + 4);
-            consume(s2); if (i + 5 < n) issue(s2, p0 + i + 5);
-        }
-        if (i < n) consume(s0);
-        if (i + 1 < n) consume(s1);
+        if (maxP > p0) ring_at(t + 1u, p0, xn);
+        MAC_PIPELINE3(Stage, p0, maxP - p0, issue, consume);
     }
     const size_t zoff = ((size_t)chunk * n_out_padded + (size_t)group * OG) * L + k0;
+    // the two sets interleaved, here and in the zeroing above: with acc_zero / acc_store once per set
+    // the float32 kernel needs 362 VGPRs instead of 358 and the float64 one 340 instead of 336
 #pragma unroll
     for (int j = 0; j < OG; j++) {
         if constexpr (V == 2) {
@@ -1278,7 +1187,6 @@ mac_xbar2_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__re
         }
     }
 }
-
 // K2 for ONE-TO-ONE plans (every output fed by at most one entry of a single coefficient term per
 // chunk: massive_config, BASELINE configs[3]): there is nothing to share between outputs, so the
 // crossbar kernel's decomposition -- a workgroup owns a 4 KiB bin tile and walks entries and
@@ -1323,7 +1231,7 @@ mac_diag_kernel(const MacEntry<T> *__restrict__ entries, const int *__restrict__
         struct Half { c2<T> x[HT][V], h[HT][V]; };
         // one half of partition p in flight: 2 x HT loads of 16 bytes per lane out of two sequential runs
         auto issue = [&](Half &b, int p, int half) {
-            const unsigned int slot = (t - (unsigned int)p - (unsigned int)delay) % (unsigned int)R;
+            const unsigned int slot = ring_slot<1>(t, p, 0, 0, delay, R);
             const c2<T> *xb = ring + (size_t)slot * L + half * HT * TB, *hb = H + (size_t)p * L + half * HT * TB;
 #pragma unroll
             for (int i = 0; i < HT; i++) {
@@ -1337,14 +1245,7 @@ mac_diag_kernel(const MacEntry<T> *__restrict__ entries, const int *__restrict__
                 const int tt = half * HT + i;
                 const bool dc = tt == 0 && kl == 0;                 // element 0 = (DC, Nyquist): real * real per component
                 const T am = dc ? (T)0 : (T)1;
-                {
-                    const T xr = b.x[i][0].x * sc, xi = b.x[i][0].y * sc;
-                    cmac_first(acc[tt][0], acc[tt][1], xr, xi, b.h[i][0], am, dc);
-                }
-                if constexpr (V == 2) {
-                    const T xr = b.x[i][1].x * sc, xi = b.x[i][1].y * sc;
-                    cmac(acc[tt][2], acc[tt][3], xr, xi, b.h[i][1]);
-                }
+                cmac_lane<T, V>(acc[tt], b.x[i], sc, b.h[i], am, dc);
             }
         };
         Half a, b;
