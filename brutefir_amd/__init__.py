@@ -142,6 +142,7 @@ def lib():
     L.bfhip_engine_uses_diag_mac.argtypes = [vp]
     L.bfhip_engine_window_blocks.argtypes = [vp]
     L.bfhip_engine_lookahead_blocks.argtypes = [vp]
+    L.bfhip_engine_lookahead_far_blocks.argtypes = [vp]
     L.bfhip_engine_mac_counts.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.bfhip_engine_enable_pairs.argtypes = [vp, ci]
     L.bfhip_engine_block_pair_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -537,6 +538,11 @@ class Engine:
     def lookahead_blocks(self):
         """3: the long plan in force runs the look-ahead MAC (tails of the next 3 blocks per call); 0: not"""
         return _check(lib().bfhip_engine_lookahead_blocks(self.h))
+
+    @property
+    def lookahead_far_blocks(self):
+        """6: the look-ahead MAC runs its far tier (partitions >= 2 of the next 6 blocks per call); 0: not"""
+        return _check(lib().bfhip_engine_lookahead_far_blocks(self.h))
 
     @property
     def mac_counts(self):

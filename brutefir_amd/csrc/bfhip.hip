@@ -476,6 +476,13 @@ struct bfhip_engine {
     unsigned long long la_epoch = 1;
     unsigned long long la_for[4][3] = {};
     unsigned long long la_at[4][3] = {};       // epoch 0: never written
+    // second tier (kernels.h, la_far_phase): partitions >= 2 of one sixth of the entries for blocks t+1 .. t+6
+    // into d_far[block mod 7][slice]; the tail pass above is then p = 1 alone.  Same epoch, its own table.
+    bool far_active = false;
+    void *d_far = nullptr;         // [7][6][n_out_padded][2L] complex
+    size_t far_cap = 0;
+    unsigned long long far_for[7][LA_FAR] = {};
+    unsigned long long far_at[7][LA_FAR] = {};
     unsigned long long n_la_head = 0, n_la_full = 0;
     unsigned long long n_mac_launches = 0;      // MAC kernels launched by do_mac, of every kind
 
@@ -873,10 +880,24 @@ c2<float> *la_buffer(bfhip_engine *e, unsigned long long block, int slice) {
 }
 // head: the head pass of this block (its three ahead buffers are current) and the tail pass of this call's slice
 // in one launch; else the tail pass alone, behind a full long MAC
+c2<float> *far_buffer(bfhip_engine *e, unsigned long long block, int slice) {
+    const size_t one = (size_t)e->n_out_padded * 2 * e->L;
+    return (c2<float> *)e->d_far + ((size_t)(block % 7ull) * LA_FAR + (size_t)slice) * one;
+}
 void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
     const int n_tc = e->lw_tiles;
     const unsigned long long T = e->blocks_done;
     const int slice = (int)(T % 3ull);
+    const bool two = e->far_active && e->d_far != nullptr;
+    LaFar<float> far = {};
+    if (two) {
+        far.slice = (int)(T % (unsigned long long)LA_FAR);
+        for (int k = 0; k < LA_FAR; k++) {
+            far.A[k] = far_buffer(e, T, k);
+            far.Z[k] = far_buffer(e, T + 1 + k, far.slice);
+            far.age[k] = block_age(e, k + 1);
+        }
+    }
 #define BFHIP_LAUNCH_LA(PHASES)                                                                                        \
     hipLaunchKernelGGL((mac_la_kernel<float, PHASES>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,         \
                        (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,      \
@@ -884,8 +905,9 @@ void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
                        (const c2<float> *)la_buffer(e, T, 2),                                                          \
                        la_buffer(e, T + 1, slice), la_buffer(e, T + 2, slice), la_buffer(e, T + 3, slice),             \
                        2 * e->L, e->n_groups, n_tc, e->blockcounter, block_age(e), block_age(e, 1), block_age(e, 2),   \
-                       block_age(e, 3), slice, e->lstream)
-    if (head) BFHIP_LAUNCH_LA(3); else BFHIP_LAUNCH_LA(2);
+                       block_age(e, 3), slice, e->lstream, far)
+    if (two) { if (head) BFHIP_LAUNCH_LA(7); else BFHIP_LAUNCH_LA(6); }
+    else if (head) BFHIP_LAUNCH_LA(3); else BFHIP_LAUNCH_LA(2);
 #undef BFHIP_LAUNCH_LA
     *err = hipGetLastError();
     if (*err != hipSuccess) return;
@@ -894,6 +916,11 @@ void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
         e->la_for[(T + k) & 3ull][slice] = T + k;
         e->la_at[(T + k) & 3ull][slice] = e->la_epoch;
     }
+    if (two)
+        for (int k = 1; k <= LA_FAR; k++) {
+            e->far_for[(T + k) % 7ull][far.slice] = T + k;
+            e->far_at[(T + k) % 7ull][far.slice] = e->la_epoch;
+        }
 }
 // No block has been processed (or prewarm has just declared the zero-initialised rings N blocks of
 // silence): every window the tails of the next three blocks read is silence, so their ahead buffers
@@ -903,6 +930,11 @@ int la_prime(bfhip_engine *e) {
     HIPCHK(hipMemsetAsync(e->d_ahead, 0, e->ahead_cap, e->stream));
     for (unsigned long long T = e->blocks_done; T < e->blocks_done + 3; T++)
         for (int j = 0; j < 3; j++) { e->la_for[T & 3ull][j] = T; e->la_at[T & 3ull][j] = e->la_epoch; }
+    if (!e->far_active || e->d_far == nullptr) return BFHIP_OK;
+    // the far tails of the next six blocks read silence alone as well
+    HIPCHK(hipMemsetAsync(e->d_far, 0, e->far_cap, e->stream));
+    for (unsigned long long T = e->blocks_done; T < e->blocks_done + LA_FAR; T++)
+        for (int j = 0; j < LA_FAR; j++) { e->far_for[T % 7ull][j] = T; e->far_at[T % 7ull][j] = e->la_epoch; }
     return BFHIP_OK;
 }
 // are the three ahead buffers of the block about to run current?
@@ -910,6 +942,9 @@ bool la_block_valid(const bfhip_engine *e) {
     const unsigned long long T = e->blocks_done;
     for (int j = 0; j < 3; j++)
         if (e->la_for[T & 3ull][j] != T || e->la_at[T & 3ull][j] != e->la_epoch) return false;
+    if (e->far_active && e->d_far != nullptr)
+        for (int j = 0; j < LA_FAR; j++)
+            if (e->far_for[T % 7ull][j] != T || e->far_at[T % 7ull][j] != e->la_epoch) return false;
     return true;
 }
 
@@ -1278,7 +1313,7 @@ struct LongWhole { bool ok = false; int E = 0, P = 0; std::vector<int> wpos; };
 int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat, const std::vector<ChunkRange> &chunks, int S,
                       const LongWhole &lwh) {
     e->lw_active = false;
-    e->la_active = false;
+    e->la_active = e->far_active = false;
     e->la_epoch++;                 // a new plan: other sets, scales, delays or lengths than the stored products used
     if (!lwh.ok || flat.empty() || e->mac_diag || !e->mac_nt || e->mac_unroll != 0 || e->mac_threads != 256)
         return BFHIP_OK;
@@ -1406,6 +1441,29 @@ int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat,
         }
     }
     e->la_active = la;
+    // second tier: some entry has a partition >= 2 beyond the first, none of them reaches a block younger
+    // than t - 6 (the shifted last partition does when it is p = 2 without delay), and the same volume
+    // (BFHIP_LOOKAHEAD_FAR=1 / 0: whenever the first tier runs / never; BFHIP_LOOKAHEAD=1 alone: not)
+    int want_far = -1;
+    if (const char *env = getenv("BFHIP_LOOKAHEAD_FAR")) want_far = atoi(env) != 0 ? 1 : 0;
+    bool far = la && want_far != 0 && (want_far == 1 || vol >= 1073741824.0);
+    bool any3 = false;
+    for (size_t i = 0; i < lflat.size() && far; i++) {
+        const MacEntry<float> &en = lflat[i];
+        any3 = any3 || en.maxP >= 3;
+        far = en.maxP < 3 || 3 * (en.maxP - 1) - en.shift + en.delay >= 6;
+    }
+    far = far && any3;
+    if (far) {
+        const size_t fb = (size_t)7 * LA_FAR * e->n_out_padded * LL * sizeof(c2<float>);
+        if (fb > e->far_cap) {
+            if (e->d_far) (void)hipFree(e->d_far);
+            e->d_far = nullptr; e->far_cap = 0;
+            if (dev_alloc(&e->d_far, fb) != hipSuccess) { (void)hipGetLastError(); far = false; }   // one tier
+            else e->far_cap = fb;
+        }
+    }
+    e->far_active = far;
     if (la && e->blocks_done == 0) return la_prime(e);
     return BFHIP_OK;
 }
@@ -1861,7 +1919,7 @@ int build_plan_t(bfhip_engine *e) {
         if (r != BFHIP_OK) return r;
     }
     e->lw_active = false;
-    e->la_active = false;
+    e->la_active = e->far_active = false;
     e->la_epoch++;
     if constexpr (std::is_same<T, float>::value) {
         const int r = build_long_layout(e, flat, chunks, S, lwh);
@@ -2693,7 +2751,7 @@ void bfhip_engine_destroy(bfhip_engine *e) {
                     e->d_big[0], e->d_big[1], e->d_big[2], e->d_tw13, e->d_tww,
                     e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc, e->d_stream, e->d_where,
                     e->d_planar[0], e->d_planar[1], e->d_phys_skip,
-                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere, e->d_ahead};
+                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere, e->d_ahead, e->d_far};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto ev : e->ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
@@ -3687,11 +3745,11 @@ int bfhip_engine_set_fscale(bfhip_engine *e, int filter, int index, double scale
 static int lw_drop(bfhip_engine *e) {
     if (!e->lw_struct) return BFHIP_OK;
     { const int r = sync_all(e); if (r != BFHIP_OK) return r; }
-    e->lw_struct = e->lw_active = e->la_active = false;
+    e->lw_struct = e->lw_active = e->la_active = e->far_active = false;
     e->la_epoch++;
-    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream, &e->d_ahead}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream, &e->d_ahead, &e->d_far}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     e->lstream_cap = 0;
-    e->ahead_cap = 0;
+    e->ahead_cap = e->far_cap = 0;
     e->lstream = StreamLayout{nullptr, 0, 0, 0};
     e->lkeys.clear();
     for (bool &z : e->zp_long) z = false;
@@ -4264,6 +4322,10 @@ int bfhip_engine_window_blocks(const bfhip_engine *e) {
 int bfhip_engine_lookahead_blocks(const bfhip_engine *e) {
     if (!e) return fail(BFHIP_EINVAL, "lookahead_blocks: null engine");
     return e->lw_active && e->la_active && !e->rt.on ? 3 : 0;
+}
+int bfhip_engine_lookahead_far_blocks(const bfhip_engine *e) {
+    if (!e) return fail(BFHIP_EINVAL, "lookahead_far_blocks: null engine");
+    return e->lw_active && e->la_active && e->far_active && !e->rt.on ? LA_FAR : 0;
 }
 int bfhip_engine_ring_depth(const bfhip_engine *e) { return e ? e->R : 0; }
 int bfhip_engine_mac_counts(const bfhip_engine *e, unsigned long long *counts) {

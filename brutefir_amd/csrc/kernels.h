@@ -988,13 +988,32 @@ __device__ __forceinline__ LaSlice la_slice(ChunkRange cr, int j) {
     const int first = cr.begin + j * b + (j < r ? j : r);
     return LaSlice{first, first + b + (j < r ? 1 : 0)};
 }
+// Two tiers (PHASES & 4): every p >= 2 reaches back at least 6 blocks (the host checks 3p - shift_p + delay
+// >= 6), so one read of such a tile feeds blocks t+1 .. t+6.  The near tier is the tail pass above restricted
+// to p = 1; the far tier cuts a group's entries into sixths by the same rule, call t runs slice t mod 6 and
+// stores into the far buffers of blocks t+1 .. t+6 (seven in rotation: never one of block t).  The head pass
+// then starts from ((near0 + near1) + near2) + far0 + .. + far5.
+constexpr int LA_FAR = 6;
+__device__ __forceinline__ LaSlice la_far_slice(ChunkRange cr, int j) {
+    const int n = cr.end - cr.begin, b = n / LA_FAR, r = n % LA_FAR;
+    const int first = cr.begin + j * b + (j < r ? j : r);
+    return LaSlice{first, first + b + (j < r ? 1 : 0)};
+}
+template <typename T> struct LaFar {
+    const c2<T> *A[LA_FAR];     // head pass: the far buffers of block t, slices 0 .. 5
+    c2<T> *Z[LA_FAR];           // far pass: this call's slice of the far buffers of blocks t+1 .. t+6
+    int age[LA_FAR];            // the ages blocks t+1 .. t+6 will have
+    int slice, pad;             // t mod 6
+};
 
 // head pass: Zp[o] = A0[o] + A1[o] + A2[o] + sum over entries of scale * W_(t + shift0 - delay) * G_(e, 0)
-template <typename T, bool FIX>
+// (FAR: the six far buffers of the block on top of the three, in slice order)
+template <typename T, bool FIX, bool FAR = false>
 __device__ __forceinline__ void
 la_head_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsigned char *wg,
               c2<T> *__restrict__ Zp, const c2<T> *__restrict__ A0, const c2<T> *__restrict__ A1,
-              const c2<T> *__restrict__ A2, int L, int group, int k0, unsigned int t, int age, StreamLayout sl) {
+              const c2<T> *__restrict__ A2, int L, int group, int k0, unsigned int t, int age, StreamLayout sl,
+              const LaFar<T> &far) {
     constexpr int V = 2;
     const bool dc = (k0 == 0);
     const T am = dc ? (T)0 : (T)1;
@@ -1009,6 +1028,16 @@ la_head_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsi
         Load16<T, false>::get(A2 + zoff + (size_t)j * L, a2);
         acc[j][0] = (a0[0].x + a1[0].x) + a2[0].x; acc[j][1] = (a0[0].y + a1[0].y) + a2[0].y;
         acc[j][2] = (a0[1].x + a1[1].x) + a2[1].x; acc[j][3] = (a0[1].y + a1[1].y) + a2[1].y;
+        if constexpr (FAR) {
+            c2<T> f[LA_FAR][V];
+#pragma unroll
+            for (int s = 0; s < LA_FAR; s++) Load16<T, false>::get(far.A[s] + zoff + (size_t)j * L, f[s]);
+#pragma unroll
+            for (int s = 0; s < LA_FAR; s++) {
+                acc[j][0] += f[s][0].x; acc[j][1] += f[s][0].y;
+                acc[j][2] += f[s][1].x; acc[j][3] += f[s][1].y;
+            }
+        }
     }
 
     const unsigned int hstep = (unsigned int)OG * sl.chunk, hlane = (unsigned int)threadIdx.x * 16u;
@@ -1041,7 +1070,8 @@ la_head_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsi
 
 // tail pass of slice `slice`: Zk[o] = sum over the slice's entries and p >= 1 of
 // scale * W_(t + k - 3p + shift_p - delay) * G_(e, p) for k = 1, 2, 3 (agek: the age block t + k will have)
-template <typename T, bool FIX>
+// (NEAR: the near tier, p = 1 alone; p >= 2 is the far pass's)
+template <typename T, bool FIX, bool NEAR = false>
 __device__ __forceinline__ void
 la_tail_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsigned char *wg,
               c2<T> *__restrict__ Z1, c2<T> *__restrict__ Z2, c2<T> *__restrict__ Z3,
@@ -1059,7 +1089,9 @@ la_tail_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsi
     // partitions of entry E that exist for a block of age `age`
     auto parts = [&](const MacEntry<T> *E, int age) {
         const int avail = age - E->delay > 0 ? (age - E->delay + 2) / 3 : 0;
-        return E->maxP < avail ? E->maxP : avail;
+        const int pm = E->maxP < avail ? E->maxP : avail;
+        if constexpr (NEAR) return pm < 2 ? pm : 2;
+        else return pm;
     };
     struct Stage { c2<T> x[NB][V]; c2<T> h[OG][V]; T sc[OG]; };
     // the loads of partition p of entry E: the windows of blocks t + 1 .. t + 3 and the OG coefficient tiles
@@ -1125,18 +1157,120 @@ la_tail_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsi
     for (int k = 0; k < NB; k++) acc_store<T, V>(Z[k] + zoff, L, acc[k]);
 }
 
+// far pass of slice far.slice: far.Z[k - 1][o] = sum over the slice's entries and p >= 2 of
+// scale * W_(t + k - 3p + shift_p - delay) * G_(e, p) for k = 1 .. 6.  Six accumulator sets of OG outputs and
+// three load stages do not fit 256 registers, and the packed product cannot take AGPRs: the group's outputs
+// are done in two sweeps of OG / 2 (96 accumulators, 3 x (6 ring + 4 coefficient tiles) in flight).  Every
+// coefficient tile is still read once -- sweep 0 reads tiles 0 .. 3 of each (entry, p), sweep 1 tiles 4 .. 7,
+// 16 KiB runs 32 KiB apart -- and the ring tiles twice, the second time from L2.
+template <typename T, bool FIX>
+__device__ __forceinline__ void
+la_far_phase(const MacEntry<T> *__restrict__ entries, ChunkRange cr, const unsigned char *wg,
+             int L, int group, int k0, unsigned int t, StreamLayout sl, const LaFar<T> &far) {
+    constexpr int V = 2, NB = LA_FAR, HG = OG / 2;
+    const bool dc = (k0 == 0);
+    const T am = dc ? (T)0 : (T)1;
+    const LaSlice ls = la_far_slice(cr, far.slice);
+    const unsigned int hstep = (unsigned int)OG * sl.chunk, hlane = (unsigned int)threadIdx.x * 16u;
+    auto parts = [&](const MacEntry<T> *E, int age) {
+        const int avail = age - E->delay > 0 ? (age - E->delay + 2) / 3 : 0;
+        return E->maxP < avail ? E->maxP : avail;
+    };
+    // the slice's (entry, p >= 2) pairs, entry-major; steady: the six blocks have the same partitions
+    int n_items = 0;
+    bool steady = true;
+    for (int e = ls.begin; e < ls.end; e++) {
+        const int pm0 = parts(&entries[e], far.age[0]), pm5 = parts(&entries[e], far.age[NB - 1]);
+        steady = steady && pm0 == pm5;
+        if (pm5 > 2) n_items += pm5 - 2;
+    }
+    const size_t zoff = (size_t)group * OG * L + k0;
+#pragma unroll 1
+    for (int half = 0; half < 2; half++) {
+        T acc[NB][HG][2 * V];
+#pragma unroll
+        for (int k = 0; k < NB; k++)
+#pragma unroll
+            for (int j = 0; j < HG; j++)
+#pragma unroll
+                for (int v = 0; v < 2 * V; v++) acc[k][j][v] = (T)0;
+        const unsigned char *wh = wg + (unsigned int)(half * HG) * sl.chunk;
+        struct Stage { c2<T> x[NB][V]; c2<T> h[HG][V]; T sc[HG]; };
+        // the loads of partition p of entry E: the windows of blocks t + 1 .. t + 6 and this sweep's coefficient tiles
+        auto load = [&](Stage &st, const MacEntry<T> *E, int p) {
+            const c2<T> *ring = E->ring;
+            const int R = E->R;
+            // slot of block t + 6 - (3p - shift_p) - delay; those of t + 5 .. t + 1 are the ones before it
+            unsigned int slot = ring_slot<3>(t + (unsigned int)NB, p, E->maxP - 1, E->shift, E->delay, R);
+            const unsigned int hoff = sl.head + (unsigned int)(E - entries - cr.begin) * (sl.entry_bytes - hstep) +
+                                      (unsigned int)(p - 1) * hstep + hlane;
+#pragma unroll
+            for (int k = NB - 1; k >= 0; k--) {
+                Load16<T, false>::get((const c2<T> *)((const char *)ring + spec_off<T>(slot, L, k0)), st.x[k]);
+                slot = slot == 0u ? (unsigned int)R - 1u : slot - 1u;
+            }
+#pragma unroll
+            for (int j = 0; j < HG; j++) {
+                Load16<T, true>::get((const c2<T> *)(wh + (unsigned int)j * sl.chunk + hoff), st.h[j]);
+                st.sc[j] = E->term[half * HG + j].scale;
+            }
+        };
+        auto consume_k = [&](const Stage &st, int k) {
+#pragma unroll
+            for (int j = 0; j < HG; j++) cmac_lane<T, V, FIX>(acc[k][j], st.x[k], st.sc[j], st.h[j], am, dc);
+        };
+        if (steady) {
+            // one load pipeline over all the pairs: a cursor walks them in the order they are accumulated in
+            int ce = ls.begin - 1, cp = 0, cpm = 0;
+            auto issue = [&](Stage &st, int) {
+                while (cp >= cpm) { ce++; cpm = parts(&entries[ce], far.age[NB - 1]); cp = 2; }
+                load(st, &entries[ce], cp);
+                cp++;
+            };
+            auto consume = [&](const Stage &st) {
+#pragma unroll
+                for (int k = 0; k < NB; k++) consume_k(st, k);
+            };
+            MAC_PIPELINE3(Stage, 0, n_items, issue, consume);
+        } else {
+            // warm-up: the later of the six blocks have more partitions than the earlier ones
+            for (int e = ls.begin; e < ls.end; e++) {
+                const MacEntry<T> *E = &entries[e];
+                int pm[NB];
+#pragma unroll
+                for (int k = 0; k < NB; k++) pm[k] = parts(E, far.age[k]);
+                for (int p = 2; p < pm[NB - 1]; p++) {
+                    Stage st;
+                    load(st, E, p);
+#pragma unroll
+                    for (int k = 0; k < NB; k++) if (p < pm[k]) consume_k(st, k);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NB; k++)
+#pragma unroll
+            for (int j = 0; j < HG; j++)
+                *reinterpret_cast<float4 *>(far.Z[k] + zoff + (size_t)(half * HG + j) * L) =
+                    make_float4(acc[k][j][0], acc[k][j][1], acc[k][j][2], acc[k][j][3]);
+    }
+}
+
 // The look-ahead launch of call t.  PHASES & 1: the head pass of block t (Zp from its ahead buffers A0 .. A2);
 // PHASES & 2: the tail pass of slice `slice` into Z1 .. Z3, ahead buffers of blocks t + 1 .. t + 3.  The tail
 // pass never writes a buffer of block t (four buffers in rotation), so a workgroup runs one after the
 // other with nothing to wait for: one launch per block in steady state, no ramp between two grids.
+// PHASES & 4: two tiers -- the head pass adds the block's six far buffers, the tail pass is the near tier
+// (p = 1), and the far pass of slice far.slice follows it.
 template <typename T, int PHASES>
 __global__ __launch_bounds__(256) void
 mac_la_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__restrict__ chunks,
               c2<T> *__restrict__ Zp, const c2<T> *__restrict__ A0, const c2<T> *__restrict__ A1,
               const c2<T> *__restrict__ A2, c2<T> *__restrict__ Z1, c2<T> *__restrict__ Z2, c2<T> *__restrict__ Z3,
               int L, int n_groups, int n_tc, unsigned int t, int age, int age1, int age2, int age3, int slice,
-              StreamLayout sl) {
+              StreamLayout sl, LaFar<T> far) {
     static_assert(sizeof(T) == 4, "float32 only");
+    constexpr bool FAR = (PHASES & 4) != 0;
     const int bid = blockIdx.x;
     const MacTile m = mac_decode(bid, n_groups, 1);
     if (m.tc >= n_tc) return;
@@ -1147,11 +1281,13 @@ mac_la_kernel(const MacEntry<T> *__restrict__ entries, const ChunkRange *__restr
     // element 0 = (DC, Nyquist) is in the first lane of the wave whose first bin is 0: that wave alone
     // runs the copy of the passes that carries its fix-up
     if (__builtin_amdgcn_readfirstlane(k0) == 0) {
-        if constexpr (PHASES & 1) la_head_phase<T, true>(entries, cr, wg, Zp, A0, A1, A2, L, group, k0, t, age, sl);
-        if constexpr (PHASES & 2) la_tail_phase<T, true>(entries, cr, wg, Z1, Z2, Z3, L, group, k0, t, age1, age2, age3, slice, sl);
+        if constexpr (PHASES & 1) la_head_phase<T, true, FAR>(entries, cr, wg, Zp, A0, A1, A2, L, group, k0, t, age, sl, far);
+        if constexpr (PHASES & 2) la_tail_phase<T, true, FAR>(entries, cr, wg, Z1, Z2, Z3, L, group, k0, t, age1, age2, age3, slice, sl);
+        if constexpr (FAR) la_far_phase<T, true>(entries, cr, wg, L, group, k0, t, sl, far);
     } else {
-        if constexpr (PHASES & 1) la_head_phase<T, false>(entries, cr, wg, Zp, A0, A1, A2, L, group, k0, t, age, sl);
-        if constexpr (PHASES & 2) la_tail_phase<T, false>(entries, cr, wg, Z1, Z2, Z3, L, group, k0, t, age1, age2, age3, slice, sl);
+        if constexpr (PHASES & 1) la_head_phase<T, false, FAR>(entries, cr, wg, Zp, A0, A1, A2, L, group, k0, t, age, sl, far);
+        if constexpr (PHASES & 2) la_tail_phase<T, false, FAR>(entries, cr, wg, Z1, Z2, Z3, L, group, k0, t, age1, age2, age3, slice, sl);
+        if constexpr (FAR) la_far_phase<T, false>(entries, cr, wg, L, group, k0, t, sl, far);
     }
 }
 // K2 over TWO consecutive blocks in one pass over the coefficients (uniform crossbars only: every

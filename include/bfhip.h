@@ -412,6 +412,11 @@ int bfhip_engine_window_blocks(const bfhip_engine *e);
    real-time mode, >= 1 GiB of coefficients, BFHIP_LOOKAHEAD=0/1 to force); 0: it does not.
    < 0 on a NULL handle */
 int bfhip_engine_lookahead_blocks(const bfhip_engine *e);
+/* 6: the look-ahead MAC in force runs two tiers -- p = 1 as above, and one sixth of the partitions
+   p >= 2 once for the next six blocks (some filter has three long partitions or more, every p >= 2
+   reaches back six blocks or more, >= 1 GiB of coefficients; BFHIP_LOOKAHEAD_FAR=0/1 to force,
+   BFHIP_LOOKAHEAD=1 alone does not switch it on); 0: one tier or none.  < 0 on a NULL handle */
+int bfhip_engine_lookahead_far_blocks(const bfhip_engine *e);
 /* depth of the input spectrum rings (n_blocks, plus one spare slot when the block is pipelined) */
 int bfhip_engine_ring_depth(const bfhip_engine *e);
 /* counts[0]: MAC kernels launched by the block calls so far, of every kind; counts[1]: blocks of the

@@ -38,8 +38,10 @@ def demangle(names):
     return {n: re.sub(r"^void (bfhip::)?(\(anonymous namespace\)::)?", "", d).split("(")[0] for n, d in zip(names, out)}
 
 
-def loop_mix(body):
-    """the innermost loop with the most fused multiply-adds -> instruction counts"""
+def loop_mix(body, pipelined=False):
+    """the innermost loop with the most fused multiply-adds -> instruction counts
+    (pipelined: every innermost multiplying loop that issues all the loads of three stages itself, in code order --
+    a kernel of several passes has one or two per pass)"""
     lines = [ln.split(";")[0].strip() for ln in body]
     label_at = {m.group(1): i for i, ln in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", ln)] if m}
     loops = []
@@ -67,6 +69,8 @@ def loop_mix(body):
             "v_cndmask": sum(1 for x in ins if x.startswith("v_cndmask")),
             "global_load": sum(1 for x in ins if x.startswith("global_load")),
         })
+    if pipelined:
+        return [f for f in found if f["global_load"] >= 27]
     # the steady loops issue every load themselves (those that fill and drain a pipeline branch around some);
     # a kernel that runs the wave holding element 0 through a copy of its own has two: the lean one first
     top = max(((f["fma"], f["global_load"]) for f in found), default=None)
@@ -90,6 +94,8 @@ def kernels(text):
         b = next(i for i in range(a, len(lines)) if lines[i].startswith(".Lfunc_end"))
         row = dict(row)
         row["loops"] = loop_mix(lines[a:b])
+        if names[name].startswith("mac_la_"):
+            row["pipelined_loops"] = loop_mix(lines[a:b], pipelined=True)
         out[names[name]] = row
     return out
 

@@ -24,9 +24,11 @@ def main():
                        if ln.startswith("{")][-1])
     # the MAC of the plan: the crossbar kernel, or mac_diag_kernel for one-to-one plans (workload D)
     macs = [k for k in kt if ("mac_xbar_kernel" in k or "mac_diag_kernel" in k) and k in fetch and k in write]
-    # the look-ahead long MAC is one launch per block, head and tail pass in one grid (mac_la_kernel<float, 3>)
-    la = sorted(k for k in kt if "mac_la_kernel" in k and ", 3>" in k and k in fetch and k in write)
+    # the look-ahead long MAC is one launch per block, all its passes in one grid: mac_la_kernel<float, 3>
+    # (head and tail), or <float, 7> with the far tier
     spent = lambda ks: sum(kt[k]["avg_ns_all"] * kt[k]["calls"] for k in ks)      # noqa: E731
+    la = sorted((k for k in kt if "mac_la_kernel" in k and (", 3>" in k or ", 7>" in k) and k in fetch and k in write),
+                key=lambda k: -spent([k]))[:1]
     if len(la) == 1 and (not macs or spent(la) > max(spent([k]) for k in macs)):
         name = " + ".join(la)
         f = {q: sum(fetch[k][q] for k in la) for q in ("fetch_bytes_corrected", "FETCH_SIZE_per_dispatch_steady")}
