@@ -67,6 +67,29 @@ def interleaved_formats(name, n_channels):
     return [make_format(name, n_channels, c * nbytes) for c in range(n_channels)]
 
 
+def period_layout(L0, devices):
+    """buffer_format of one side's period buffer of L0 frames for a list of devices laid back to back
+    (dai.c:537-576).  A device is (format name, open_channels, channel_selection, interleaved); the
+    side's channels are numbered in device order, then selection order.  An interleaved device takes
+    L0 frames of open_channels samples and channel i of its selection sits at sample slot
+    channel_selection[i] of every frame; a non-interleaved one gives each selected channel a plane of
+    L0 samples.  The running size is rounded up to 32 bytes after every device.
+    Returns (formats, n_bytes): what Nupc.set_format and Nupc.set_buffer_bytes take."""
+    formats, n_bytes = [], 0
+    for name, open_channels, selection, interleaved in devices:
+        nbytes = SAMPLE_FORMATS[name][0]
+        for slot in selection:
+            if interleaved:
+                formats.append(make_format(name, open_channels, n_bytes + slot * nbytes))
+            else:
+                formats.append(make_format(name, 1, n_bytes))
+                n_bytes += L0 * nbytes
+        if interleaved:
+            n_bytes += L0 * open_channels * nbytes
+        n_bytes = -(-n_bytes // 32) * 32
+    return formats, n_bytes
+
+
 _lib = None
 
 
@@ -173,6 +196,9 @@ def lib():
     L.bfhip_nupc_taps.argtypes = [vp]
     L.bfhip_nupc_latency.argtypes = [vp]
     L.bfhip_nupc_set_format.argtypes = [vp, ci, ci, C.POINTER(Format)]
+    L.bfhip_nupc_set_buffer_bytes.argtypes = [vp, ci, C.c_long]
+    L.bfhip_nupc_buffer_bytes.restype = C.c_long
+    L.bfhip_nupc_buffer_bytes.argtypes = [vp, ci]
     L.bfhip_nupc_set_safety_limit.argtypes = [vp, cd]
     L.bfhip_nupc_add_filter.argtypes = [vp, ci, ci, vp, C.c_long, cd, cd]
     L.bfhip_nupc_finalize.argtypes = [vp]
@@ -620,9 +646,22 @@ class Nupc:
     def __del__(self):
         self.close()
 
+    def set_buffer_bytes(self, io, nbytes):
+        """before finalize, after the side's set_format calls: the side's period buffer is nbytes long
+        and every channel is laid out on its own (planes, several devices: period_layout)"""
+        self._chk(lib().bfhip_nupc_set_buffer_bytes(self.h, io, nbytes))
+        if io == IN:
+            self.in_bytes = nbytes
+        else:
+            self.out_bytes = nbytes
+
+    def buffer_bytes(self, io):
+        """after finalize: bytes of one period buffer of the side, whichever way it was declared"""
+        return self._chk(lib().bfhip_nupc_buffer_bytes(self.h, io))
+
     def set_format(self, io, ch, fmt):
-        """every channel of a side must share one frame layout (sample_spacing and bytes; checked at
-        finalize); the period size follows the last format set on the side"""
+        """without set_buffer_bytes every channel of a side must share one frame layout (sample_spacing
+        and bytes; checked at finalize); the period size follows the last format set on the side"""
         self._chk(lib().bfhip_nupc_set_format(self.h, io, ch, C.byref(fmt)))
         nbytes = self.L0 * fmt.sample_spacing * fmt.bytes
         if io == IN:

@@ -186,9 +186,11 @@ sd_fir_period(unsigned char *smem, const NupcSd<T> &sd, int ch, int L0, Src src,
 }
 
 // Input side, one launch per period behind the delay / mute step: one workgroup per input channel
-// converts the slot's L0 raw frames with load_raw -- the conversion the engines' input transform
+// converts the period's L0 raw samples with load_raw -- the conversion the engines' input transform
 // uses -- into the ring of reals the segment engines read ([frame][n_in], interleaved), through the
-// FIR for a channel that has a filter.
+// FIR for a channel that has a filter.  Each channel has its own format, offset and stride in `raw`
+// (a frame slot of the raw ring, or the staged period buffer of a side with planes or several
+// devices); adjacent threads take adjacent samples, so a contiguous plane is read coalesced.
 template <typename T>
 __global__ __launch_bounds__(256) void
 nupc_subdelay_in_kernel(const uint8_t *__restrict__ raw, const DevFormat *__restrict__ fmt, T *__restrict__ real,
@@ -318,11 +320,15 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
 // arguments.  The line's data lives in a device arena per channel:
 //     [n_full_cap whole fragments][rest][short 0][short 1][scratch], `fragp` bytes each
 // (fragp = L0 * bytes rounded up to 16, so change_delay's whole-fragment zero-fill is one range).
+// A channel's sample size, its stride in the raw block and so its fragment pitch are its own: the
+// channels of a side may come from devices with different sample formats and layouts.
 struct NupcDelayJob {
     uint8_t *line;                 // the channel's arena
     unsigned long long zfull;      // change_delay: bytes of whole fragments to zero, from line[0]
     int rest_frag;                 // index of the rest fragment (n_full_cap)
-    int byte_offset;               // the channel's first sample in a raw frame
+    int byte_offset;               // the channel's first sample in the raw block
+    int ss, stride;                // bytes of a sample, bytes from one sample to the next in the raw block
+    unsigned int fragp;            // bytes from one fragment of the arena to the next
     int kind;                      // 0 mute only, 1 whole fragments (update_delay_buffer),
                                    // 2 short (update_delay_short_buffer)
     int muted;
@@ -330,7 +336,8 @@ struct NupcDelayJob {
     int rr;                        // n_rest
     int zrest, zshort;             // change_delay: bytes to zero in the rest / in each short buffer
 };
-constexpr int kDelayJobs = 32;     // jobs per launch (1792 bytes of kernel arguments)
+constexpr int kDelayJobs = 32;     // jobs per launch (2048 bytes of kernel arguments)
+static_assert(sizeof(NupcDelayJob) <= 64, "32 jobs must stay well inside the 4 KB of kernel arguments");
 struct NupcDelayJobs { NupcDelayJob j[kDelayJobs]; };
 
 __device__ __forceinline__ unsigned long long smp_ld(const uint8_t *p, int ss) {
@@ -348,16 +355,16 @@ __device__ __forceinline__ void zero_bytes(uint8_t *p, unsigned long long n) {
     for (unsigned long long i = n16 * 16 + threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
 }
 
-// One workgroup per job, on the raw block `raw` of F frames (frame_bytes apart, ss-byte
+// One workgroup per job, on the raw block `raw` of F frames (the job's stride apart, ss-byte
 // samples).  mute_first: input side (do_mute before update_delay: zeros enter the line); else
 // output side (the delayed block is muted).  Every thread reads and writes only its own samples of
 // the raw block; the exchange between samples goes through the arena's scratch fragment.
 __global__ __launch_bounds__(256) void
-nupc_delay_kernel(const NupcDelayJobs jobs, uint8_t *__restrict__ raw, int F, int ss, int frame_bytes,
-                  unsigned long long fragp, int mute_first) {
+nupc_delay_kernel(const NupcDelayJobs jobs, uint8_t *__restrict__ raw, int F, int mute_first) {
     const NupcDelayJob j = jobs.j[blockIdx.x];
     uint8_t *buf = raw + j.byte_offset;
-    const size_t stride = (size_t)frame_bytes;
+    const int ss = j.ss;
+    const size_t stride = (size_t)j.stride, fragp = (size_t)j.fragp;
     if (j.kind == 0) {                                             // no delay in force: a muted channel
         for (int n = threadIdx.x; n < F; n += blockDim.x) smp_st(buf + n * stride, 0, ss);
         return;
@@ -449,7 +456,7 @@ struct NupcDelay {
                 }
                 cur = 0; curdelay = nd;
             }
-            jb.line = arena; jb.rest_frag = n_full_cap; jb.rr = n_rest;
+            jb.line = arena; jb.rest_frag = n_full_cap; jb.rr = n_rest; jb.fragp = (unsigned int)fragp;
             if (n_full > 0) {
                 jb.kind = 1; jb.cur = cur; jb.last = cur == n_full - 1 ? 0 : cur + 1;
                 if (++cur == n_full) cur = 0;
@@ -542,8 +549,16 @@ struct bfhip_nupc {
     bool background = true;
     int A = 0;                             // accumulator ring length in frames
     void *d_acc = nullptr;                 // [A][n_out] reals
-    uint8_t *d_in = nullptr;               // raw input ring: Lmax frames
-    size_t frame_bytes[2] = {0, 0};        // interleaved raw frame size in / out
+    uint8_t *d_in = nullptr;               // raw input ring: 2 * Lmax frames (not for an input side with a declared buffer)
+    size_t frame_bytes[2] = {0, 0};        // interleaved raw frame size in / out (no meaning on a side with a declared buffer)
+    // bfhip_nupc_set_buffer_bytes: > 0 = the side declared its period buffer, every channel laid out
+    // on its own (planes, several devices).  Such an input side stages the period in d_stage, runs
+    // delay and mute in place there and converts it into d_in_real: per-period planes are not
+    // contiguous across periods, so no raw ring could give segment k its L_k consecutive frames.
+    long buf_bytes[2] = {0, 0};
+    size_t period_bytes[2] = {0, 0};       // bytes of one period buffer in / out, whichever way it was declared
+    uint8_t *d_stage = nullptr;            // [buf_bytes[0]]: its readers are all ordered on the main stream
+    bool in_real = false;                  // the segment engines read d_in_real (fixed at finalize)
     uint8_t *d_rawout = nullptr;
     DevFormat *d_fmt_out = nullptr;
     NupcGain *d_gain = nullptr;            // [n_out]: 1/scale, output gain and its ramp (the emit step advances it)
@@ -690,7 +705,7 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     }
     void *p[] = {n->d_acc, n->d_acc2, n->d_in, n->d_rawout, n->d_fmt_out, n->d_gain, n->d_over, n->d_status, n->d_arrive,
                  n->d_dither_slot, n->d_dither_state, n->d_dither_table, n->d_randmap, n->d_dither_stage,
-                 n->d_sd_bank, n->d_sd_hist[0], n->d_sd_hist[1], n->d_fmt_in, n->d_in_real};
+                 n->d_sd_bank, n->d_sd_hist[0], n->d_sd_hist[1], n->d_fmt_in, n->d_in_real, n->d_stage};
     for (void *q : p) if (q) (void)hipFree(q);
     for (auto &side : n->dl) for (auto &d : side) if (d.arena) (void)hipFree(d.arena);
     if (n->h_status) (void)hipHostFree(n->h_status);
@@ -716,14 +731,29 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
 long bfhip_nupc_taps(const bfhip_nupc *n) { return n ? n->seg.back().off + (long)n->seg.back().L * n->seg.back().N : 0; }
 int bfhip_nupc_latency(const bfhip_nupc *n) { return n ? n->seg[0].L : 0; }
 
-// raw formats of the L0-frame I/O buffers; frames must be interleaved (every channel of a side
-// has the same sample_spacing = frame size in samples), the way dai.c lays out an interleaved
-// device, because segment k reads L_k consecutive frames of the input ring
+// raw formats of the L0-frame I/O buffers.  On a side that does not declare its buffer
+// (bfhip_nupc_set_buffer_bytes) frames must be interleaved (every channel of the side has the same
+// sample_spacing = frame size in samples), the way dai.c lays out one interleaved device, because
+// segment k reads L_k consecutive frames of the raw input ring; on one that does, every channel is
+// laid out on its own
 int bfhip_nupc_set_format(bfhip_nupc *n, int io, int ch, const bfhip_format *f) {
     if (!n || !f || io < 0 || io > 1 || ch < 0 || ch >= (io ? n->n_out : n->n_in)) return nfail(BFHIP_EINVAL, "nupc_set_format: bad argument");
     if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_format after finalize");
     n->fmt[io][ch] = *f;
     return BFHIP_OK;
+}
+
+int bfhip_nupc_set_buffer_bytes(bfhip_nupc *n, int io, long bytes) {
+    if (!n || io < 0 || io > 1 || bytes < 1) return nfail(BFHIP_EINVAL, "nupc_set_buffer_bytes: bad argument");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_buffer_bytes after finalize");
+    n->buf_bytes[io] = bytes;
+    return BFHIP_OK;
+}
+
+long bfhip_nupc_buffer_bytes(const bfhip_nupc *n, int io) {
+    if (!n || io < 0 || io > 1) return nfail(BFHIP_EINVAL, "nupc_buffer_bytes: bad argument");
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_buffer_bytes before finalize");
+    return (long)n->period_bytes[io];
 }
 
 // dither_init for the listed outputs (bfhip_engine_enable_dither's checks; max_samples_per_loop =
@@ -821,6 +851,29 @@ int bfhip_nupc_finalize(bfhip_nupc *n) {
     return r;
 }
 
+// a side that declared its buffer: every channel's L0 samples lie inside it and no byte belongs to
+// two channels (a byte map of the buffer)
+static int nupc_check_layout(const bfhip_nupc *n, int io) {
+    const size_t total = (size_t)n->buf_bytes[io], L0 = (size_t)n->seg[0].L;
+    std::vector<unsigned char> owned(total, 0);
+    for (size_t ch = 0; ch < n->fmt[io].size(); ch++) {
+        const bfhip_format &f = n->fmt[io][ch];
+        const std::string who = std::string("nupc: ") + (io ? "output " : "input ") + std::to_string(ch);
+        if (f.sample_spacing < 1 || f.byte_offset < 0 || f.bytes < 1)
+            return nfail(BFHIP_EINVAL, who + ": sample_spacing must be >= 1, byte_offset >= 0 and bytes >= 1");
+        const size_t stride = (size_t)f.sample_spacing * f.bytes;
+        if ((size_t)f.byte_offset + (L0 - 1) * stride + f.bytes > total)
+            return nfail(BFHIP_EINVAL, who + ": its last sample lies past the side's buffer of " + std::to_string(total) + " bytes");
+        for (size_t t = 0; t < L0; t++)
+            for (int b = 0; b < f.bytes; b++) {
+                unsigned char &o = owned[(size_t)f.byte_offset + t * stride + b];
+                if (o) return nfail(BFHIP_EINVAL, who + ": its samples overlap another channel's in the side's buffer");
+                o = 1;
+            }
+    }
+    return BFHIP_OK;
+}
+
 static int nupc_finalize_impl(bfhip_nupc *n) {
     OWNER(n);
     for (int io = 0; io < 2; io++) {
@@ -852,15 +905,25 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(hipStreamCreateWithPriority(&n->stream, hipStreamNonBlocking, prio_greatest));
     NCHK(hipEventCreateWithFlags(&n->ev_in, hipEventDisableTiming));
     if (const char *bg = getenv("BFHIP_NUPC_BACKGROUND")) n->background = atoi(bg) != 0;
+    const int L0 = n->seg[0].L, Lmax = n->seg.back().L;
     for (int io = 0; io < 2; io++) {
         const int c = io ? n->n_out : n->n_in;
+        if (n->buf_bytes[io]) {
+            // the input side goes through the conversion kernel's argument block (NupcSdVals)
+            if (io == BFHIP_IN && c > kSdChannels)
+                return nfail(BFHIP_EINVAL, "nupc: an input side that declares its buffer can have at most " + std::to_string(kSdChannels) + " channels");
+            { const int r = nupc_check_layout(n, io); if (r < 0) return r; }
+            n->period_bytes[io] = (size_t)n->buf_bytes[io];
+            continue;
+        }
         const int spacing = n->fmt[io][0].sample_spacing, bytes = n->fmt[io][0].bytes;
         for (int ch = 0; ch < c; ch++)
             if (n->fmt[io][ch].sample_spacing != spacing || n->fmt[io][ch].bytes != bytes)
                 return nfail(BFHIP_EINVAL, "nupc: all channels of a side must share one interleaved frame layout");
         n->frame_bytes[io] = (size_t)spacing * bytes;
+        n->period_bytes[io] = (size_t)L0 * n->frame_bytes[io];
     }
-    const int L0 = n->seg[0].L, Lmax = n->seg.back().L;
+    n->in_real = n->sd_use[0] || n->buf_bytes[0];
     long reach = 0;
     for (auto &s : n->seg) reach = std::max(reach, s.off + 2L * s.L);
     int A = 1;
@@ -871,10 +934,16 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     // two periods of the longest segment: its forward transform may still be reading one while
     // the next is being filled
     n->in_frames = 2 * Lmax;
-    NCHK(bfhip_internal_dev_alloc((void **)&n->d_in, (size_t)n->in_frames * n->frame_bytes[0]));
-    NCHK(hipMemset(n->d_in, 0, (size_t)n->in_frames * n->frame_bytes[0]));
-    NCHK(bfhip_internal_dev_alloc((void **)&n->d_rawout, (size_t)L0 * n->frame_bytes[1]));
-    NCHK(hipMemset(n->d_rawout, 0, (size_t)L0 * n->frame_bytes[1]));
+    if (n->buf_bytes[0]) {
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_stage, n->period_bytes[0]));
+        NCHK(hipMemset(n->d_stage, 0, n->period_bytes[0]));
+    } else {
+        NCHK(bfhip_internal_dev_alloc((void **)&n->d_in, (size_t)n->in_frames * n->frame_bytes[0]));
+        NCHK(hipMemset(n->d_in, 0, (size_t)n->in_frames * n->frame_bytes[0]));
+    }
+    // bytes no output channel owns are never written: they stay zero
+    NCHK(bfhip_internal_dev_alloc((void **)&n->d_rawout, n->period_bytes[1]));
+    NCHK(hipMemset(n->d_rawout, 0, n->period_bytes[1]));
     std::vector<DevFormat> df(n->n_out);
     n->ramp.resize(n->n_out);
     std::vector<DevOverflow> ov(n->n_out);
@@ -896,8 +965,8 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     NCHK(bfhip_internal_dev_alloc((void **)&n->d_arrive, sizeof(unsigned int)));
     NCHK(hipMemset(n->d_arrive, 0, sizeof(unsigned int)));
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_status, sizeof(int), hipHostMallocDefault));
-    NCHK(bfhip_internal_pin_alloc((void **)&n->h_in, (size_t)L0 * n->frame_bytes[0], hipHostMallocDefault));
-    NCHK(bfhip_internal_pin_alloc((void **)&n->h_out, (size_t)L0 * n->frame_bytes[1], hipHostMallocDefault));
+    NCHK(bfhip_internal_pin_alloc((void **)&n->h_in, n->period_bytes[0], hipHostMallocDefault));
+    NCHK(bfhip_internal_pin_alloc((void **)&n->h_out, n->period_bytes[1], hipHostMallocDefault));
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_over, (size_t)n->n_out * sizeof(DevOverflow), hipHostMallocDefault));
     *n->h_status = 0;
     NCHK(bfhip_internal_pin_alloc((void **)&n->h_gain, (size_t)n->n_out * sizeof(NupcGain), hipHostMallocDefault));
@@ -919,8 +988,9 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
         NCHK(bfhip_internal_dev_alloc(&n->d_dither_stage, n->dither_ch.size() * L0 * n->rs));
     }
     for (int io = 0; io < 2; io++)
-        for (auto &d : n->dl[io]) {
-            const size_t bytes = d.init(L0, n->fmt[io][0].bytes);     // delay_allocate_buffer
+        for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
+            NupcDelay &d = n->dl[io][ch];
+            const size_t bytes = d.init(L0, n->fmt[io][ch].bytes);    // delay_allocate_buffer, the channel's own sample size
             if (bytes == 0) continue;
             NCHK(bfhip_internal_dev_alloc((void **)&d.arena, bytes));
             NCHK(hipMemset(d.arena, 0, bytes));
@@ -936,11 +1006,11 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
             NCHK(hipMemset(n->d_sd_hist[io], 0, bytes));
         }
     }
-    if (n->sd_use[0]) {
+    if (n->in_real) {
         std::vector<DevFormat> dfi(n->n_in);
         for (int ch = 0; ch < n->n_in; ch++) {
             const bfhip_format &f = n->fmt[0][ch];
-            if (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->frame_bytes[0])
+            if (!n->buf_bytes[0] && (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->frame_bytes[0]))
                 return nfail(BFHIP_EINVAL, "nupc: sub-sample delay on a side with a channel whose samples lie outside the raw frame");
             dfi[ch].isfloat = f.isfloat; dfi[ch].swap = f.swap; dfi[ch].bytes = f.bytes; dfi[ch].sbytes = f.sbytes;
             dfi[ch].sample_spacing = f.sample_spacing; dfi[ch].byte_offset = f.byte_offset; dfi[ch].alt = nullptr;
@@ -959,7 +1029,7 @@ static int nupc_finalize_impl(bfhip_nupc *n) {
     for (auto &s : n->seg) {
         for (int ch = 0; ch < n->n_in; ch++) {
             bfhip_format f = n->fmt[0][ch];
-            if (n->sd_use[0]) {
+            if (n->in_real) {
                 // the ring of converted (and filtered) reals; the format's scale stays where it is
                 // applied today, in the engines' filter scales
                 f.isfloat = 1; f.swap = 0; f.bytes = f.sbytes = n->rs;
@@ -1040,7 +1110,8 @@ int nupc_accumulate(bfhip_nupc *n, const Seg &s, unsigned long long pos, void *a
 // this period's delay / mute step of one side on its raw block; no launch if no channel of the
 // side is muted or has a delay line with work
 int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
-    for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
+    // (a side with a declared buffer had every channel's samples checked against it at finalize)
+    for (size_t ch = 0; ch < n->dl[io].size() && !n->buf_bytes[io]; ch++) {
         const bfhip_format &f = n->fmt[io][ch];
         if ((n->dl[io][ch].arena || n->dl[io][ch].muted) &&
             (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->frame_bytes[io]))
@@ -1051,18 +1122,19 @@ int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
     for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
         NupcDelayJob jb;
         if (!n->dl[io][ch].step(jb)) continue;
-        jb.byte_offset = n->fmt[io][ch].byte_offset;
+        const bfhip_format &f = n->fmt[io][ch];
+        jb.byte_offset = f.byte_offset;
+        jb.ss = f.bytes;
+        jb.stride = f.sample_spacing * f.bytes;
         jobs.push_back(jb);
     }
-    const NupcDelay &d0 = n->dl[io][0];
-    const unsigned long long fragp = ((unsigned long long)n->seg[0].L * d0.ss + 15) / 16 * 16;
     for (size_t first = 0; first < jobs.size(); first += kDelayJobs) {
         const int cnt = (int)std::min(jobs.size() - first, (size_t)kDelayJobs);
         NupcDelayJobs args;
         memset(&args, 0, sizeof(args));
         std::copy(jobs.begin() + first, jobs.begin() + first + cnt, args.j);
-        hipLaunchKernelGGL(nupc_delay_kernel, dim3(cnt), dim3(256), 0, n->stream, args, raw, n->seg[0].L, d0.ss,
-                           (int)n->frame_bytes[io], fragp, io == BFHIP_IN ? 1 : 0);
+        hipLaunchKernelGGL(nupc_delay_kernel, dim3(cnt), dim3(256), 0, n->stream, args, raw, n->seg[0].L,
+                           io == BFHIP_IN ? 1 : 0);
         NCHK(hipGetLastError());
     }
     return BFHIP_OK;
@@ -1072,11 +1144,11 @@ int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
 template <typename T> NupcSd<T> nupc_sd_args(const bfhip_nupc *n, int io) {
     NupcSd<T> a;
     memset(&a, 0, sizeof(a));
+    memset(a.vals.v, -100, sizeof(a.vals.v));                     // no channel has a filter
     if (!n->sd_use[io]) return a;
     a.bank = (const T *)n->d_sd_bank;
     a.hist = (T *)n->d_sd_hist[io];
     a.bs = n->sd_bs; a.flen = n->sd_flen; a.tile = std::min(n->seg[0].L, kSdTile);
-    memset(a.vals.v, -100, sizeof(a.vals.v));
     for (size_t ch = 0; ch < n->sd[io].size(); ch++) a.vals.v[ch] = (signed char)n->sd[io][ch];
     return a;
 }
@@ -1084,8 +1156,9 @@ size_t nupc_sd_smem(const bfhip_nupc *n, int io) {
     return n->sd_use[io] ? nupc_sd_lds(n->sd_bs, n->sd_flen, std::min(n->seg[0].L, kSdTile), n->rs) : 0;
 }
 
-// input side with sub-delay: the slot's raw frames (delayed and muted already) become the reals
-// of the same slot of the ring the segment engines read
+// input side with sub-delay or a declared buffer: the period's raw samples (delayed and muted
+// already; the raw ring's slot, or the stage) become the reals of slot wpos of the ring the segment
+// engines read
 int nupc_subdelay_in(bfhip_nupc *n, const uint8_t *raw_slot, size_t wpos) {
     const int L0 = n->seg[0].L;
     uint8_t *real = n->d_in_real + wpos * (size_t)n->n_in * n->rs;
@@ -1326,13 +1399,16 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     const unsigned long long end = (n->block + 1) * (unsigned long long)L0;       // samples received
     // append to the input ring (segment blocks are aligned: never split by the wrap)
     const size_t wpos = (size_t)((end - L0) % (unsigned long long)n->in_frames);
-    if ((const uint8_t *)rawin_dev != n->d_in + wpos * n->frame_bytes[0])     // block() uploads straight into the slot
-        NCHK(hipMemcpyAsync(n->d_in + wpos * n->frame_bytes[0], rawin_dev, (size_t)L0 * n->frame_bytes[0], hipMemcpyDeviceToDevice, n->stream));
+    // (a side with a declared buffer has no raw ring: the period is staged, and only its reals are kept)
+    uint8_t *slot = n->buf_bytes[0] ? n->d_stage : n->d_in + wpos * n->frame_bytes[0];
+    if ((const uint8_t *)rawin_dev != slot)                                   // block() uploads straight into the slot
+        NCHK(hipMemcpyAsync(slot, rawin_dev, n->period_bytes[0], hipMemcpyDeviceToDevice, n->stream));
     // input delay and mute on the slot, before any segment (or ev_in, which the background
     // segment streams wait on) reads it
-    { const int r = nupc_delay_side(n, BFHIP_IN, n->d_in + wpos * n->frame_bytes[0]); if (r < 0) return r; }
-    // sub-delay on the input side: convert (and filter) the slot once, in front of all segments
-    if (n->sd_use[0]) { const int r = nupc_subdelay_in(n, n->d_in + wpos * n->frame_bytes[0], wpos); if (r < 0) return r; }
+    { const int r = nupc_delay_side(n, BFHIP_IN, slot); if (r < 0) return r; }
+    // sub-delay or a declared buffer on the input side: convert (and filter) the period once, in
+    // front of all segments
+    if (n->in_real) { const int r = nupc_subdelay_in(n, slot, wpos); if (r < 0) return r; }
     if (n->gain_dirty) {
         // output gains set since the last block: this block's first frame is the first of the step
         // or ramp, which starts from the gain of the last emitted frame.  Every record goes up as
@@ -1371,7 +1447,7 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
             if (mode == 2) acc2 = n->ring(1 - n->cur);
             if (need_old) n->old_hi = std::max(n->old_hi, (long long)(pos + s.L));
         }
-        const uint8_t *in = n->sd_use[0] ? n->d_in_real + rpos * (size_t)n->n_in * n->rs : n->d_in + rpos * n->frame_bytes[0];
+        const uint8_t *in = n->in_real ? n->d_in_real + rpos * (size_t)n->n_in * n->rs : n->d_in + rpos * n->frame_bytes[0];
         if (s.delay_steps == 0) {
             { const int r = seg_run(n, s, in, mode); if (r < 0) return r; }
             { const int r = nupc_accumulate(n, s, pos, acc, acc2); if (r < 0) return r; }
@@ -1442,21 +1518,21 @@ int bfhip_nupc_block(bfhip_nupc *n, const void *rawin, void *rawout, bfhip_overf
     // upload straight into this block's slot of the input ring
     const unsigned long long end = (n->block + 1) * (unsigned long long)L0;
     const size_t wpos = (size_t)((end - L0) % (unsigned long long)n->in_frames);
-    uint8_t *slot = n->d_in + wpos * n->frame_bytes[0];
+    uint8_t *slot = n->buf_bytes[0] ? n->d_stage : n->d_in + wpos * n->frame_bytes[0];
     // through pinned staging buffers: copies from pageable memory stall in the runtime every so often
-    memcpy(n->h_in, rawin, (size_t)L0 * n->frame_bytes[0]);
-    NCHK(hipMemcpyAsync(slot, n->h_in, (size_t)L0 * n->frame_bytes[0], hipMemcpyHostToDevice, n->stream));
+    memcpy(n->h_in, rawin, n->period_bytes[0]);
+    NCHK(hipMemcpyAsync(slot, n->h_in, n->period_bytes[0], hipMemcpyHostToDevice, n->stream));
     if (overflow) {
         memcpy(n->h_over, overflow, n->n_out * sizeof(DevOverflow));
         NCHK(hipMemcpyAsync(n->d_over, n->h_over, n->n_out * sizeof(DevOverflow), hipMemcpyHostToDevice, n->stream));
     }
     int r = bfhip_nupc_block_dev(n, slot, n->d_rawout);
     if (r < 0) return r;
-    NCHK(hipMemcpyAsync(n->h_out, n->d_rawout, (size_t)L0 * n->frame_bytes[1], hipMemcpyDeviceToHost, n->stream));
+    NCHK(hipMemcpyAsync(n->h_out, n->d_rawout, n->period_bytes[1], hipMemcpyDeviceToHost, n->stream));
     if (overflow) NCHK(hipMemcpyAsync(n->h_over, n->d_over, n->n_out * sizeof(DevOverflow), hipMemcpyDeviceToHost, n->stream));
     r = bfhip_nupc_sync(n);
     if (r < 0) return r;
-    memcpy(rawout, n->h_out, (size_t)L0 * n->frame_bytes[1]);
+    memcpy(rawout, n->h_out, n->period_bytes[1]);
     if (overflow) memcpy(overflow, n->h_over, n->n_out * sizeof(DevOverflow));
     return r;
 }

@@ -17,8 +17,17 @@
  * the longest period costs about what the common one does (tools/nupc_latency.py).
  *
  * Filters are single-input single-output impulse responses (a crossbar is one call per pair).
- * Raw I/O buffers hold interleaved frames (dai.c's interleaved layout): all channels of a side
- * share sample_spacing and bytes.
+ *
+ * Raw I/O buffers hold one period of seg_length[0] (L0) frames per side, in one of two layouts:
+ *   - Interleaved frames (the default; dai.c's layout of one interleaved device): all channels of
+ *     the side share sample_spacing and bytes, a frame is sample_spacing * bytes bytes and the
+ *     buffer is L0 frames.  The input frames go straight into a raw ring that the segments read.
+ *   - A declared buffer (bfhip_nupc_set_buffer_bytes, per side): every channel has its own
+ *     byte_offset, sample_spacing and sample format -- dai.c's period buffer for any set of devices
+ *     laid back to back, interleaved or not (calc_buffer_format, dai.c:537-576): planes as JACK
+ *     delivers them, two sound cards with different sample widths.  Such an input period is staged
+ *     on the device, delayed and muted in place and converted once into the ring of reals the
+ *     segments read; the results are those of the interleaved path, bit for bit.
  */
 #ifndef BFHIP_NUPC_H
 #define BFHIP_NUPC_H
@@ -37,7 +46,33 @@ bfhip_nupc *bfhip_nupc_create(int device, int realsize, int n_in, int n_out, int
 void bfhip_nupc_destroy(bfhip_nupc *n);
 long bfhip_nupc_taps(const bfhip_nupc *n);        /* taps covered by the schedule */
 int bfhip_nupc_latency(const bfhip_nupc *n);      /* I/O block size in frames = seg_length[0] */
+/* before finalize (BFHIP_ESTATE after): sample format and place of one raw channel in the side's
+   period buffer; sample t (0 <= t < L0) lies at byte_offset + t * sample_spacing * bytes.  On a
+   side that does not declare its buffer all channels must share sample_spacing and bytes (one
+   interleaved frame layout; checked at finalize) and the buffer is L0 * sample_spacing * bytes
+   long.  On a side that does (below) every channel is on its own. */
 int bfhip_nupc_set_format(bfhip_nupc *n, int io, int channel, const bfhip_format *bf);
+/* before finalize (BFHIP_ESTATE after); bytes >= 1, io BFHIP_IN / BFHIP_OUT (BFHIP_EINVAL otherwise,
+   NULL handle included).  Declares side io's period buffer to be `bytes` long with every channel
+   laid out on its own: sample t (0 <= t < L0) of channel c lies at
+   byte_offset_c + t * sample_spacing_c * bytes_c, bytes_c wide -- dai.c's buffer for any set of
+   devices (interleaved or not, one sample format each).  Finalize then checks, per channel and with
+   BFHIP_EINVAL and a message naming it: sample_spacing >= 1, byte_offset >= 0, the last sample
+   inside the buffer, and no byte shared with another channel of the side; there is no alignment
+   rule.  An input side that declares its buffer has at most 256 channels.
+   Every call keeps its documented semantics per channel: block and block_dev, the overflow structs,
+   dither, gains and ramps, switches and cross-fades, integer delay and mute, sub-sample delay.
+   Bytes of the output buffer that no channel owns (like the gap bytes of gapped frames):
+   bfhip_nupc_block returns them as zero, bfhip_nupc_block_dev does not touch them.
+   bfhip_nupc_block_dev never modifies the caller's input buffer on either kind of side.
+   Cost: one copy into the stage and one conversion launch per period on an input side that
+   declares its buffer, nothing on the output side.  A convolver that never
+   calls this allocates, launches and computes exactly as before. */
+int bfhip_nupc_set_buffer_bytes(bfhip_nupc *n, int io, long bytes);
+/* after finalize: bytes of one period buffer of the side, whichever way it was declared
+   (L0 * sample_spacing * bytes for a side that did not opt in); BFHIP_ESTATE before finalize,
+   BFHIP_EINVAL on a NULL handle or bad io */
+long bfhip_nupc_buffer_bytes(const bfhip_nupc *n, int io);
 int bfhip_nupc_set_safety_limit(bfhip_nupc *n, double limit);
 int bfhip_nupc_add_filter(bfhip_nupc *n, int in_channel, int out_channel, const void *taps,
                           long n_taps, double in_scale, double out_scale);
@@ -299,8 +334,10 @@ int bfhip_nupc_reset_overflow(bfhip_nupc *n);
  * once per block call: the output is the reference's at a period of L0 frames.
  * Input side.  A muted input's samples are zeroed on the raw block before its delay line; the
  * zeros enter the line and the line keeps advancing (do_mute, then update_delay).  The delay runs
- * in place on the block in the input ring, so every segment, whatever its length and however
- * late it is launched, reads delayed input.
+ * in place on the block in the input ring (on the staged period of a side that declares its
+ * buffer, in front of the conversion into the ring of reals), so every segment, whatever its
+ * length and however late it is launched, reads delayed input.  Every channel's line is sized
+ * from its own sample width.
  * Output side.  The delay runs on the quantised raw output, after dither, output gain and the
  * cross-fade; the mute comes after the delay (update_delay, then mute).  The overflow structs and
  * status bits count the undelayed, unmuted samples, as real2raw does before dai.c touches the

@@ -10,7 +10,7 @@ uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum]]
-                                  [--dump-output FILE]
+                                  [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
 on both outputs (an integer --out-format is needed; sample rate 48000); --delay gives both
@@ -31,7 +31,10 @@ instead of one).  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
-and untimed periods to FILE (to compare two builds byte for byte)."""
+and untimed periods to FILE (to compare two builds byte for byte).  --layout planar declares both
+sides as one non-interleaved device (a plane per channel, bfhip_nupc_set_buffer_bytes): the input
+period is staged and converted into the ring of reals by one more launch per period; the input
+samples are the interleaved run's, plane by plane."""
 import argparse
 import json
 import os
@@ -59,6 +62,7 @@ def main():
     ap.add_argument("--eq", action="store_true")
     ap.add_argument("--eq-mode", choices=["linear", "minimum"], default="linear")
     ap.add_argument("--dump-output")
+    ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
     L0, steps = a.L0, a.steps
     seg_len, k = [], L0
@@ -70,8 +74,15 @@ def main():
     seg_len.append(8192)
     seg_blk.append(-(-(1048576 - covered) // 8192))
     nu = bf.Nupc(seg_len, seg_blk, 8, 2, 2)
-    nu.set_interleaved(0, "FLOAT64_LE")
-    nu.set_interleaved(1, a.out_format)
+    if a.layout == "planar":
+        for io, name in ((bf.IN, "FLOAT64_LE"), (bf.OUT, a.out_format)):
+            fmts, n_bytes = bf.period_layout(L0, [(name, 2, [0, 1], False)])
+            for c, f in enumerate(fmts):
+                nu.set_format(io, c, f)
+            nu.set_buffer_bytes(io, n_bytes)
+    else:
+        nu.set_interleaved(0, "FLOAT64_LE")
+        nu.set_interleaved(1, a.out_format)
     if a.dither:
         nu.enable_dither([0, 1], 48000)
     if a.delay:
@@ -122,6 +133,8 @@ def main():
     in_flight = []                     # per period: a rewrite was in flight (or made) during it
     dump = []
     x = rng.standard_normal((8, L0, 2)) * 0.1
+    if a.layout == "planar":
+        x = np.ascontiguousarray(x.transpose(0, 2, 1))             # [2][L0]: a plane per channel
     import gc
     gc.disable()                       # the timed loop allocates one small array per period
     ts = []
@@ -214,7 +227,7 @@ def main():
     full = ts[[i for i in range(len(ts)) if (i + 256 + 1) % ratio == 0]]
     print(json.dumps({
         "workload": "configs[4]: 2-in/2-out, %d taps, float64, partitions %s x %s" % (nu.taps, seg_len, seg_blk),
-        "out_format": a.out_format, "dithered_outputs": [0, 1] if a.dither else [],
+        "layout": a.layout, "out_format": a.out_format, "dithered_outputs": [0, 1] if a.dither else [],
         "delayed_outputs": {"maxdelay": 48000, "changes_every_periods": 300, "changes": n_changes} if a.delay else None,
         "subdelay": {"sdf_length": 31, "inputs": [0, 1], "outputs": [0, 1], "changes_every_periods": 300,
                      "changes": n_sd_changes} if a.subdelay else None,
