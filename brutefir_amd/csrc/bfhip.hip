@@ -1,4 +1,4 @@
-// bfhip.hip -- host side of the engine + the C ABI of include/bfhip.h.
+// bfhip.hip -- host side of the engine + the C ABI of include/bfhip.h (the plan builder: plan.hip).
 //
 // What the reference's filter_process() does with host buffers and a chain of convolver_*
 // calls per filter (bfrun.c:1493-2008) is turned into a static device plan here:
@@ -29,19 +29,14 @@
 #include <tuple>
 #include <type_traits>
 
-#include "../../include/bfhip.h"
-#include "alloc.h"
+#include "engine.h"
 #include "coeff_async.h"
 #include "conv_shared.h"
 #include "dither_init.h"
-#include "kernels.h"
 #include "subdelay_filter.h"
 #include "bigfft.h"
 
-using namespace bfhip;
-
-// Every device / pinned allocation of the engines goes through these (alloc.h), so that the tests
-// can make the n-th one fail (bfhip_selftest_fail_alloc) and walk every out-of-memory path there is.
+// what the allocation wrappers of engine.h end in (alloc.h)
 static int g_fail_alloc = 0;           // countdown: the allocation that takes it to zero fails
 static inline bool alloc_injected() { return g_fail_alloc > 0 && --g_fail_alloc == 0; }
 extern "C" hipError_t bfhip_internal_dev_alloc(void **p, size_t bytes) {
@@ -52,13 +47,12 @@ extern "C" hipError_t bfhip_internal_pin_alloc(void **p, size_t bytes, unsigned 
     if (alloc_injected()) { *p = nullptr; return hipErrorOutOfMemory; }
     return hipHostMalloc(p, bytes, flags);
 }
-static inline hipError_t dev_alloc(void **p, size_t bytes) { return bfhip_internal_dev_alloc(p, bytes); }
-template <typename P> static hipError_t dev_alloc(P **p, size_t bytes) { return bfhip_internal_dev_alloc((void **)p, bytes); }
-static inline hipError_t pin_alloc(void **p, size_t bytes, unsigned int flags) { return bfhip_internal_pin_alloc(p, bytes, flags); }
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
+
+BFHIP_HOST_NS {
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -76,467 +70,28 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess)                                                             \
-            return fail(BFHIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                        __FILE__, __LINE__);                                              \
-    } while (0)
-
-int ilog2(int v) {
-    int o = 0;
-    while ((1 << o) < v) o++;
-    return ((1 << o) == v) ? o : -1;
-}
-
-struct Coeff {
-    int n_blocks = 0;
-    void *d_H = nullptr;     // [n_blocks][L] packed spectra
-    // a set the host keeps in (shared) memory in the reference's cbuf layout and that another
-    // process may rewrite at run time (bflogic_eq through bfaccess->convolver_coeffs2cbuf):
-    // where each block lives on the host, and the change-notice generation last uploaded
-    std::vector<const void *> watch_src;
-    std::vector<uint64_t> watch_gen;
-    // BFHIP_COEFF_LAZY: the host blocks are remembered (watch_src) and go to the device the first
-    // time an ACTIVE filter refers to the set -- a filter process of a multi-process host holds the
-    // sets of its own filters, not the whole configuration's (d_H == nullptr until then)
-    bool lazy = false, watched = false;
-};
-
-// Pinned staging for the small per-block tables (N:1 channel jobs, delay-line moves, sub-sample
-// delay jobs) that go to the device with every block: K slots, one per block in flight, so the
-// upload is truly asynchronous and the host copy outlives the call that queued it.
-struct Stage {
-    static constexpr int K = 4;
-    uint8_t *base = nullptr;
-    size_t slot = 0;
-    unsigned int turn = 0;             // (unsigned: a stream of 64-frame blocks passes 2^31 in a month)
-    hipEvent_t done[K] = {nullptr, nullptr, nullptr, nullptr};
-    bool pending[K] = {false, false, false, false};
-
-    hipError_t init(size_t slot_bytes) {
-        slot = (slot_bytes + 63) & ~(size_t)63;
-        hipError_t r = pin_alloc((void **)&base, slot * K, hipHostMallocDefault);
-        for (int i = 0; i < K && r == hipSuccess; i++) r = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
-        return r;
-    }
-    void release() {
-        for (int i = 0; i < K; i++) if (done[i]) { (void)hipEventDestroy(done[i]); done[i] = nullptr; }
-        if (base) { (void)hipHostFree(base); base = nullptr; }
-    }
-    // next slot, free again once the copy queued from it K blocks ago has run
-    hipError_t take(uint8_t **p) {
-        const int i = (int)(turn++ % (unsigned int)K);
-        if (pending[i]) { const hipError_t r = hipEventSynchronize(done[i]); if (r != hipSuccess) return r; pending[i] = false; }
-        *p = base + (size_t)i * slot;
-        return hipSuccess;
-    }
-    // the copies out of the slot handed out last have been queued on st
-    hipError_t queued(hipStream_t st) {
-        const int i = (int)((turn - 1u) % (unsigned int)K);
-        const hipError_t r = hipEventRecord(done[i], st);
-        pending[i] = r == hipSuccess;
-        return r;
-    }
-};
-
-struct Filter {
-    std::vector<int> in_ch, in_f, out_ch;
-    std::vector<double> in_scale, in_fscale, out_scale;
-    int coeff = -1, delayblocks = 0, crossfade = 0;
-    int prevcoeff = -1;
-    // false: another engine (another filter process of the host, bfrun.c:2312-2328) runs this filter.
-    // It still takes part in the PLAN -- groups, entry order, chunk boundaries are those of the whole
-    // configuration, so every output is summed in exactly the order a single engine would use --
-    // but none of its work is launched here and its coefficients are not loaded.
-    bool active = true;
-    int name = -1;                     // the host's own number for the filter (intname); -1: its index here
-};
-
-constexpr int MAX_TIMED = 4096;
-// event pairs of a timed block: T_IN K1 (input transforms), T_MAC K2 (MAC), T_OUT K3 (output pass,
-// everything of it), T_POST the part of the output pass behind the inverse transforms (dither, N:1
-// mix, sub-sample delay), T_LEVELS the per-filter level kernels in front of the MAC (N-way input
-// mixes, cascades, cross-fades)
-enum { T_IN, T_MAC, T_OUT, T_POST, T_LEVELS, EV_PAIRS };
-constexpr int EV_PER_BLOCK = 2 * EV_PAIRS;
-
-// Host mirror of the reference's integer delay buffer (delay.c:29-45, 229-340, 346-411): same
-// state variables, same decisions; the byte moves themselves are emitted as ByteOps that a
-// device kernel executes on buffers in HBM.  Contiguous buffers only (how filter_process() uses
-// it for channels that share a physical channel, bfrun.c:1517-1521, 1948).
-struct DelayLine {
-    int F = 0, ss = 0, maxdelay = 0, curdelay = 0, cur = 0, n_full = 0, n_full_cap = 0, n_rest = 0;
-    uint8_t *arena = nullptr;
-    std::vector<uint8_t *> full;
-    uint8_t *rest = nullptr, *shrt[2] = {nullptr, nullptr}, *tmp = nullptr;
-
-    size_t frag() const { return (size_t)F * ss; }
-
-    bool host = false;                 // self test: arena in host memory, moves executed on the host
-
-    int init(int fragment, int initdelay, int maxd, int sample_size) {
-        F = fragment; ss = sample_size;
-        int delay = maxd <= 0 ? initdelay : maxd;                      // delay.c:357-360
-        if (maxd >= 0 && delay > maxd) delay = initdelay = maxd;
-        if (maxd > 0 && initdelay > maxd) initdelay = maxd;            // (the reference overruns its buffer here)
-        curdelay = initdelay; maxdelay = maxd;
-        n_full_cap = delay > F ? delay / F + 1 : 0;
-        const size_t total = (size_t)(n_full_cap + 4) * frag();
-        if (host) {
-            arena = (uint8_t *)calloc(total, 1);
-            if (!arena) return BFHIP_ENOMEM;
-        } else {
-            if (dev_alloc((void **)&arena, total) != hipSuccess) return BFHIP_ENOMEM;
-            if (hipMemset(arena, 0, total) != hipSuccess) return BFHIP_EHIP;
-        }
-        uint8_t *p = arena;
-        for (int i = 0; i < n_full_cap; i++) { full.push_back(p); p += frag(); }
-        rest = p; p += frag();
-        shrt[0] = p; p += frag();
-        shrt[1] = p; p += frag();
-        tmp = p;
-        if (delay == 0) return BFHIP_OK;
-        if (delay <= F) { n_rest = initdelay; return BFHIP_OK; }       // :365-374
-        n_rest = initdelay % F;
-        n_full = initdelay / F + 1;
-        if (n_full == 1) n_full = 0;
-        return BFHIP_OK;
-    }
-
-    static void op(std::vector<ByteOp> &ops, uint8_t *dst, const uint8_t *src, size_t n) {
-        if (n == 0) return;
-        ByteOp o; o.dst = dst; o.src = src; o.n = (unsigned int)n; o.pad = 0;
-        ops.push_back(o);
-    }
-
-    void retarget(int newdelay, std::vector<ByteOp> &ops) {           // change_delay, :283-318
-        if (newdelay == curdelay || newdelay > maxdelay) return;
-        if (newdelay <= F) {
-            n_rest = newdelay;
-            if (curdelay > F || curdelay < newdelay) {
-                op(ops, shrt[0], nullptr, (size_t)newdelay * ss);
-                op(ops, shrt[1], nullptr, (size_t)newdelay * ss);
-            }
-            n_full = 0; cur = 0; curdelay = newdelay;
-            return;
-        }
-        n_rest = newdelay % F;
-        n_full = newdelay / F + 1;
-        if (curdelay < newdelay) {
-            for (int i = 0; i < n_full; i++) op(ops, full[i], nullptr, frag());
-            if (n_rest != 0) op(ops, rest, nullptr, (size_t)n_rest * ss);
-        }
-        cur = 0; curdelay = newdelay;
-    }
-
-    void update(uint8_t *buf, int delay, std::vector<ByteOp> &ops) {  // delay_update, :320-340
-        retarget(delay, ops);
-        const size_t rr = (size_t)n_rest * ss;
-        if (n_full > 0) {                                              // update_delay_buffer
-            uint8_t *last = cur == n_full - 1 ? full[0] : full[cur + 1];
-            op(ops, full[cur], buf, frag());
-            if (rr != 0) {
-                op(ops, buf, rest, rr);
-                op(ops, rest, last + (frag() - rr), rr);
-            }
-            op(ops, buf + rr, last, frag() - rr);
-            if (++cur == n_full) cur = 0;
-        } else if (n_rest > 0) {                                       // update_delay_short_buffer
-            op(ops, shrt[cur], buf + (frag() - rr), rr);
-            op(ops, tmp, buf, frag() - rr);                            // shift_samples via a
-            op(ops, buf + rr, tmp, frag() - rr);                       // scratch copy
-            cur = !cur;
-            op(ops, buf, shrt[cur], rr);
-        }
-    }
-};
-
-}  // namespace
-
-struct bfhip_engine {
-    int device = 0;
-    pid_t owner = 0;               // the process that created the engine (HIP state does not survive fork())
-    int L = 0, N = 0, rs = 4, log2L = 0;
-    int n_ch[2] = {0, 0};
-    std::vector<bfhip_format> fmt[2];
-    double safety_limit = 0.0;
-    // `powersave:` (bfconf.c:1549-1561): 0 off, >= 1 exact-zero windows, < 1 linear noise floor
-    double powersave = 0.0;
-    int *d_ps_flags = nullptr, *d_ps_live = nullptr;
-    unsigned long long *d_ps_acc = nullptr;    // partition lengths above 8192: [2][n_in] running maxima
-    double *d_ps_scale = nullptr;
-    std::vector<Coeff> coeffs;
-    // Coefficient sets are carved out of a few large slabs instead of one hipMalloc each: the MAC
-    // streams all of them at once (config C: 4096 sets, 8 GiB), and thousands of separate 2 MiB
-    // allocations cost it 5-10 % (one hipMalloc per set: 0.79 - 0.86 of peak box to box, one slab
-    // 0.886).  Where inside the slab a set starts matters as much -- the stream-ordered
-    // copy below takes that out of the host's hands.
-    struct Slab { void *base = nullptr; size_t cap = 0, used = 0; };
-    std::vector<Slab> slabs;
-    bool coeff_arena = true;               // BFHIP_COEFF_ARENA=0: one hipMalloc per set
-    unsigned int skew_state = 12345u;
-    // Stream-ordered copy of the coefficients for uniform crossbar plans (StreamLayout, kernels.h):
-    // every MAC workgroup reads one sequential slice.  Built / refreshed by build_plan.
-    int stream_wanted = 1;                 // BFHIP_COEFF_STREAM: 0 off, 1 from 64 MiB of coefficients up, 2 always
-    StreamLayout hstream = {nullptr, 0, 0, 0};
-    void *d_stream = nullptr;
-    size_t stream_cap = 0;
-    StreamWhere *d_where = nullptr;
-    int *d_which = nullptr;
-    size_t where_cap = 0;
-    std::vector<std::array<const void *, OG>> stream_keys;     // per flat entry: the sets laid out there
-    int stream_geom[5] = {0, 0, 0, 0, 0};                          // entries, E_c, P, n_tc, n_groups
-    bool any_watched = false;
-    unsigned long long watch_seq = 0;       // bfhip_coeff_dirty_sequence() at the last poll
-    unsigned long long watch_lost = 0;      // bfhip_dirty_lost() at the last poll
-    std::vector<Filter> filters;
-    // shard of a configuration (multi-process host): which outputs this engine converts and writes.
-    // -1 = derive at finalize (fed by an active filter, or by no filter at all), 0 / 1 = set by the host
-    std::vector<signed char> out_active_set;
-    std::vector<char> out_active;          // after finalize
-    bool sharded = false;                  // some output belongs to another engine
-    struct OwnedRun { size_t offset, len, stride; };       // bytes: per frame `len` at `offset`, frames `stride` apart
-    std::vector<OwnedRun> owned_runs;      // the raw output samples this engine owns (merged channel runs)
-    std::vector<unsigned char> h_stage;    // host staging for bfhip_engine_block of a sharded engine
-    bool finalized = false, finalize_failed = false, plan_dirty = true;
-    unsigned int blockcounter = 0;
-    // ... which wraps by a multiple of every ring depth (N, and N + 1 when a spare slot exists)
-    // long before 2^32, so that `blockcounter mod depth` never jumps (BlockState, kernels.h)
-    unsigned int wrap_at = 0, wrap_by = 0;
-    unsigned long long blocks_done = 0;      // since creation (procblocks analogue)
-
-    hipStream_t stream = nullptr;      // main stream: per-filter kernels and the crossbar MAC
-    bool own_stream = false;
-    hipStream_t ls = nullptr;          // stream the next launch goes to
-    // How bfhip_engine_block[_dev] schedules a block (BFHIP_MODE_*, choose_mode at finalize):
-    //  - PIPELINED: the input FFT of block t+1 and the inverse FFT / requantiser of block t-1 run on
-    //    their own streams beside the HBM-bound MAC of block t, the way the reference overlaps its
-    //    input, filter and output processes (bfrun.c:2312-2616).  Needs one spare ring slot (R = N + 1).
-    //  - DEFERRED (large crossbars on one stream): the inverse transforms of block t run in ONE launch
-    //    with the forward transforms of block t+1 (io_wave_kernel) -- both are a handful of workgroups
-    //    that would otherwise run back to back, each alone on the chip, in front of and behind the
-    //    millisecond MAC.  The output of a block is therefore written during the NEXT
-    //    bfhip_engine_block_dev call, or by bfhip_engine_sync (which flushes it).
-    //  - PINGPONG (small crossbars with the wave FFT): [K3 of t-2 | K1 of t] in one launch on the side
-    //    stream s_in while the MAC of t-1 runs on the main stream; the MAC of t waits for that launch.
-    //    Two launches and four event calls per block instead of three launches and seven, and the two
-    //    transforms run side by side.  Outputs are owed for two calls.
-    int mode = BFHIP_MODE_SEQUENTIAL;
-    int overlap_mode = -1;             // -1 auto, 0 off, 1 on (bfhip_engine_set_overlap)
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_mac[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    hipEvent_t ev_io[2] = {nullptr, nullptr}, ev_mac3[3] = {nullptr, nullptr, nullptr};
-    int R = 0;                         // depth of the input rings
-    struct Pending {
-        void *Zp = nullptr; size_t chunk_stride = 0; int n_chunks = 0;
-        void *rawout = nullptr; hipEvent_t out_done = nullptr;
-        hipEvent_t mac_done = nullptr;     // ping-pong: the side stream waits for it before the inverse transforms
-    };
-    std::deque<Pending> pendq;         // outputs owed, oldest first (at most output_lag of them)
-
-    // partition lengths above the LDS limit (bigfft.h): global scratch for [transform][L] complex
-    bool big = false;
-    int big_R = 1;                 // L / 8192
-    void *d_big[3] = {nullptr, nullptr, nullptr};   // zin, zmid, zout
-    size_t big_cap = 0;            // transforms the scratch holds
-    void *d_tw13 = nullptr;        // twiddle table of the 8192-point LDS transform
-    // K1 / K3 on the wave FFT (fft_wave.h: L = 1024 .. 8192, default from 4096 up; BFHIP_FFT_WAVE=0/1)
-    bool wave = false;
-    void *d_tww = nullptr;         // its twiddle table
-
-    // device state
-    void *d_tw = nullptr;          // [2L] complex
-    void *d_prev = nullptr;        // [n_in][L] real
-    void *d_ring = nullptr;        // [n_in][N][L] complex
-    DevFormat *d_fmt[2] = {nullptr, nullptr};
-    DevOverflow *d_over = nullptr;
-    int *d_status = nullptr;
-    int *d_status_own = nullptr;   // the engine's allocation while d_status points at a caller's word
-    int *d_bad = nullptr;
-    // partial-sum ring, [n_chunks][n_out_padded][L] complex each: a schedule's block t writes
-    // d_Zp[t % zp_depth(e)]; zp_last is the buffer the last MAC (or paired MAC) wrote
-    void *d_Zp[3] = {nullptr, nullptr, nullptr};
-    int zp_last = 0;
-    size_t zp_bytes = 0;
-    void *d_entries = nullptr;
-    size_t entries_cap = 0;
-    ChunkRange *d_chunks = nullptr;
-    bool zp_is_sum = false;            // chunk 0 of the last block's partial-sum buffer holds the sum over all chunks (launch_sum in place)
-    size_t chunks_cap = 0;
-    uint8_t *d_rawin = nullptr, *d_rawout = nullptr;
-    size_t raw_bytes[2] = {0, 0};
-    void *d_taps = nullptr;
-    size_t taps_cap = 0;
-
-    // filters that need more than the shared-ring fast path (SURVEY A3 N-way mix, A7, A8)
-    std::vector<int> level, owner_index, y_index, sink_index, fade_index;
-    std::vector<char> is_source;
-    std::vector<void *> promoted;      // private ring given to a shared-ring filter at run time
-    int n_levels = 0, n_owners = 0, n_y = 0, n_sinks = 0, n_fadeable = 0;
-    void *d_fring = nullptr;       // [n_owners][N][L] complex: private rings
-    void *d_Y = nullptr;           // [n_y][L] complex: materialised filter outputs
-    void *d_Yold = nullptr;        // [n_fadeable][L] complex: old-coefficient result in a fade block
-    void *d_evalprev = nullptr;    // [n_sinks][L] real: previous valid half (convolve_eval state)
-    void *d_jobs = nullptr;        // fill jobs | mix sources | filter jobs | fade jobs
-    size_t jobs_cap = 0;
-    struct LevelJobs { size_t fill_off = 0; int n_fill = 0; size_t filt_off = 0; int n_filt = 0;
-                       size_t fade_off = 0; int n_fade = 0; };
-    std::vector<LevelJobs> level_jobs;
-    size_t src_off = 0;
-    bool any_fading = false;
-
-    // N:1 virtual -> physical channels (bfconf->virt2phys): fmt[] is indexed by PHYSICAL channel
-    int n_phys[2] = {0, 0};
-    std::vector<int> v2p[2], n_vpp[2], vdelay[2], vmaxdelay[2], vmuted[2];
-    std::vector<DelayLine> vline[2];
-    std::vector<int> vin_list;             // virtual inputs that share a physical one
-    std::vector<std::vector<int>> vout_groups;   // members of every shared physical output
-    uint8_t *d_incopy = nullptr;           // [vin_list.size()][L * 8]
-    void *d_vjobs = nullptr;               // per-block job/op tables (device): input half | output half
-    size_t vjobs_slot = 0;
-    Stage st_vin, st_vout, st_sd[2];       // their pinned staging, one slot per block in flight
-    bool has_vchan = false;
-
-    // sub-sample delay (sdf_length / sdf_beta / per-channel subdelay; delay.c:416-505)
-    int sdf_length = 0, sd_flen = 0, sd_bs = 0;
-    std::vector<int> subdelay[2];          // current value per virtual channel (-100 = undefined)
-    std::vector<int> sd_slot[2];           // filter slot of a channel, -1 = none (fixed at finalize)
-    void *d_sd_bank = nullptr;             // [199][flen] taps, index 99 + subdelay
-    void *d_sd_rest[2] = {nullptr, nullptr};
-    void *d_sdin = nullptr;                // [n filtered inputs][L] reals, what K1 reads
-    void *d_sdjobs[2] = {nullptr, nullptr};
-
-    // HP-TPDF dither (dither.c, dither.h)
-    std::vector<int> dither_channels;      // output channel of each dither slot (virtual, ascending, after finalize)
-    std::vector<int> dither_rank;          // its rank among the dithered PHYSICAL outputs: where its table walk starts
-    std::vector<char> dither_late;         // slot is the head of a shared / sub-sample-filtered output: dithered after the mix
-    std::vector<int8_t> dither_table;
-    int dither_spacing = 0;
-    int *d_dither_ch = nullptr;
-    void *d_dither_state = nullptr;
-    int8_t *d_dither_table = nullptr;
-    void *d_randmap = nullptr;             // 512 entries; centre at +256
-    unsigned char *d_skip_quant = nullptr; // [n_out] 1 = the dither pass writes this channel
-    void *d_timeout = nullptr;             // [n_out][L] time samples for the dither pass
-
-    // plan geometry
-    int n_groups = 0, n_out_padded = 0, n_chunks = 1, n_tiles = 1, mac_threads = 256;
-    int n_entries = 0;
-    bool mac_nt = true;            // non-temporal coefficient loads (BFHIP_MAC_NT=0 turns them off)
-    int mac_unroll = 0;            // 0: rotating three-stage pipeline; 1..4: plain unroll (BFHIP_MAC_UNROLL, tools/tune_mac.py)
-    // wide interleaved sides (>= 128 channels in one uniform frame; BFHIP_WIDE_IO=0/1): the raw frames are
-    // transposed to / from a planar copy by a coalesced pass of their own (transpose_words_kernel)
-    bool wide[2] = {false, false};
-    uint8_t *d_planar[2] = {nullptr, nullptr};     // [n_phys][L] words of the side's sample size
-    unsigned char *d_phys_skip = nullptr;          // [n_phys out] 1 = another engine's channel (shards)
-    // two blocks per pass over the coefficients (bfhip_engine_enable_pairs / bfhip_engine_block_pair_dev)
-    bool pairs = false;
-    unsigned long long n_pair_launches = 0;
-    bool all_dense = false;        // every MAC entry takes the crossbar path
-    // one-to-one plans (every output fed by at most one single-term entry per chunk): mac_diag_kernel,
-    // one workgroup per (chunk, output) walking whole spectra (BFHIP_MAC_DIAG=0 keeps the crossbar kernel)
-    bool mac_diag = false;
-    const int *d_diag_jobs = nullptr;      // [n_chunks * n_out_padded] entry index or -1 (lives behind d_chunks)
-    double alg_bytes_total = 0, alg_bytes_mac = 0;
-    // long-window overlap-save (kernels.h: windows of 4 blocks, partitions of 3 blocks of taps).
-    // lw_struct: decided at finalize (f32, L = 8192, wave transforms, N >= 8, >= 1 GiB of coefficients in
-    // the whole configuration, or BFHIP_LONG_WINDOW=1); then the long transforms run in every block and
-    // keep the history and the long ring current.  lw_active: the plan built last covers its blocks with
-    // the long MAC (a plain uniform crossbar without fades, private rings, powersave or dither); any
-    // other block runs the standard MAC and output pass, which the standard transforms keep exact.
-    bool lw_struct = false, lw_active = false;
-    void *d_hist = nullptr;        // [n_in][R][L] real blocks
-    void *d_lring = nullptr;       // [n_in][R][2L] long window spectra
-    void *d_tw14 = nullptr;        // twiddles of the 2L-point complex transform
-    void *d_lentries = nullptr;
-    size_t lentries_cap = 0;
-    ChunkRange *d_lchunks = nullptr;
-    size_t lchunks_cap = 0;
-    int lw_chunks = 1, lw_P = 0, lw_tiles = 0, lw_Pstd = 0;     // chunks per group, long / standard partitions, bin tiles
-    StreamLayout lstream = {nullptr, 0, 0, 0};
-    void *d_lstream = nullptr;
-    size_t lstream_cap = 0;
-    StreamWhere *d_lwhere = nullptr;
-    int *d_lwhich = nullptr;
-    size_t lwhere_cap = 0;
-    std::vector<std::array<const void *, OG + 1>> lkeys;     // per long entry: its sets and (delay, length)
-    bool zp_long[3] = {false, false, false};                   // d_Zp[i] holds long partial spectra
-    // look-ahead long MAC (kernels.h, mac_la_*): call t computes the tails (partitions >= 1) of one slice
-    // of entries for blocks t+1 .. t+3 into the ahead buffers d_ahead[block mod 4][slice]; the block's own
-    // MAC is then the head pass (partition 0 on top of its three ahead buffers).  la_active: the plan
-    // built last may run it (build_long_layout).  The validity table names, per ahead buffer, the block
-    // (blocks_done when it runs) it was computed for and the epoch; anything that can change a product
-    // already stored bumps the epoch, and a block whose three buffers are not all current runs the full
-    // long MAC instead.
-    bool la_active = false;
-    void *d_ahead = nullptr;       // [4][3][n_out_padded][2L] complex
-    size_t ahead_cap = 0;
-    unsigned long long la_epoch = 1;
-    unsigned long long la_for[4][3] = {};
-    unsigned long long la_at[4][3] = {};       // epoch 0: never written
-    // second tier (kernels.h, la_far_phase): partitions >= 2 of one sixth of the entries for blocks t+1 .. t+6
-    // into d_far[block mod 7][slice]; the tail pass above is then p = 1 alone.  Same epoch, its own table.
-    bool far_active = false;
-    void *d_far = nullptr;         // [7][6][n_out_padded][2L] complex
-    size_t far_cap = 0;
-    unsigned long long far_for[7][LA_FAR] = {};
-    unsigned long long far_at[7][LA_FAR] = {};
-    unsigned long long n_la_head = 0, n_la_full = 0;
-    unsigned long long n_mac_launches = 0;      // MAC kernels launched by do_mac, of every kind
-
-    // real-time mode (bfhip_engine_rt_*): pinned host double buffer, the block's launch
-    // sequence replayed from a HIP graph, completion signalled through pinned memory
-    struct Rt {
-        bool on = false;
-        int flags = 0;
-        void *h_in[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
-        DevOverflow *h_over[2] = {nullptr, nullptr};
-        int *h_status[2] = {nullptr, nullptr};      // [0] status bits, [1] sequence number
-        hipGraphExec_t exec[2] = {nullptr, nullptr};
-        bool valid[2] = {false, false};
-        bool primed = false;                        // one direct block ran since the last plan change
-        hipEvent_t done[2] = {nullptr, nullptr};
-        unsigned long long submitted = 0, waited = 0;
-        unsigned int bs_t = 0;                      // what d_bs->t holds
-        bool bs_synced = false;
-        unsigned long long n_graph = 0, n_direct = 0, n_capture = 0;
-        // what rt_wait last wrote into the caller's overflow array: an entry that differs from it
-        // next time was changed by the HOST (bf_reset_peak, bfrun.c: the CLI's peak reset) and
-        // becomes the device's state for that output
-        std::vector<DevOverflow> last_over;
-        std::vector<unsigned long long> over_from;
-        bool last_valid = false;
-        // BFHIP_RT_OVERLAP: copies of neighbouring periods run on the copy engines beside compute
-        hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-        hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_cmp[2] = {nullptr, nullptr};
-        uint8_t *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
-    } rt;
-    BlockState *d_bs = nullptr;
-    unsigned int *d_rt_arrive = nullptr;
-    BlockState *bs_arg = nullptr;      // non-null while a graph is being captured
-
-    // timing
-    bool timing = false;
-    std::vector<hipEvent_t> ev;    // EV_PER_BLOCK per block: start/stop of the EV_PAIRS stages on their streams
-    int ev_used = 0;
-    int timing_stride = 1;         // time every n-th block (the event records cost ~3 us each)
-    bool timed_now = false;
-    int timed_mask = 0;            // which of the three kernel pairs of the block in progress were recorded
-    unsigned long long timed_for = ~0ull;   // blocks_done the decision above was taken for
-    std::vector<unsigned char> ev_mask;     // [MAX_TIMED] timed_mask of every timed block
-
-    size_t csize() const { return (size_t)2 * rs; }     // bytes per complex
-};
-
-namespace {
-
 int sync_all(bfhip_engine *e) {
     if (e->s_in) HIPCHK(hipStreamSynchronize(e->s_in));
     if (e->stream) HIPCHK(hipStreamSynchronize(e->stream));
     if (e->s_out) HIPCHK(hipStreamSynchronize(e->s_out));
     return BFHIP_OK;
+}
+
+// partial-sum buffers a schedule cycles through: the MAC of block t writes one while the output passes
+// of the blocks before it still read the others (a pair writes two at once)
+int zp_depth(const bfhip_engine *e) {
+    const int d = e->mode == BFHIP_MODE_PINGPONG ? 3 : e->mode == BFHIP_MODE_SEQUENTIAL ? 1 : 2;
+    return e->pairs ? std::max(d, 2) : d;
+}
+
+}  // namespace bfhip_host
+
+namespace {
+
+int ilog2(int v) {
+    int o = 0;
+    while ((1 << o) < v) o++;
+    return ((1 << o) == v) ? o : -1;
 }
 
 // the streams a block's input and output passes go to, and how many calls its output is owed for
@@ -548,12 +103,6 @@ hipStream_t out_stream(const bfhip_engine *e) {
 }
 int output_lag(const bfhip_engine *e) {
     return e->mode == BFHIP_MODE_PINGPONG ? 2 : e->mode == BFHIP_MODE_DEFERRED ? 1 : 0;
-}
-// partial-sum buffers a schedule cycles through: the MAC of block t writes one while the output passes
-// of the blocks before it still read the others (a pair writes two at once)
-int zp_depth(const bfhip_engine *e) {
-    const int d = e->mode == BFHIP_MODE_PINGPONG ? 3 : e->mode == BFHIP_MODE_SEQUENTIAL ? 1 : 2;
-    return e->pairs ? std::max(d, 2) : d;
 }
 
 // ---------------------------------------------------------------- coefficient memory
@@ -629,8 +178,6 @@ void coeff_release(bfhip_engine *e, void *p, size_t bytes) {
         else { DISPATCH_LOG2L(double, FN, __VA_ARGS__) }                    \
     } while (0)
 
-// raise a kernel's dynamic-LDS limit once per (device, kernel, size): the attribute call costs a
-// few microseconds, which is real money in a 35 us block
 inline PowerSave ps_arg(const bfhip_engine *e) {
     PowerSave ps;
     ps.thr = e->d_ps_flags ? e->powersave : 0.0;
@@ -638,19 +185,6 @@ inline PowerSave ps_arg(const bfhip_engine *e) {
     return ps;
 }
 
-template <typename K> hipError_t allow_lds(K kernel, size_t bytes) {
-    static std::mutex mu;
-    static std::set<std::tuple<int, const void *, size_t>> done;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const auto key = std::make_tuple(dev, reinterpret_cast<const void *>(kernel), bytes);
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count(key)) return hipSuccess;
-    const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (r == hipSuccess) done.insert(key);
-    return r;
-}
 
 template <typename T, int LOG2L>
 void launch_fft_in(bfhip_engine *e, const uint8_t *raw, int slot, hipError_t *err) {
@@ -807,7 +341,7 @@ void launch_mac(bfhip_engine *e, void *Zp, hipError_t *err) {
     const int age = block_age(e);
 #define BFHIP_LAUNCH_MAC(NTFLAG, U)                                                                   \
     hipLaunchKernelGGL((mac_xbar_kernel<T, NTFLAG, U>), dim3(grid), dim3(e->mac_threads), 0, e->ls,      \
-                       (const MacEntry<T> *)e->d_entries, (const ChunkRange *)e->d_chunks,               \
+                       (const MacEntry<T> *)e->b_entries.p, (const ChunkRange *)e->b_chunks.p,               \
                        (c2<T> *)Zp, e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc,               \
                        e->blockcounter, age, (const BlockState *)e->bs_arg,                              \
                        (NTFLAG && U == 0) ? e->hstream : StreamLayout{nullptr, 0, 0, 0})
@@ -826,7 +360,7 @@ void launch_mac(bfhip_engine *e, void *Zp, hipError_t *err) {
         const int tiles = all_tiles / tsplit;
 #define BFHIP_LAUNCH_DIAG(NTFLAG, TL)                                                                                  \
         hipLaunchKernelGGL((mac_diag_kernel<T, NTFLAG, TL>), dim3(n_jobs * tsplit), dim3(256), 0, e->ls,               \
-                           (const MacEntry<T> *)e->d_entries, e->d_diag_jobs, (c2<T> *)Zp, e->L, e->n_out_padded,      \
+                           (const MacEntry<T> *)e->b_entries.p, e->d_diag_jobs, (c2<T> *)Zp, e->L, e->n_out_padded,      \
                            e->blockcounter, age, (const BlockState *)e->bs_arg, tsplit)
 #define BFHIP_DIAG_TILES(NTFLAG)                                              \
         switch (tiles) {                                                      \
@@ -858,7 +392,7 @@ void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
     const int n_tc = e->n_tiles * e->n_chunks;
     e->zp_is_sum = false;
     hipLaunchKernelGGL((mac_xbar2_kernel<T, true>), dim3(mac_grid(n_tc, e->n_groups)), dim3(e->mac_threads), 0, e->ls,
-                       (const MacEntry<T> *)e->d_entries, (const ChunkRange *)e->d_chunks, (c2<T> *)Zp0, (c2<T> *)Zp1,
+                       (const MacEntry<T> *)e->b_entries.p, (const ChunkRange *)e->b_chunks.p, (c2<T> *)Zp0, (c2<T> *)Zp1,
                        e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc, e->blockcounter, e->hstream);
     *err = hipGetLastError();
 }
@@ -867,7 +401,7 @@ void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
 void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
     const int n_tc = e->lw_tiles * e->lw_chunks;
     hipLaunchKernelGGL((mac_xbar_kernel<float, true, 0, 3>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,
-                       (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,
+                       (const MacEntry<float> *)e->b_lentries.p, (const ChunkRange *)e->b_lchunks.p, (c2<float> *)Zp,
                        2 * e->L, e->n_out_padded, e->n_groups, e->lw_chunks, n_tc, e->blockcounter, block_age(e),
                        (const BlockState *)e->bs_arg, e->lstream);
     *err = hipGetLastError();
@@ -876,19 +410,19 @@ void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
 // the look-ahead passes (kernels.h): ahead buffer of (block mod 4, slice)
 c2<float> *la_buffer(bfhip_engine *e, unsigned long long block, int slice) {
     const size_t one = (size_t)e->n_out_padded * 2 * e->L;
-    return (c2<float> *)e->d_ahead + ((size_t)(block & 3ull) * 3 + (size_t)slice) * one;
+    return (c2<float> *)e->b_ahead.p + ((size_t)(block & 3ull) * 3 + (size_t)slice) * one;
 }
 // head: the head pass of this block (its three ahead buffers are current) and the tail pass of this call's slice
 // in one launch; else the tail pass alone, behind a full long MAC
 c2<float> *far_buffer(bfhip_engine *e, unsigned long long block, int slice) {
     const size_t one = (size_t)e->n_out_padded * 2 * e->L;
-    return (c2<float> *)e->d_far + ((size_t)(block % 7ull) * LA_FAR + (size_t)slice) * one;
+    return (c2<float> *)e->b_far.p + ((size_t)(block % 7ull) * LA_FAR + (size_t)slice) * one;
 }
 void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
     const int n_tc = e->lw_tiles;
     const unsigned long long T = e->blocks_done;
     const int slice = (int)(T % 3ull);
-    const bool two = e->far_active && e->d_far != nullptr;
+    const bool two = e->far_active && e->b_far.p != nullptr;
     LaFar<float> far = {};
     if (two) {
         far.slice = (int)(T % (unsigned long long)LA_FAR);
@@ -900,7 +434,7 @@ void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
     }
 #define BFHIP_LAUNCH_LA(PHASES)                                                                                        \
     hipLaunchKernelGGL((mac_la_kernel<float, PHASES>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,         \
-                       (const MacEntry<float> *)e->d_lentries, (const ChunkRange *)e->d_lchunks, (c2<float> *)Zp,      \
+                       (const MacEntry<float> *)e->b_lentries.p, (const ChunkRange *)e->b_lchunks.p, (c2<float> *)Zp,      \
                        (const c2<float> *)la_buffer(e, T, 0), (const c2<float> *)la_buffer(e, T, 1),                   \
                        (const c2<float> *)la_buffer(e, T, 2),                                                          \
                        la_buffer(e, T + 1, slice), la_buffer(e, T + 2, slice), la_buffer(e, T + 3, slice),             \
@@ -922,34 +456,39 @@ void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
             e->far_at[(T + k) % 7ull][far.slice] = e->la_epoch;
         }
 }
+}  // namespace
+
+BFHIP_HOST_NS {
 // No block has been processed (or prewarm has just declared the zero-initialised rings N blocks of
 // silence): every window the tails of the next three blocks read is silence, so their ahead buffers
 // are zeros.  Store that instead of running three full MACs first.
 int la_prime(bfhip_engine *e) {
-    if (!e->la_active || e->d_ahead == nullptr) return BFHIP_OK;
-    HIPCHK(hipMemsetAsync(e->d_ahead, 0, e->ahead_cap, e->stream));
+    if (!e->la_active || e->b_ahead.p == nullptr) return BFHIP_OK;
+    HIPCHK(hipMemsetAsync(e->b_ahead.p, 0, e->b_ahead.cap, e->stream));
     for (unsigned long long T = e->blocks_done; T < e->blocks_done + 3; T++)
         for (int j = 0; j < 3; j++) { e->la_for[T & 3ull][j] = T; e->la_at[T & 3ull][j] = e->la_epoch; }
-    if (!e->far_active || e->d_far == nullptr) return BFHIP_OK;
+    if (!e->far_active || e->b_far.p == nullptr) return BFHIP_OK;
     // the far tails of the next six blocks read silence alone as well
-    HIPCHK(hipMemsetAsync(e->d_far, 0, e->far_cap, e->stream));
+    HIPCHK(hipMemsetAsync(e->b_far.p, 0, e->b_far.cap, e->stream));
     for (unsigned long long T = e->blocks_done; T < e->blocks_done + LA_FAR; T++)
         for (int j = 0; j < LA_FAR; j++) { e->far_for[T % 7ull][j] = T; e->far_at[T % 7ull][j] = e->la_epoch; }
     return BFHIP_OK;
 }
+}  // namespace bfhip_host
+
+namespace {
 // are the three ahead buffers of the block about to run current?
 bool la_block_valid(const bfhip_engine *e) {
     const unsigned long long T = e->blocks_done;
     for (int j = 0; j < 3; j++)
         if (e->la_for[T & 3ull][j] != T || e->la_at[T & 3ull][j] != e->la_epoch) return false;
-    if (e->far_active && e->d_far != nullptr)
+    if (e->far_active && e->b_far.p != nullptr)
         for (int j = 0; j < LA_FAR; j++)
             if (e->far_for[T % 7ull][j] != T || e->far_at[T % 7ull][j] != e->la_epoch) return false;
     return true;
 }
 
 // [long K3 of `count` outputs from the long partial sums Zp | long K1 of this block's inputs (inputs)]
-constexpr int LW_LOG2 = 14;        // the 4B-point real transform of B = 8192: 2^14 complex points
 void launch_io_long(bfhip_engine *e, const void *Zp, int count, uint8_t *rawout, bool inputs, hipError_t *err) {
     constexpr int NT = fft_threads<float>(LW_LOG2);
     const int n_in = inputs ? e->n_ch[0] : 0;
@@ -994,7 +533,7 @@ void launch_levels(bfhip_engine *e, hipError_t *err) {
     auto kf = ring_fill_kernel<T, LOG2L>;
     auto kx = crossfade_kernel<T, LOG2L>;
     const int age = block_age(e);
-    const unsigned char *base = (const unsigned char *)e->d_jobs;
+    const unsigned char *base = (const unsigned char *)e->b_jobs.p;
     const int V = 16 / (int)sizeof(c2<T>);
     const int threads = e->mac_threads;
     const int tiles = (e->L + threads * V - 1) / (threads * V);
@@ -1027,20 +566,25 @@ void launch_levels(bfhip_engine *e, hipError_t *err) {
 int big_reserve(bfhip_engine *e, size_t n_tr) {
     if (n_tr <= e->big_cap) return BFHIP_OK;
     { int r = sync_all(e); if (r != BFHIP_OK) return r; }
-    for (int i = 0; i < 3; i++) {
-        if (e->d_big[i]) (void)hipFree(e->d_big[i]);
-        e->d_big[i] = nullptr;
-        HIPCHK(dev_alloc(&e->d_big[i], n_tr * (size_t)e->L * e->csize()));
-    }
+    for (DevBuf &b : e->b_big) HIPCHK(b.grow(n_tr * (size_t)e->L * e->csize()));
     e->big_cap = n_tr;
+    return BFHIP_OK;
+}
+
+// the staging buffer for taps and processed blocks on their way to or from a set: `bytes` of it, and
+// nothing on the device still reading the one it replaces
+int taps_reserve(bfhip_engine *e, size_t bytes) {
+    if (bytes <= e->b_taps.cap) return BFHIP_OK;
+    if (e->b_taps.p) { const int r = sync_all(e); if (r != BFHIP_OK) return r; }
+    HIPCHK(e->b_taps.grow(bytes));
     return BFHIP_OK;
 }
 
 // zin -> zout: complex FFT of L points for n_tr transforms on `st`
 template <typename T>
 void big_fft(bfhip_engine *e, int n_tr, bool inv, hipStream_t st, hipError_t *err) {
-    const c2<T> *zin = (const c2<T> *)e->d_big[0];
-    c2<T> *zmid = (c2<T> *)e->d_big[1], *zout = (c2<T> *)e->d_big[2];
+    const c2<T> *zin = (const c2<T> *)e->b_big[0].p;
+    c2<T> *zmid = (c2<T> *)e->b_big[1].p, *zout = (c2<T> *)e->b_big[2].p;
     const c2<T> *tw13 = (const c2<T> *)e->d_tw13, *twL = (const c2<T> *)e->d_tw;
     *err = inv ? big_fft_run<T, true>(zin, zmid, zout, e->log2L, n_tr, tw13, twL, st)
                : big_fft_run<T, false>(zin, zmid, zout, e->log2L, n_tr, tw13, twL, st);
@@ -1054,11 +598,11 @@ void launch_fft_in_big(bfhip_engine *e, const uint8_t *raw, int slot, hipError_t
     const int parity = (int)(e->blocks_done & 1);
     const bool ps_on = e->d_ps_flags != nullptr;
     hipLaunchKernelGGL(big_in_pre<T>, big_grid_half(e, n), dim3(256), 0, e->ls, raw, e->d_fmt[0], (T *)e->d_prev,
-                       (c2<T> *)e->d_big[0], e->L, ps_on ? e->d_ps_acc : (unsigned long long *)nullptr, n, parity,
+                       (c2<T> *)e->b_big[0].p, e->L, ps_on ? e->d_ps_acc : (unsigned long long *)nullptr, n, parity,
                        e->powersave >= 1.0 ? 1 : 0);
     big_fft<T>(e, n, false, e->ls, err);
     if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n), dim3(256), 0, e->ls, (const c2<T> *)e->d_big[2],
+    hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n), dim3(256), 0, e->ls, (const c2<T> *)e->b_big[2].p,
                        (c2<T> *)e->d_ring + (size_t)slot * e->L, (size_t)e->R * e->L, (const c2<T> *)e->d_tw, e->L, (T)1);
     if (ps_on)
         hipLaunchKernelGGL(big_ps_finish<T>, dim3((unsigned)(e->L / 256), (unsigned)n), dim3(256), 0, e->ls,
@@ -1072,10 +616,10 @@ void launch_coeff_prep_big(bfhip_engine *e, const void *taps, int n_taps, double
     hipStream_t keep = e->ls;
     e->ls = e->stream;
     hipLaunchKernelGGL(big_coeff_pre<T>, big_grid_half(e, n_blocks), dim3(256), 0, e->stream, (const T *)taps, n_taps,
-                       (T)scale, (c2<T> *)e->d_big[0], e->L, e->d_bad);
+                       (T)scale, (c2<T> *)e->b_big[0].p, e->L, e->d_bad);
     big_fft<T>(e, n_blocks, false, e->stream, err);
     if (*err == hipSuccess) {
-        hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n_blocks), dim3(256), 0, e->stream, (const c2<T> *)e->d_big[2],
+        hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n_blocks), dim3(256), 0, e->stream, (const c2<T> *)e->b_big[2].p,
                            (c2<T> *)H, (size_t)e->L, (const c2<T> *)e->d_tw, e->L, (T)1.0 / (T)(2 * e->L));
         *err = hipGetLastError();
     }
@@ -1086,10 +630,10 @@ template <typename T>
 void launch_ifft_out_big(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks,
                          int first, int count, uint8_t *raw, hipError_t *err) {
     hipLaunchKernelGGL(big_out_pre<T>, big_grid_half(e, count), dim3(256), 0, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, (c2<T> *)e->d_big[0], (const c2<T> *)e->d_tw, e->L);
+                       n_chunks, (c2<T> *)e->b_big[0].p, (const c2<T> *)e->d_tw, e->L);
     big_fft<T>(e, count, true, e->ls, err);
     if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(big_out_post<T>, dim3(count), dim3(1024), 0, e->ls, (const c2<T> *)e->d_big[2], first, e->d_fmt[1],
+    hipLaunchKernelGGL(big_out_post<T>, dim3(count), dim3(1024), 0, e->ls, (const c2<T> *)e->b_big[2].p, first, e->d_fmt[1],
                        e->d_over, (const unsigned char *)e->d_skip_quant, raw,
                        e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr, e->L, e->safety_limit,
                        e->d_status);
@@ -1099,7 +643,7 @@ void launch_ifft_out_big(bfhip_engine *e, const void *Zp, size_t chunk_stride, i
 template <typename T>
 void launch_levels_big(bfhip_engine *e, hipError_t *err) {
     const int age = block_age(e);
-    const unsigned char *base = (const unsigned char *)e->d_jobs;
+    const unsigned char *base = (const unsigned char *)e->b_jobs.p;
     const int V = 16 / (int)sizeof(c2<T>);
     const int threads = e->mac_threads;
     const int tiles = (e->L + threads * V - 1) / (threads * V);
@@ -1109,15 +653,15 @@ void launch_levels_big(bfhip_engine *e, hipError_t *err) {
             const FillJob<T> *jobs = (const FillJob<T> *)(base + lj.fill_off);
             const MixSrc<T> *src = (const MixSrc<T> *)(base + e->src_off);
             hipLaunchKernelGGL(big_fill_pre<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs, src,
-                               (c2<T> *)e->d_big[0], twL, e->L);
+                               (c2<T> *)e->b_big[0].p, twL, e->L);
             big_fft<T>(e, lj.n_fill, true, e->ls, err);
             if (*err != hipSuccess) return;
             hipLaunchKernelGGL(big_fill_slide<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs,
-                               (const c2<T> *)e->d_big[2], (c2<T> *)e->d_big[0], e->L);
+                               (const c2<T> *)e->b_big[2].p, (c2<T> *)e->b_big[0].p, e->L);
             big_fft<T>(e, lj.n_fill, false, e->ls, err);
             if (*err != hipSuccess) return;
             hipLaunchKernelGGL(big_fill_post<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs, src,
-                               (const c2<T> *)e->d_big[2], twL, e->N, e->blockcounter, e->L, (const BlockState *)e->bs_arg);
+                               (const c2<T> *)e->b_big[2].p, twL, e->N, e->blockcounter, e->L, (const BlockState *)e->bs_arg);
         }
         if (lj.n_filt > 0) {
             hipLaunchKernelGGL(mac_filter_kernel<T>, dim3(tiles, lj.n_filt), dim3(threads), 0, e->ls,
@@ -1127,15 +671,15 @@ void launch_levels_big(bfhip_engine *e, hipError_t *err) {
         if (lj.n_fade > 0) {
             const FadeJob<T> *jobs = (const FadeJob<T> *)(base + lj.fade_off);
             hipLaunchKernelGGL(big_fade_pre<T>, big_grid_half(e, 2 * lj.n_fade), dim3(256), 0, e->ls, jobs,
-                               (c2<T> *)e->d_big[0], twL, e->L);
+                               (c2<T> *)e->b_big[0].p, twL, e->L);
             big_fft<T>(e, 2 * lj.n_fade, true, e->ls, err);
             if (*err != hipSuccess) return;
             hipLaunchKernelGGL(big_fade_mix<T>, dim3((unsigned)(e->L / 256), (unsigned)lj.n_fade), dim3(256), 0, e->ls,
-                               (const c2<T> *)e->d_big[2], (c2<T> *)e->d_big[0], e->L);
+                               (const c2<T> *)e->b_big[2].p, (c2<T> *)e->b_big[0].p, e->L);
             big_fft<T>(e, lj.n_fade, false, e->ls, err);
             if (*err != hipSuccess) return;
             hipLaunchKernelGGL(big_fade_post<T>, big_grid_half(e, lj.n_fade), dim3(256), 0, e->ls, jobs,
-                               (const c2<T> *)e->d_big[2], twL, e->L);
+                               (const c2<T> *)e->b_big[2].p, twL, e->L);
         }
         if ((*err = hipGetLastError()) != hipSuccess) return;
     }
@@ -1145,813 +689,6 @@ void launch_levels_big(bfhip_engine *e, hipError_t *err) {
     do {                                                                    \
         if (e->rs == 4) FN<float>(__VA_ARGS__); else FN<double>(__VA_ARGS__); \
     } while (0)
-
-// ---------------------------------------------------------------- plan
-
-int clamp_delay(const bfhip_engine *e, int d) {          // bfrun.c:1579-1584
-    if (d < 0) return 0;
-    if (d > e->N - 1) return e->N - 1;
-    return d;
-}
-
-int cblocks_of(const bfhip_engine *e, int coeff, int delay) {   // bfrun.c:1585-1591
-    if (coeff < 0 || e->coeffs[coeff].n_blocks > e->N - delay) return e->N - delay;
-    return e->coeffs[coeff].n_blocks;
-}
-
-// (Re)build the stream-ordered coefficient copy for the plan just uploaded, if the plan is a
-// uniform crossbar: every entry OG coefficient terms of the same length, no split entries, every
-// chunk the same number of entries, no idle blocks in the grid.  Entries whose OG sets did not
-// change since the last build are left alone (scale changes rebuild the plan, not the data).
-const void *const STREAM_KEY_STALE = (const void *)(uintptr_t)1;     // never a set's address
-void *const PROMOTED_ELSEWHERE = (void *)(uintptr_t)1;               // promoted[] of an inactive filter: no ring here
-int coeff_make_resident(bfhip_engine *e, int ci);
-
-// long partitions [p_first, p_first + n_p) of the long entries listed in d_lwhich[0 .. n_which)
-int derive_long(bfhip_engine *e, int p_first, int n_p, int n_which) {
-    const size_t lds = lds_fft_bytes(LW_LOG2, sizeof(c2<float>));
-    auto k = coeff_long_kernel<float, LW_LOG2>;
-    HIPCHK(allow_lds(k, lds));
-    hipLaunchKernelGGL(k, dim3((unsigned)n_p, (unsigned)OG, (unsigned)n_which), dim3(fft_threads<float>(LW_LOG2)), lds,
-                       e->stream, (const MacEntry<float> *)e->d_lentries, (const StreamWhere *)e->d_lwhere,
-                       (const int *)e->d_lwhich, p_first, e->lw_Pstd, e->N, e->n_groups, e->lw_chunks, e->lstream,
-                       (const c2<float> *)e->d_tw, (const c2<float> *)e->d_tw14);
-    HIPCHK(hipGetLastError());
-    return sync_all(e);
-}
-
-// standard partition `block` of set H changed in place: long partition block / 3 of every long entry
-// that uses H (or, with no long plan in force now, forget that those entries hold H)
-int long_refresh_block(bfhip_engine *e, const void *H, int block) {
-    e->la_epoch++;                 // products of the rewritten partition may be stored ahead
-    if (e->lkeys.empty()) return BFHIP_OK;
-    std::vector<int> hit;
-    for (size_t i = 0; i < e->lkeys.size(); i++)
-        for (int j = 0; j < OG; j++) if (e->lkeys[i][j] == H) { hit.push_back((int)i); break; }
-    if (hit.empty()) return BFHIP_OK;
-    if (!e->lw_active || e->plan_dirty || block / 3 >= e->lw_P) {
-        for (int i : hit)
-            for (int j = 0; j < OG; j++) if (e->lkeys[i][j] == H) e->lkeys[i][j] = STREAM_KEY_STALE;
-        return BFHIP_OK;
-    }
-    { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    HIPCHK(hipMemcpy(e->d_lwhich, hit.data(), hit.size() * sizeof(int), hipMemcpyHostToDevice));
-    return derive_long(e, block / 3, 1, (int)hit.size());
-}
-
-template <typename T>
-int build_stream_layout(bfhip_engine *e, const std::vector<MacEntry<T>> &flat, const std::vector<ChunkRange> &chunks,
-                        int S, double bytes_H) {
-    e->hstream = StreamLayout{nullptr, 0, 0, 0};
-    if (!e->stream_wanted || !e->all_dense || flat.empty()) return BFHIP_OK;
-    if (e->stream_wanted == 1 && bytes_H < 64.0 * 1048576.0) return BFHIP_OK;      // cache resident anyway
-    const int n_tc = e->n_tiles * S;
-    if (n_tc % 8 != 0 || e->mac_threads != 256 || !e->mac_nt || e->mac_unroll != 0) return BFHIP_OK;
-    const int P = flat[0].maxP, E_c = chunks[0].end - chunks[0].begin;
-    for (auto &cr : chunks) if (cr.end - cr.begin != E_c) return BFHIP_OK;
-    for (auto &en : flat) if (en.dense != 1 || en.p0 != 0 || en.maxP != P) return BFHIP_OK;
-    if (E_c < 1 || P < 1) return BFHIP_OK;
-    const unsigned int chunk = 256u * 16u;
-    const unsigned long long entry_bytes = (unsigned long long)P * OG * chunk;
-    const unsigned long long slice = (unsigned long long)E_c * entry_bytes;
-    if (entry_bytes >= (1ull << 31) || slice >= (1ull << 32)) return BFHIP_OK;       // 32-bit offsets inside a slice
-    const unsigned long long grid = (unsigned long long)n_tc * e->n_groups;
-    const size_t total = (size_t)(grid * slice);
-    const int geom[5] = {(int)flat.size(), E_c, P, n_tc, e->n_groups};
-    const bool same_geom = e->d_stream != nullptr && memcmp(geom, e->stream_geom, sizeof(geom)) == 0;
-    if (!same_geom) {
-        if (total > e->stream_cap) {
-            if (e->d_stream) (void)hipFree(e->d_stream);
-            e->d_stream = nullptr; e->stream_cap = 0;
-            if (dev_alloc(&e->d_stream, total) != hipSuccess) {
-                (void)hipGetLastError();
-                return BFHIP_OK;                 // no room for the second copy: the set-major path still works
-            }
-            e->stream_cap = total;
-        }
-        e->stream_keys.clear();
-        memcpy(e->stream_geom, geom, sizeof(geom));
-    }
-    // which entries hold other sets than last time?
-    std::vector<int> changed;
-    std::vector<StreamWhere> where(flat.size());
-    e->stream_keys.resize(flat.size(), std::array<const void *, OG>{});
-    for (int g = 0; g < e->n_groups; g++) {
-        for (int c = 0; c < S; c++) {
-            const ChunkRange cr = chunks[(size_t)g * S + c];
-            for (int q = 0; q < E_c; q++) {
-                const int idx = cr.begin + q;
-                where[idx] = StreamWhere{g, c, q, 0};
-                std::array<const void *, OG> key;
-                for (int j = 0; j < OG; j++) key[j] = flat[idx].term[j].H;
-                if (key != e->stream_keys[idx]) { changed.push_back(idx); e->stream_keys[idx] = key; }
-            }
-        }
-    }
-    StreamLayout sl;
-    sl.base = (const unsigned char *)e->d_stream; sl.slice = slice; sl.entry_bytes = (unsigned int)entry_bytes; sl.chunk = chunk;
-    if (!changed.empty()) {
-        const size_t wb = where.size() * sizeof(StreamWhere), cb = changed.size() * sizeof(int);
-        if (wb + cb > e->where_cap) {
-            if (e->d_where) (void)hipFree(e->d_where);
-            e->d_where = nullptr;
-            HIPCHK(dev_alloc((void **)&e->d_where, wb + flat.size() * sizeof(int)));
-            e->where_cap = wb + flat.size() * sizeof(int);
-        }
-        e->d_which = (int *)((unsigned char *)e->d_where + wb);
-        HIPCHK(hipMemcpy(e->d_where, where.data(), wb, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->d_which, changed.data(), cb, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(stream_relayout_kernel<T>, dim3((unsigned)P, (unsigned)e->n_tiles, (unsigned)changed.size()), dim3(256), 0,
-                           e->stream, (const MacEntry<T> *)e->d_entries, (const StreamWhere *)e->d_where, (const int *)e->d_which,
-                           0, e->L, e->n_groups, S, sl);
-        HIPCHK(hipGetLastError());
-        { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    }
-    e->hstream = sl;
-    return BFHIP_OK;
-}
-
-// one partition of a coefficient set changed in place (update_coeff_block, refresh of a watched
-// set): bring the stream-ordered copy up to date
-template <typename T>
-int stream_refresh_block(bfhip_engine *e, const void *H, int block) {
-    if constexpr (std::is_same<T, float>::value) {
-        const int r = long_refresh_block(e, H, block);
-        if (r != BFHIP_OK) return r;
-    }
-    if (e->hstream.base == nullptr || e->plan_dirty) {
-        // no copy now (the plan is about to be rebuilt, or this block runs without the stream-ordered
-        // copy: a cross-fade block).  The rebuild compares entries by their set POINTERS, which an
-        // in-place rewrite does not change: forget that these entries hold H, so that the next
-        // build_stream_layout lays them out again from the new data.
-        for (auto &k : e->stream_keys)
-            for (int j = 0; j < OG; j++) if (k[j] == H) k[j] = STREAM_KEY_STALE;
-        return BFHIP_OK;
-    }
-    std::vector<int> hit;
-    for (size_t i = 0; i < e->stream_keys.size(); i++)
-        for (int j = 0; j < OG; j++) if (e->stream_keys[i][j] == H) { hit.push_back((int)i); break; }
-    if (hit.empty()) return BFHIP_OK;
-    const int P = e->stream_geom[2];
-    if (block >= P) return BFHIP_OK;
-    HIPCHK(hipMemcpy(e->d_which, hit.data(), hit.size() * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(stream_relayout_kernel<T>, dim3(1u, (unsigned)e->n_tiles, (unsigned)hit.size()), dim3(256), 0, e->stream,
-                       (const MacEntry<T> *)e->d_entries, (const StreamWhere *)e->d_where, (const int *)e->d_which,
-                       block, e->L, e->n_groups, e->n_chunks, e->hstream);
-    HIPCHK(hipGetLastError());
-    return sync_all(e);
-}
-
-// The long-window plan for a plain uniform crossbar: the standard plan's entries with the long rings
-// (ring step 3 in the MAC), chunks of lw_chunks per group, and the long coefficient partitions derived
-// from the sets' standard spectra straight into their own stream-ordered layout (StreamLayout; only the
-// entries whose sets, delay or length changed since the last build).  Anything else: lw_active = false
-// and every block runs the standard path.
-// what build_plan_t found on the whole configuration's entries: a plain uniform crossbar (ok), its
-// entries per group (E) and partitions (P), and the whole-plan position of every entry of `flat`
-struct LongWhole { bool ok = false; int E = 0, P = 0; std::vector<int> wpos; };
-int build_long_layout(bfhip_engine *e, const std::vector<MacEntry<float>> &flat, const std::vector<ChunkRange> &chunks, int S,
-                      const LongWhole &lwh) {
-    e->lw_active = false;
-    e->la_active = e->far_active = false;
-    e->la_epoch++;                 // a new plan: other sets, scales, delays or lengths than the stored products used
-    if (!lwh.ok || flat.empty() || e->mac_diag || !e->mac_nt || e->mac_unroll != 0 || e->mac_threads != 256)
-        return BFHIP_OK;
-    const size_t L = e->L, LL = 2 * L;
-    const c2<float> *ring0 = (const c2<float> *)e->d_ring;
-    // (a filter delayed by d blocks uses min(P, N - d) partitions: what the derivation cuts, coeff_long_kernel)
-    const int P = lwh.P;
-    int SL = 1;
-    if (const char *env = getenv("BFHIP_LONG_CHUNKS")) SL = std::max(1, atoi(env));
-    if (lwh.E % SL != 0) return BFHIP_OK;
-    // long chunk c of a group = the whole plan's entries [c E_c, (c + 1) E_c) of it (those of them this
-    // engine runs: a shard's entries keep their whole-plan order, its chunks may be shorter)
-    const int E_c = lwh.E / SL, PL = (P + 2) / 3;
-    std::vector<ChunkRange> lchunks((size_t)e->n_groups * SL);
-    int E_here = 1;
-    for (int g = 0; g < e->n_groups; g++) {
-        int idx = chunks[(size_t)g * S].begin;
-        const int end = chunks[(size_t)g * S + S - 1].end;
-        for (int c = 0; c < SL; c++) {
-            ChunkRange cr{idx, idx};
-            while (idx < end && lwh.wpos[idx] / E_c == c) idx++;
-            cr.end = idx;
-            lchunks[(size_t)g * SL + c] = cr;
-            E_here = std::max(E_here, cr.end - cr.begin);
-        }
-        if (idx != end) return BFHIP_OK;
-    }
-    const int tiles = (int)(LL * sizeof(c2<float>) / 4096u);
-    const int n_tc = tiles * SL;
-    if (n_tc % 8 != 0) return BFHIP_OK;
-    const unsigned int chunk = 256u * 16u;
-    const unsigned long long entry_bytes = (unsigned long long)PL * OG * chunk;
-    const unsigned long long slice = (unsigned long long)E_here * entry_bytes;
-    if (entry_bytes >= (1ull << 31) || slice >= (1ull << 32)) return BFHIP_OK;
-    const size_t total = (size_t)((unsigned long long)n_tc * e->n_groups * slice);
-    const bool same_geom = e->d_lstream != nullptr && e->lw_chunks == SL && e->lw_P == PL && e->lkeys.size() == flat.size() &&
-                           e->lstream.slice == slice;
-    if (!same_geom) {
-        if (total > e->lstream_cap) {
-            if (e->d_lstream) (void)hipFree(e->d_lstream);
-            e->d_lstream = nullptr; e->lstream_cap = 0;
-            if (dev_alloc(&e->d_lstream, total) != hipSuccess) {
-                (void)hipGetLastError();
-                return BFHIP_OK;                 // no room for the long copy: the standard path
-            }
-            e->lstream_cap = total;
-        }
-        e->lkeys.assign(flat.size(), std::array<const void *, OG + 1>{});
-    }
-    // the long entries, and which of them hold other sets (or another delay / length) than last time
-    std::vector<MacEntry<float>> lflat(flat);
-    std::vector<StreamWhere> where(flat.size());
-    std::vector<int> changed;
-    for (int g = 0; g < e->n_groups; g++)
-        for (int c = 0; c < SL; c++) {
-            const ChunkRange cr = lchunks[(size_t)g * SL + c];
-            for (int q = 0; q < cr.end - cr.begin; q++) {
-                const int idx = cr.begin + q;
-                MacEntry<float> &en = lflat[idx];
-                const size_t in = (size_t)(en.ring - ring0) / (e->R * L);
-                en.ring = (const c2<float> *)e->d_lring + in * e->R * LL;
-                en.shift = 3 * ((en.maxP + 2) / 3) - en.maxP;     // the last partition's (kernels.h)
-                en.maxP = (en.maxP + 2) / 3;
-                where[idx] = StreamWhere{g, c, q, 0};
-                std::array<const void *, OG + 1> key;
-                for (int j = 0; j < OG; j++) key[j] = en.term[j].H;
-                key[OG] = (const void *)(uintptr_t)(((size_t)(unsigned)en.delay << 32) | (unsigned)P);
-                if (key != e->lkeys[idx]) { changed.push_back(idx); e->lkeys[idx] = key; }
-            }
-        }
-    const size_t eb = lflat.size() * sizeof(MacEntry<float>), cb = lchunks.size() * sizeof(ChunkRange);
-    if (eb > e->lentries_cap) {
-        if (e->d_lentries) (void)hipFree(e->d_lentries);
-        e->d_lentries = nullptr; e->lentries_cap = 0;
-        HIPCHK(dev_alloc(&e->d_lentries, eb));
-        e->lentries_cap = eb;
-    }
-    if (cb > e->lchunks_cap) {
-        if (e->d_lchunks) (void)hipFree(e->d_lchunks);
-        e->d_lchunks = nullptr; e->lchunks_cap = 0;
-        HIPCHK(dev_alloc((void **)&e->d_lchunks, cb));
-        e->lchunks_cap = cb;
-    }
-    const size_t wb = where.size() * sizeof(StreamWhere), ib = flat.size() * sizeof(int);
-    if (wb + ib > e->lwhere_cap) {
-        if (e->d_lwhere) (void)hipFree(e->d_lwhere);
-        e->d_lwhere = nullptr; e->lwhere_cap = 0;
-        HIPCHK(dev_alloc((void **)&e->d_lwhere, wb + ib));
-        e->lwhere_cap = wb + ib;
-    }
-    e->d_lwhich = (int *)((unsigned char *)e->d_lwhere + wb);
-    { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    HIPCHK(hipMemcpy(e->d_lentries, lflat.data(), eb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_lchunks, lchunks.data(), cb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_lwhere, where.data(), wb, hipMemcpyHostToDevice));
-    e->lw_chunks = SL; e->lw_P = PL; e->lw_tiles = tiles; e->lw_Pstd = P;
-    e->lstream = StreamLayout{(const unsigned char *)e->d_lstream, slice, (unsigned int)entry_bytes, chunk,
-                              (unsigned int)E_here * OG * chunk};
-    if (!changed.empty()) {
-        HIPCHK(hipMemcpy(e->d_lwhich, changed.data(), changed.size() * sizeof(int), hipMemcpyHostToDevice));
-        const int r = derive_long(e, 0, PL, (int)changed.size());
-        if (r != BFHIP_OK) { e->lkeys.clear(); return r; }
-    }
-    e->lw_active = true;
-    // look-ahead: the whole plan is this engine's, one chunk per group, no tail partition reaches a block
-    // younger than t - 3 (the shifted last partition does when it is p = 1), and the coefficients are
-    // large enough to be worth three ahead buffers per block (BFHIP_LOOKAHEAD=1 / 0: always / never)
-    int want = -1;
-    if (const char *env = getenv("BFHIP_LOOKAHEAD")) want = atoi(env) != 0 ? 1 : 0;
-    double vol = 0;
-    for (auto &c : e->coeffs) vol += (double)c.n_blocks * (double)L * (double)sizeof(c2<float>);
-    bool la = want != 0 && (want == 1 || vol >= 1073741824.0) && SL == 1 && !e->sharded && !e->pairs &&
-              flat.size() == (size_t)e->n_groups * (size_t)lwh.E;
-    for (size_t i = 0; i < lflat.size() && la; i++) {
-        const MacEntry<float> &en = lflat[i];
-        la = en.dense == 1 && en.p0 == 0 && (en.maxP < 2 || 3 * (en.maxP - 1) - en.shift + en.delay >= 3);
-    }
-    if (la) {
-        const size_t ab = (size_t)4 * 3 * e->n_out_padded * LL * sizeof(c2<float>);
-        if (ab > e->ahead_cap) {
-            if (e->d_ahead) (void)hipFree(e->d_ahead);
-            e->d_ahead = nullptr; e->ahead_cap = 0;
-            if (dev_alloc(&e->d_ahead, ab) != hipSuccess) { (void)hipGetLastError(); la = false; }
-            else e->ahead_cap = ab;
-        }
-    }
-    e->la_active = la;
-    // second tier: some entry has a partition >= 2 beyond the first, none of them reaches a block younger
-    // than t - 6 (the shifted last partition does when it is p = 2 without delay), and the same volume
-    // (BFHIP_LOOKAHEAD_FAR=1 / 0: whenever the first tier runs / never; BFHIP_LOOKAHEAD=1 alone: not)
-    int want_far = -1;
-    if (const char *env = getenv("BFHIP_LOOKAHEAD_FAR")) want_far = atoi(env) != 0 ? 1 : 0;
-    bool far = la && want_far != 0 && (want_far == 1 || vol >= 1073741824.0);
-    bool any3 = false;
-    for (size_t i = 0; i < lflat.size() && far; i++) {
-        const MacEntry<float> &en = lflat[i];
-        any3 = any3 || en.maxP >= 3;
-        far = en.maxP < 3 || 3 * (en.maxP - 1) - en.shift + en.delay >= 6;
-    }
-    far = far && any3;
-    if (far) {
-        const size_t fb = (size_t)7 * LA_FAR * e->n_out_padded * LL * sizeof(c2<float>);
-        if (fb > e->far_cap) {
-            if (e->d_far) (void)hipFree(e->d_far);
-            e->d_far = nullptr; e->far_cap = 0;
-            if (dev_alloc(&e->d_far, fb) != hipSuccess) { (void)hipGetLastError(); far = false; }   // one tier
-            else e->far_cap = fb;
-        }
-    }
-    e->far_active = far;
-    if (la && e->blocks_done == 0) return la_prime(e);
-    return BFHIP_OK;
-}
-
-template <typename T>
-int build_plan_t(bfhip_engine *e) {
-    const int O = e->n_ch[1], I = e->n_ch[0], F = (int)e->filters.size();
-    const size_t L = e->L;
-    e->n_groups = (O + OG - 1) / OG;
-    e->n_out_padded = e->n_groups * OG;
-    std::vector<std::vector<MacEntry<T>>> per_group(e->n_groups);
-    std::vector<std::map<std::pair<long, int>, std::vector<int>>> index(e->n_groups);
-    double bytes_H = 0, bytes_ring = 0;
-    // ring id: 0..I-1 input rings, I+f private ring of filter f, I+F+f materialised Y_f
-    std::map<long, std::vector<char>> ring_used;
-
-    std::vector<std::vector<FillJob<T>>> fills(e->n_levels);
-    std::vector<std::vector<FilterJob<T>>> filts(e->n_levels);
-    std::vector<std::vector<FadeJob<T>>> fades(e->n_levels);
-    std::vector<MixSrc<T>> srcs;
-    e->any_fading = false;
-
-    auto Yptr = [&](int f) { return (c2<T> *)e->d_Y + (size_t)e->y_index[f] * L; };
-    // ring ids order the entries of a group: filters go by the host's own numbering where it gave one,
-    // so that the order does not depend on the order the filters were added in
-    long NAMES = F;
-    for (auto &f : e->filters) NAMES = std::max(NAMES, (long)f.name + 1);
-    auto fname = [&](int fi) { return (long)(e->filters[fi].name >= 0 ? e->filters[fi].name : fi); };
-
-    // lazily loaded coefficient sets: whatever an active filter refers to now has to be on the device
-    for (int fi = 0; fi < F; fi++) {
-        const Filter &f = e->filters[fi];
-        if (!f.active) continue;
-        for (int c : {f.coeff, (f.crossfade && f.prevcoeff != f.coeff) ? f.prevcoeff : -1}) {
-            if (c < 0 || c >= (int)e->coeffs.size() || e->coeffs[c].d_H != nullptr) continue;
-            const int r = coeff_make_resident(e, c);
-            if (r != BFHIP_OK) return r;
-        }
-    }
-    // which terms belong to filters another engine runs: [group][entry] bit j
-    std::vector<std::vector<unsigned int>> foreign(e->n_groups);
-    bool lw_plain = true;              // no filter mixes, cascades, fades or has a ring of its own
-    double bytes_H_plan = 0;           // the whole configuration's: what the launch geometry is chosen for
-
-    for (int fi = 0; fi < F; fi++) {
-        const Filter &f = e->filters[fi];
-        if (f.coeff >= (int)e->coeffs.size()) return fail(BFHIP_EINVAL, "filter %d: bad coeff", fi);
-        const int delay = clamp_delay(e, f.delayblocks);
-        const int P = f.coeff < 0 ? 1 : cblocks_of(e, f.coeff, delay);
-        // (an inactive filter is classified like an active one -- the plan's shape must not depend
-        // on who runs what -- but owns no memory here)
-        const bool owner_kind = f.in_ch.size() != 1 || !f.in_f.empty();
-        const bool owner = f.active ? (e->owner_index[fi] >= 0 || e->promoted[fi] != nullptr)
-                                    : (owner_kind || e->promoted[fi] != nullptr);
-        const bool fading = f.crossfade && f.prevcoeff != f.coeff;
-        const bool needY = e->is_source[fi] || fading;
-        if (fading && f.active) e->any_fading = true;
-        if (owner || owner_kind || needY) lw_plain = false;        // (every engine sees every filter's state)
-        if (f.active && needY && e->y_index[fi] < 0) return fail(BFHIP_ESTATE, "filter %d: no output buffer reserved", fi);
-
-        // where this filter's history lives and how to index it
-        const c2<T> *ring;
-        long ring_id;
-        int rdelay;
-        double rscale;
-        if (owner) {
-            ring = !f.active ? nullptr
-                 : e->promoted[fi] ? (const c2<T> *)e->promoted[fi]
-                                   : (const c2<T> *)e->d_fring + (size_t)e->owner_index[fi] * e->N * L;
-            ring_id = I + fname(fi); rdelay = 0; rscale = 1.0;
-            if (f.active) {
-            FillJob<T> job;
-            memset(&job, 0, sizeof(job));
-            job.ring = (c2<T> *)ring;
-            job.delay = delay;
-            job.n_in = (int)f.in_ch.size();
-            job.in_off = (int)srcs.size();
-            for (size_t i = 0; i < f.in_ch.size(); i++) {
-                MixSrc<T> m;
-                m.spec = (const c2<T> *)e->d_ring + (size_t)f.in_ch[i] * e->R * L;
-                m.scale = (T)(f.in_scale[i] * e->fmt[0][e->v2p[0][f.in_ch[i]]].scale);      // bfrun.c:1641 (virtscales)
-                m.R = e->R;
-                srcs.push_back(m);
-            }
-            job.n_up = (int)f.in_f.size();
-            job.up_off = (int)srcs.size();
-            for (size_t i = 0; i < f.in_f.size(); i++) {
-                MixSrc<T> m;
-                m.spec = Yptr(f.in_f[i]);
-                m.scale = (T)f.in_fscale[i];
-                m.R = 1;
-                srcs.push_back(m);
-            }
-            job.evalprev = job.n_up > 0 ? (T *)e->d_evalprev + (size_t)e->sink_index[fi] * L : nullptr;
-            fills[e->level[fi]].push_back(job);
-            }
-        } else {
-            const int ch = f.in_ch[0];
-            ring = (const c2<T> *)e->d_ring + (size_t)ch * e->R * L;
-            ring_id = ch; rdelay = delay;
-            rscale = f.in_scale[0] * e->fmt[0][e->v2p[0][ch]].scale;                         // bfrun.c:1664
-        }
-        if (f.active) {
-            auto &u = ring_used[ring_id];
-            u.resize(e->N, 0);
-            for (int p = 0; p < P; p++) u[(p + rdelay) % e->N] = 1;
-        }
-
-        if (needY && f.active) {
-            FilterJob<T> job;
-            job.ring = ring; job.R = owner ? e->N : e->R; job.delay = rdelay; job.scale = (T)rscale;
-            job.H = f.coeff < 0 ? nullptr : (const c2<T> *)e->coeffs[f.coeff].d_H;
-            job.P = P; job.kind = f.coeff < 0 ? TERM_DIRAC : TERM_COEFF;
-            job.Y = Yptr(fi);
-            filts[e->level[fi]].push_back(job);
-            if (f.coeff >= 0) bytes_H += (double)P * (double)L * (double)sizeof(c2<T>);
-            if (fading) {
-                // old-coefficient result for the fade (bfrun.c:1726-1769, 1803-1827)
-                FilterJob<T> old = job;
-                const int pc = f.prevcoeff;
-                old.H = pc < 0 ? nullptr : (const c2<T> *)e->coeffs[pc].d_H;
-                old.P = pc < 0 ? 1 : cblocks_of(e, pc, delay);
-                old.kind = pc < 0 ? TERM_DIRAC : TERM_COEFF;
-                old.Y = (c2<T> *)e->d_Yold + (size_t)e->fade_index[fi] * L;
-                filts[e->level[fi]].push_back(old);
-                FadeJob<T> fj;
-                fj.Ynew = job.Y; fj.Yold = old.Y;
-                fades[e->level[fi]].push_back(fj);
-            }
-        }
-        if (needY && f.coeff >= 0) bytes_H_plan += (double)P * (double)L * (double)sizeof(c2<T>);
-
-        for (size_t oi = 0; oi < f.out_ch.size(); oi++) {
-            const int o = f.out_ch[oi];
-            const int g = o / OG, j = o % OG;
-            const double s_out = f.out_scale[oi] / e->fmt[1][e->v2p[1][o]].scale;            // bfrun.c:1850
-            const std::pair<long, int> key = needY ? std::make_pair((long)(I + NAMES + fname(fi)), 0)
-                                                   : std::make_pair(ring_id, rdelay);
-            auto &slots = index[g][key];
-            int ei = -1;
-            for (int cand : slots) {
-                if (per_group[g][cand].term[j].kind == TERM_NONE) { ei = cand; break; }
-            }
-            if (ei < 0) {
-                MacEntry<T> ne;
-                memset(&ne, 0, sizeof(ne));
-                ne.ring = needY ? (f.active ? Yptr(fi) : nullptr) : ring;
-                ne.R = needY ? 1 : (owner ? e->N : e->R);
-                ne.delay = needY ? 0 : rdelay;
-                ne.live = (!needY && !owner && e->d_ps_live) ? e->d_ps_live + ring_id : nullptr;
-                for (int q = 0; q < OG; q++) ne.term[q].kind = TERM_NONE;
-                per_group[g].push_back(ne);
-                foreign[g].push_back(0u);
-                ei = (int)per_group[g].size() - 1;
-                slots.push_back(ei);
-            }
-            MacTerm<T> &tm = per_group[g][ei].term[j];
-            if (!f.active) foreign[g][ei] |= 1u << j;
-            if (needY) {
-                tm.kind = TERM_IDENT; tm.H = nullptr; tm.P = 1; tm.scale = (T)s_out;
-            } else {
-                tm.kind = f.coeff < 0 ? TERM_DIRAC : TERM_COEFF;
-                tm.H = f.coeff < 0 ? nullptr : (const c2<T> *)e->coeffs[f.coeff].d_H;
-                tm.P = P;
-                tm.scale = (T)(rscale * s_out);
-                if (f.coeff >= 0) {
-                    bytes_H_plan += (double)P * (double)L * (double)sizeof(c2<T>);
-                    if (f.active) bytes_H += (double)P * (double)L * (double)sizeof(c2<T>);
-                }
-            }
-            per_group[g][ei].maxP = std::max(per_group[g][ei].maxP, tm.P);
-        }
-    }
-
-    // Canonical entry order inside a group: by (ring, delay), then by the order in which the same
-    // key was needed again (an output fed twice from one ring).  An output's terms are then summed
-    // in an order that depends on its own filters only -- not on which other outputs share its
-    // group, nor on the order the host listed its filters in.
-    for (int g = 0; g < e->n_groups; g++) {
-        std::vector<std::pair<std::pair<std::pair<long, int>, int>, int>> order;     // ((key, n-th use), old index)
-        for (auto &kv : index[g])
-            for (size_t n = 0; n < kv.second.size(); n++) order.push_back({{kv.first, (int)n}, kv.second[n]});
-        std::sort(order.begin(), order.end());
-        std::vector<MacEntry<T>> sorted;
-        std::vector<unsigned int> fsorted;
-        for (auto &o : order) { sorted.push_back(per_group[g][o.second]); fsorted.push_back(foreign[g][o.second]); }
-        per_group[g].swap(sorted);
-        foreign[g].swap(fsorted);
-    }
-
-    // launch geometry: one fat workgroup per CU measured best on MI355X (tools/tune_mac.py): each
-    // wave keeps 18 KiB of loads in flight, so 4 waves per CU already saturate HBM, and fewer
-    // chunks mean fewer partial sums to write and re-read
-    e->mac_threads = std::min(256, std::max(64, e->L / (int)(16 / sizeof(c2<T>))));
-    const int bins_per_wg = e->mac_threads * (int)(16 / sizeof(c2<T>));
-    e->n_tiles = (e->L + bins_per_wg - 1) / bins_per_wg;
-    int target_wgs = 256;
-    if (const char *env = getenv("BFHIP_MAC_TARGET_WGS")) target_wgs = std::max(1, atoi(env));
-    if (const char *env = getenv("BFHIP_MAC_NT")) e->mac_nt = atoi(env) != 0;
-    if (const char *env = getenv("BFHIP_MAC_UNROLL")) e->mac_unroll = atoi(env);
-    const int s_full = std::max(1, std::min(64, (target_wgs + e->n_tiles * e->n_groups - 1) / (e->n_tiles * e->n_groups)));
-    int S = s_full;
-    if (!getenv("BFHIP_MAC_TARGET_WGS")) {
-        // every chunk costs the output pass one more partial spectrum to read (~2 us measured);
-        // a workgroup streams ~1.35 GB/s per KiB it keeps in flight per wave (2 partitions x
-        // (1 ring + n coefficient loads) KiB; 25 GB/s at the crossbar's 18 KiB), the chip
-        // ~6.4 TB/s, and a launch is never shorter than ~13 us.  Pick the split that minimises
-        // MAC + output-pass time (matters for small crossbars; config C: S = 2).
-        double n_terms = 0, n_ent = 0;
-        for (auto &v : per_group)
-            for (auto &en : v) {
-                n_ent += 1;
-                for (int q = 0; q < OG; q++) n_terms += en.term[q].kind == TERM_COEFF ? 1 : 0;
-            }
-        const double rate = 1.35e9 * 2.0 * (1.0 + (n_ent > 0 ? n_terms / n_ent : 1.0));
-        double best = 1e30;
-        for (int c = 1; c <= s_full; c++) {
-            const double wgs = std::min(256.0, (double)e->n_tiles * e->n_groups * c);
-            const double t_mac = std::max(std::max(13e-6, bytes_H_plan / 6.4e12), bytes_H_plan / (wgs * rate));
-            const double t_out = 2e-6 * c;
-            if (t_mac + t_out < best - 1e-9) { best = t_mac + t_out; S = c; }
-        }
-    }
-
-    // One-to-one plans (massive_config, BASELINE configs[3]): every entry a single coefficient term,
-    // every output fed by one entry.  They get mac_diag_kernel -- a workgroup per (chunk, output)
-    // that walks whole spectra -- and their parallelism from splitting the PARTITIONS of every entry
-    // into S parts (part c of every entry = chunk c), not from bin tiles.
-    // (a workgroup holds up to 16 tiles of the spectrum in registers, a job is split over up to 8: 128 tiles)
-    bool diag_plan = !e->big && (e->L + bins_per_wg - 1) / bins_per_wg <= 128;
-    if (const char *env = getenv("BFHIP_MAC_DIAG")) diag_plan = diag_plan && atoi(env) != 0;
-    {
-        std::vector<char> fed(e->n_out_padded, 0);
-        int n_ent = 0;
-        for (int g = 0; g < e->n_groups && diag_plan; g++)
-            for (auto &en : per_group[g]) {
-                int n_terms = 0, only = -1;
-                for (int q = 0; q < OG; q++) if (en.term[q].kind != TERM_NONE) { n_terms++; only = q; }
-                if (n_terms != 1 || en.term[only].kind != TERM_COEFF || fed[g * OG + only]) { diag_plan = false; break; }
-                fed[g * OG + only] = 1;
-                n_ent++;
-            }
-        if (n_ent == 0) diag_plan = false;
-        if (diag_plan) {
-            // ~512 workgroups keep every CU busy with two; every part costs the output pass one more
-            // partial spectrum per channel
-            int maxlen = 1;
-            for (auto &v : per_group) for (auto &en : v) maxlen = std::max(maxlen, en.maxP);
-            // (workgroups come from splitting a job's SPECTRUM first -- up to 8 runs of tiles, no partial
-            // sums -- and only then from parts of the partition axis: config D 256 entries x 2 tile runs)
-            const int all_tiles = std::max(1, e->L / bins_per_wg);
-            const int per_entry = std::min(all_tiles, 8);
-            S = std::max(1, std::min(std::min(4, maxlen), (256 + n_ent * per_entry - 1) / (n_ent * per_entry)));
-            if (const char *env = getenv("BFHIP_DIAG_SPLIT")) S = std::max(1, std::min(maxlen, atoi(env)));
-        }
-    }
-
-    std::vector<std::vector<int>> part_of(e->n_groups);     // diag plans: which part an entry is (= its chunk)
-    // few filters with many partitions (room correction): split entries along p until every
-    // group has S work items
-    for (int g = 0; g < e->n_groups; g++) {
-        auto &v = per_group[g];
-        if (v.empty()) continue;
-        if (!diag_plan && (int)v.size() >= S) continue;
-        if (diag_plan && S == 1) continue;
-        const int parts = diag_plan ? S : (S + (int)v.size() - 1) / (int)v.size();
-        std::vector<MacEntry<T>> split;
-        std::vector<unsigned int> fsplit;
-        std::vector<int> psplit;
-        auto emit = [&](size_t i, int q) {
-            const MacEntry<T> &en = v[i];
-            const int len = en.maxP;
-            const int np = std::max(1, std::min(parts, len));
-            if (q >= np) return;
-            MacEntry<T> sub = en;
-            sub.p0 = (int)((long)len * q / np);
-            sub.maxP = (int)((long)len * (q + 1) / np);
-            if (sub.maxP > sub.p0) { split.push_back(sub); fsplit.push_back(foreign[g][i]); psplit.push_back(q); }
-        };
-        if (diag_plan) {
-            for (int q = 0; q < parts; q++) for (size_t i = 0; i < v.size(); i++) emit(i, q);      // part-major: chunk c = part c
-        } else {
-            for (size_t i = 0; i < v.size(); i++) for (int q = 0; q < parts; q++) emit(i, q);
-        }
-        v.swap(split);
-        foreign[g].swap(fsplit);
-        if (diag_plan) part_of[g].swap(psplit);
-    }
-    size_t max_entries = 1;
-    for (auto &v : per_group) max_entries = std::max(max_entries, v.size());
-    S = std::max(1, std::min<int>(S, (int)max_entries));
-    e->n_chunks = S;
-
-    e->all_dense = true;
-    for (auto &v : per_group) {
-        for (auto &en : v) {
-            bool dense = en.maxP > en.p0;
-            for (int q = 0; q < OG; q++) dense = dense && en.term[q].kind == TERM_COEFF && en.term[q].P >= en.maxP;
-            en.dense = dense ? 1 : 0;
-            // exactly one coefficient term (one-to-one filters, massive_config style): its own
-            // pipelined path, 2 + index of the term
-            if (en.dense != 1) e->all_dense = false;
-            int n_active = 0, only = -1;
-            for (int q = 0; q < OG; q++) if (en.term[q].kind != TERM_NONE) { n_active++; only = q; }
-            if (!dense && n_active == 1 && en.term[only].kind == TERM_COEFF && en.maxP > en.p0) en.dense = 2 + only;
-            // several (not all OG) coefficient terms of full length: the crossbar path over a subset
-            en.mask = 0;
-            if (!dense && n_active >= 2 && en.maxP > en.p0) {
-                bool ok = true;
-                int mask = 0;
-                for (int q = 0; q < OG; q++) {
-                    if (en.term[q].kind == TERM_NONE) continue;
-                    ok = ok && en.term[q].kind == TERM_COEFF && en.term[q].P >= en.maxP;
-                    mask |= 1 << q;
-                }
-                if (ok) { en.dense = 16; en.mask = mask; }
-            }
-        }
-    }
-
-    // chunk boundaries from the WHOLE plan; then the terms of filters another engine runs are taken
-    // out (an entry's path -- crossbar, single term, generic -- stays the one the whole plan gave it:
-    // the single-term path rounds differently from the others), entries left empty are dropped
-    // Whether the long-window plan (kernels.h) can take this plan is decided on the WHOLE configuration's
-    // entries, before foreign terms are taken out: a shard then runs the plan the one-process engine runs,
-    // and every output is summed in the same order (the subset path rounds like the crossbar path).
-    LongWhole lwh;
-    lwh.ok = e->lw_struct && lw_plain;
-    for (int g = 0; g < e->n_groups && lwh.ok; g++) {
-        const auto &v = per_group[g];
-        if (g == 0) lwh.E = (int)v.size();
-        if ((int)v.size() != lwh.E || v.empty()) lwh.ok = false;
-        for (auto &en : v) lwh.P = std::max(lwh.P, en.maxP);
-    }
-    for (int g = 0; g < e->n_groups && lwh.ok; g++)
-        for (auto &en : per_group[g]) {
-            const ptrdiff_t off = (const c2<T> *)en.ring - (const c2<T> *)e->d_ring;
-            bool ok = en.dense == 1 && en.p0 == 0 && en.maxP >= 1 && en.maxP == std::min(lwh.P, e->N - en.delay) &&
-                      en.live == nullptr && en.R == e->R && en.ring != nullptr && off >= 0 &&
-                      off % (ptrdiff_t)(e->R * L) == 0 && off / (ptrdiff_t)(e->R * L) < I;
-            for (int j = 0; j < OG && ok; j++) ok = en.term[j].kind == TERM_COEFF;
-            if (!ok) { lwh.ok = false; break; }
-        }
-    std::vector<MacEntry<T>> flat;
-    std::vector<ChunkRange> chunks((size_t)e->n_groups * S);
-    for (int g = 0; g < e->n_groups; g++) {
-        const auto &v = per_group[g];
-        long total = 0;
-        for (auto &en : v) total += en.maxP - en.p0;
-        size_t pos = 0;
-        long acc = 0;
-        for (int c = 0; c < S; c++) {
-            ChunkRange cr;
-            cr.begin = (int)flat.size();
-            const long want = (total * (c + 1) + S - 1) / S;
-            // (a one-to-one plan split along p: chunk c is part c of every entry, whatever their lengths)
-            const bool by_part = diag_plan && part_of[g].size() == v.size();
-            while (pos < v.size() && (by_part ? part_of[g][pos] == c : (acc < want || c == S - 1))) {
-                acc += v[pos].maxP - v[pos].p0;
-                MacEntry<T> en = v[pos];
-                const unsigned int fm = foreign[g][pos];
-                pos++;
-                if (fm) {
-                    unsigned int present = 0;
-                    for (int q = 0; q < OG; q++) if (en.term[q].kind != TERM_NONE) present |= 1u << q;
-                    const unsigned int keep = present & ~fm;
-                    if (keep == 0) continue;                              // nothing of ours in it
-                    if (en.dense == 1) { en.dense = 16; en.mask = (int)keep; }
-                    else if (en.dense == 16) en.mask &= (int)keep;
-                    for (int q = 0; q < OG; q++)
-                        if (fm & (1u << q)) { en.term[q].kind = TERM_NONE; en.term[q].H = nullptr; }
-                }
-                flat.push_back(en);
-                lwh.wpos.push_back((int)pos - 1);
-            }
-            cr.end = (int)flat.size();
-            chunks[(size_t)g * S + c] = cr;
-        }
-    }
-    e->all_dense = !flat.empty();
-    for (auto &en : flat) if (en.dense != 1) e->all_dense = false;
-    // mac_diag_kernel's job table: the one entry behind every (chunk, output), or -1.  Checked on the
-    // plan as it came out (unequal filter lengths can put two parts of one entry into one chunk):
-    // anything unexpected keeps the crossbar kernel, which takes every plan.
-    std::vector<int> diag_jobs;
-    e->mac_diag = diag_plan && !flat.empty();
-    if (e->mac_diag) {
-        diag_jobs.assign((size_t)S * e->n_out_padded, -1);
-        for (int g = 0; g < e->n_groups && e->mac_diag; g++)
-            for (int c = 0; c < S && e->mac_diag; c++) {
-                const ChunkRange cr = chunks[(size_t)g * S + c];
-                for (int idx = cr.begin; idx < cr.end; idx++) {
-                    const MacEntry<T> &en = flat[idx];
-                    if (en.dense < 2 || en.dense >= 2 + OG) { e->mac_diag = false; break; }
-                    int &slot = diag_jobs[(size_t)c * e->n_out_padded + g * OG + (en.dense - 2)];
-                    if (slot != -1) { e->mac_diag = false; break; }
-                    slot = idx;
-                }
-            }
-    }
-    e->n_entries = (int)flat.size();
-
-    // job arrays for the levelled (non fast-path) filters, one device blob
-    std::vector<unsigned char> blob;
-    auto append = [&](const void *p, size_t n) {
-        const size_t off = (blob.size() + 15) & ~(size_t)15;
-        blob.resize(off + n);
-        if (n) memcpy(blob.data() + off, p, n);
-        return off;
-    };
-    e->src_off = append(srcs.data(), srcs.size() * sizeof(MixSrc<T>));
-    e->level_jobs.assign(e->n_levels, bfhip_engine::LevelJobs());
-    for (int lv = 0; lv < e->n_levels; lv++) {
-        auto &lj = e->level_jobs[lv];
-        lj.n_fill = (int)fills[lv].size();
-        lj.fill_off = append(fills[lv].data(), fills[lv].size() * sizeof(FillJob<T>));
-        lj.n_filt = (int)filts[lv].size();
-        lj.filt_off = append(filts[lv].data(), filts[lv].size() * sizeof(FilterJob<T>));
-        lj.n_fade = (int)fades[lv].size();
-        lj.fade_off = append(fades[lv].data(), fades[lv].size() * sizeof(FadeJob<T>));
-    }
-
-    // upload
-    const size_t eb = std::max<size_t>(flat.size(), 1) * sizeof(MacEntry<T>);
-    if (eb > e->entries_cap) {
-        if (e->d_entries) (void)hipFree(e->d_entries);
-        HIPCHK(dev_alloc(&e->d_entries, eb));
-        e->entries_cap = eb;
-    }
-    const size_t cb_chunks = chunks.size() * sizeof(ChunkRange);
-    const size_t cb = cb_chunks + (e->mac_diag ? diag_jobs.size() * sizeof(int) : 0);
-    if (cb > e->chunks_cap) {
-        if (e->d_chunks) (void)hipFree(e->d_chunks);
-        HIPCHK(dev_alloc((void **)&e->d_chunks, cb));
-        e->chunks_cap = cb;
-    }
-    if (blob.size() > e->jobs_cap) {
-        if (e->d_jobs) (void)hipFree(e->d_jobs);
-        HIPCHK(dev_alloc(&e->d_jobs, blob.size()));
-        e->jobs_cap = blob.size();
-    }
-    { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    if (!flat.empty()) HIPCHK(hipMemcpy(e->d_entries, flat.data(), flat.size() * sizeof(MacEntry<T>), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_chunks, chunks.data(), cb_chunks, hipMemcpyHostToDevice));
-    e->d_diag_jobs = nullptr;
-    if (e->mac_diag) {
-        e->d_diag_jobs = (const int *)((const unsigned char *)e->d_chunks + cb_chunks);
-        HIPCHK(hipMemcpy((void *)e->d_diag_jobs, diag_jobs.data(), diag_jobs.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    if (!blob.empty()) HIPCHK(hipMemcpy(e->d_jobs, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    {   // stream-ordered coefficient copy (StreamLayout) for uniform crossbar plans
-        const int r = build_stream_layout<T>(e, flat, chunks, S, bytes_H);
-        if (r != BFHIP_OK) return r;
-    }
-    e->lw_active = false;
-    e->la_active = e->far_active = false;
-    e->la_epoch++;
-    if constexpr (std::is_same<T, float>::value) {
-        const int r = build_long_layout(e, flat, chunks, S, lwh);
-        if (r != BFHIP_OK) return r;
-    }
-    size_t zb = (size_t)S * e->n_out_padded * L * sizeof(c2<T>);
-    if (e->lw_active) zb = std::max(zb, (size_t)e->lw_chunks * e->n_out_padded * 2 * L * sizeof(c2<T>));
-    if (zb > e->zp_bytes) {
-        for (void *&z : e->d_Zp) { if (z) (void)hipFree(z); z = nullptr; }
-        for (int i = 0; i < zp_depth(e); i++) HIPCHK(dev_alloc(&e->d_Zp[i], zb));
-        for (bool &z : e->zp_long) z = false;
-        e->zp_bytes = zb;
-        e->zp_last = 0;
-    }
-
-    // algorithmic bytes per block, SURVEY 8(d): C*(F*P + U*P + U + O) + (I+O)*L*s_raw
-    const double C = (double)L * sizeof(c2<T>);
-    for (auto &kv : ring_used) for (char u : kv.second) bytes_ring += u ? C : 0;
-    double raw = 0;
-    for (int io = 0; io < 2; io++)
-        for (int c = 0; c < e->n_phys[io]; c++) raw += (double)L * e->fmt[io][c].bytes;
-    int O_here = 0;
-    for (int o = 0; o < O; o++) O_here += e->out_active.empty() || e->out_active[o] ? 1 : 0;
-    e->alg_bytes_mac = bytes_H + bytes_ring + C * O_here;
-    e->alg_bytes_total = e->alg_bytes_mac + C * (I + e->n_owners) + raw;
-    e->plan_dirty = false;
-    return BFHIP_OK;
-}
-
-int build_plan(bfhip_engine *e) {
-    return e->rs == 4 ? build_plan_t<float>(e) : build_plan_t<double>(e);
-}
 
 size_t raw_extent(const std::vector<bfhip_format> &v, int n, int L) {
     size_t m = 0;
@@ -2745,14 +1482,17 @@ void bfhip_engine_destroy(bfhip_engine *e) {
     if (e->s_out) (void)hipStreamDestroy(e->s_out);
     if (e->d_status_own) e->d_status = e->d_status_own;
     void *ptrs[] = {e->d_tw, e->d_prev, e->d_ring, e->d_fmt[0], e->d_fmt[1], e->d_over, e->d_status,
-                    e->d_bad, e->d_entries, e->d_chunks, e->d_rawin, e->d_rawout, e->d_taps,
-                    e->d_fring, e->d_Y, e->d_Yold, e->d_evalprev, e->d_jobs,
+                    e->d_bad, e->d_rawin, e->d_rawout,
+                    e->d_fring, e->d_Y, e->d_Yold, e->d_evalprev,
                     e->d_dither_ch, e->d_dither_state, e->d_dither_table, e->d_randmap, e->d_skip_quant, e->d_timeout,
-                    e->d_big[0], e->d_big[1], e->d_big[2], e->d_tw13, e->d_tww,
-                    e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc, e->d_stream, e->d_where,
+                    e->d_tw13, e->d_tww,
+                    e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc,
                     e->d_planar[0], e->d_planar[1], e->d_phys_skip,
-                    e->d_hist, e->d_lring, e->d_tw14, e->d_lentries, e->d_lchunks, e->d_lstream, e->d_lwhere, e->d_ahead, e->d_far};
+                    e->d_hist, e->d_lring, e->d_tw14};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (DevBuf *b : {&e->b_entries, &e->b_chunks, &e->b_jobs, &e->b_stream, &e->b_where, &e->b_lentries, &e->b_lchunks,
+                      &e->b_lstream, &e->b_lwhere, &e->b_ahead, &e->b_far, &e->b_taps, &e->b_big[0], &e->b_big[1], &e->b_big[2]})
+        b->release();
     for (auto ev : e->ev) (void)hipEventDestroy(ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -2890,14 +1630,10 @@ static int add_coeff_common(bfhip_engine *e, const void *taps, bool on_device, i
     if (on_device) HIPCHK(hipDeviceSynchronize());
     if (!on_device && n_taps > 0) {
         const size_t bytes = (size_t)n_taps * e->rs;
-        if (bytes > e->taps_cap) {
-            if (e->d_taps) { { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; } (void)hipFree(e->d_taps); e->d_taps = nullptr; }
-            HIPCHK(dev_alloc(&e->d_taps, bytes));
-            e->taps_cap = bytes;
-        }
+        { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
         { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-        HIPCHK(hipMemcpy(e->d_taps, taps, bytes, hipMemcpyHostToDevice));
-        src = e->d_taps;
+        HIPCHK(hipMemcpy(e->b_taps.p, taps, bytes, hipMemcpyHostToDevice));
+        src = e->b_taps.p;
     }
     Coeff c;
     c.n_blocks = n_blocks;
@@ -2960,25 +1696,22 @@ static int upload_processed_block(bfhip_engine *e, Coeff &c, int block, const vo
         if (!std::isfinite(v)) return fail(BFHIP_EINVAL, "NaN or Inf value among coefficients.");
     }
     const size_t bytes = n * e->rs;
-    if (bytes > e->taps_cap) {
-        if (e->d_taps) { { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; } (void)hipFree(e->d_taps); e->d_taps = nullptr; }
-        HIPCHK(dev_alloc(&e->d_taps, bytes));
-        e->taps_cap = bytes;
-    }
+    { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }      // d_taps is reused; nothing may still read H
-    HIPCHK(hipMemcpy(e->d_taps, cbuf, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->b_taps.p, cbuf, bytes, hipMemcpyHostToDevice));
     void *H = (unsigned char *)c.d_H + (size_t)block * e->L * e->csize();
     const dim3 grid((e->L + 255) / 256, 1);
     if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->d_taps, (c2<float> *)H, e->L, 1, (float *)nullptr);
+        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->b_taps.p, (c2<float> *)H, e->L, 1, (float *)nullptr);
     else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->d_taps, (c2<double> *)H, e->L, 1, (double *)nullptr);
+        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->b_taps.p, (c2<double> *)H, e->L, 1, (double *)nullptr);
     HIPCHK(hipGetLastError());
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     return e->rs == 4 ? stream_refresh_block<float>(e, c.d_H, block) : stream_refresh_block<double>(e, c.d_H, block);
 }
 
-namespace {
+extern "C++" {
+BFHIP_HOST_NS {
 // a lazily registered set goes to the device (the first time an active filter refers to it)
 int coeff_make_resident(bfhip_engine *e, int ci) {
     Coeff &c = e->coeffs[ci];
@@ -2996,7 +1729,8 @@ int coeff_make_resident(bfhip_engine *e, int ci) {
     }
     return BFHIP_OK;
 }
-}  // namespace
+}  // namespace bfhip_host
+}  // extern "C++"
 
 int bfhip_engine_add_coeff_processed_blocks(bfhip_engine *e, void *const cbufs[], int n_blocks, int flags) {
     if (!e || !cbufs || n_blocks < 1) return fail(BFHIP_EINVAL, "add_coeff_processed_blocks: bad argument");
@@ -3078,22 +1812,18 @@ int bfhip_engine_add_coeff_processed(bfhip_engine *e, const void *cbufs, int n_b
         if (!std::isfinite(v)) return fail(BFHIP_EINVAL, "NaN or Inf value among coefficients.");
     }
     const size_t bytes = n * e->rs;
-    if (bytes > e->taps_cap) {
-        if (e->d_taps) { { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; } (void)hipFree(e->d_taps); e->d_taps = nullptr; }
-        HIPCHK(dev_alloc(&e->d_taps, bytes));
-        e->taps_cap = bytes;
-    }
+    { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    HIPCHK(hipMemcpy(e->d_taps, cbufs, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->b_taps.p, cbufs, bytes, hipMemcpyHostToDevice));
     Coeff c;
     c.n_blocks = n_blocks;
     if ((c.d_H = coeff_alloc(e, (size_t)n_blocks * e->L * e->csize())) == nullptr)
         return fail(BFHIP_ENOMEM, "out of device memory for coefficient set");
     const dim3 grid((e->L + 255) / 256, n_blocks);
     if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->d_taps, (c2<float> *)c.d_H, e->L, 1, (float *)nullptr);
+        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->b_taps.p, (c2<float> *)c.d_H, e->L, 1, (float *)nullptr);
     else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->d_taps, (c2<double> *)c.d_H, e->L, 1, (double *)nullptr);
+        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->b_taps.p, (c2<double> *)c.d_H, e->L, 1, (double *)nullptr);
     HIPCHK(hipGetLastError());
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     e->coeffs.push_back(c);
@@ -3107,19 +1837,15 @@ int bfhip_engine_read_coeff_processed(bfhip_engine *e, int coeff, void *cbufs) {
     { const int rr = coeff_make_resident(e, coeff); if (rr != BFHIP_OK) return rr; }
     const int nb = e->coeffs[coeff].n_blocks;
     const size_t bytes = (size_t)nb * 2 * e->L * e->rs;
-    if (bytes > e->taps_cap) {
-        if (e->d_taps) { { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; } (void)hipFree(e->d_taps); e->d_taps = nullptr; }
-        HIPCHK(dev_alloc(&e->d_taps, bytes));
-        e->taps_cap = bytes;
-    }
+    { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
     const dim3 grid((e->L + 255) / 256, nb);
     if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)nullptr, (c2<float> *)e->coeffs[coeff].d_H, e->L, 0, (float *)e->d_taps);
+        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)nullptr, (c2<float> *)e->coeffs[coeff].d_H, e->L, 0, (float *)e->b_taps.p);
     else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)nullptr, (c2<double> *)e->coeffs[coeff].d_H, e->L, 0, (double *)e->d_taps);
+        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)nullptr, (c2<double> *)e->coeffs[coeff].d_H, e->L, 0, (double *)e->b_taps.p);
     HIPCHK(hipGetLastError());
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    HIPCHK(hipMemcpy(cbufs, e->d_taps, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cbufs, e->b_taps.p, bytes, hipMemcpyDeviceToHost));
     return nb;
 }
 
@@ -3131,19 +1857,15 @@ int bfhip_engine_update_coeff_block(bfhip_engine *e, int coeff, int block, const
     HIPCHK(hipSetDevice(e->device));
     { const int rr = coeff_make_resident(e, coeff); if (rr != BFHIP_OK) return rr; }
     const size_t bytes = (size_t)e->L * e->rs;
-    if (bytes > e->taps_cap) {
-        if (e->d_taps) { { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; } (void)hipFree(e->d_taps); e->d_taps = nullptr; }
-        HIPCHK(dev_alloc(&e->d_taps, bytes));
-        e->taps_cap = bytes;
-    }
+    { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
-    HIPCHK(hipMemcpy(e->d_taps, taps, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->b_taps.p, taps, bytes, hipMemcpyHostToDevice));
     void *H = (unsigned char *)e->coeffs[coeff].d_H + (size_t)block * e->L * e->csize();
     hipError_t err = hipSuccess;
     if (e->big) {
         { int rr = big_reserve(e, 1); if (rr != BFHIP_OK) return rr; }
-        DISPATCH_BIG(launch_coeff_prep_big, e, e->d_taps, e->L, 1.0, H, 1, &err);
-    } else DISPATCH(launch_coeff_prep, e, e->d_taps, e->L, 1.0, H, 1, &err);
+        DISPATCH_BIG(launch_coeff_prep_big, e, e->b_taps.p, e->L, 1.0, H, 1, &err);
+    } else DISPATCH(launch_coeff_prep, e, e->b_taps.p, e->L, 1.0, H, 1, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "coeff_prep launch: %s", hipGetErrorString(err));
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     return e->rs == 4 ? stream_refresh_block<float>(e, e->coeffs[coeff].d_H, block)
@@ -3638,7 +2360,7 @@ static int finalize_impl(bfhip_engine *e) {
     {
         // long-window plan: structure here, the per-plan conditions in build_long_layout.  The size test
         // is on every set registered -- the whole configuration's, not a shard's share: a shard
-        // engine takes the long plan exactly when the one-process engine does (build_plan_t)
+        // engine takes the long plan exactly when the one-process engine does (plan_long_whole, plan.hip)
         int want = -1;
         if (const char *env = getenv("BFHIP_LONG_WINDOW")) want = atoi(env) != 0 ? 1 : 0;
         double vol = 0;
@@ -3747,9 +2469,8 @@ static int lw_drop(bfhip_engine *e) {
     { const int r = sync_all(e); if (r != BFHIP_OK) return r; }
     e->lw_struct = e->lw_active = e->la_active = e->far_active = false;
     e->la_epoch++;
-    for (void **p : {&e->d_hist, &e->d_lring, &e->d_lstream, &e->d_ahead, &e->d_far}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    e->lstream_cap = 0;
-    e->ahead_cap = e->far_cap = 0;
+    for (void **p : {&e->d_hist, &e->d_lring}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    e->b_lstream.release(); e->b_ahead.release(); e->b_far.release();
     e->lstream = StreamLayout{nullptr, 0, 0, 0};
     e->lkeys.clear();
     for (bool &z : e->zp_long) z = false;
