@@ -1,4 +1,5 @@
-// bfhip.hip -- host side of the engine + the C ABI of include/bfhip.h (the plan builder: plan.hip).
+// bfhip.hip -- host side of the engine + the C ABI of include/bfhip.h (the plan builder: plan.hip; the
+// channel stage around the transforms: channels.hip).
 //
 // What the reference's filter_process() does with host buffers and a chain of convolver_*
 // calls per filter (bfrun.c:1493-2008) is turned into a static device plan here:
@@ -235,8 +236,8 @@ void launch_ifft_out_wave(bfhip_engine *e, const void *Zp, size_t chunk_stride, 
     *err = allow_lds(k, lds);
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(k, dim3(count), dim3(NT), lds, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, first, e->d_fmt[1], e->d_over, (const unsigned char *)e->d_skip_quant,
-                       raw, e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr,
+                       n_chunks, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
+                       raw, e->ch.timeout<T>(first, e->L),
                        (const c2<T> *)e->d_tww, e->safety_limit, e->d_status);
     *err = hipGetLastError();
 }
@@ -252,8 +253,8 @@ void launch_io_wave(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(k, dim3(count + e->n_ch[0]), dim3(NT), lds, e->ls, count,
                        (const c2<T> *)Zp, chunk_stride, n_chunks, first, e->d_fmt[1], e->d_over,
-                       (const unsigned char *)e->d_skip_quant, rawout,
-                       e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr,
+                       e->ch.skip_quant(), rawout,
+                       e->ch.timeout<T>(first, e->L),
                        e->safety_limit, e->d_status,
                        rawin, e->d_fmt[0], (T *)e->d_prev, (c2<T> *)e->d_ring, e->R, slot,
                        (const c2<T> *)e->d_tww, ps_arg(e), (const BlockState *)e->bs_arg);
@@ -273,29 +274,6 @@ void launch_coeff_prep(bfhip_engine *e, const void *taps, int n_taps, double sca
     *err = hipGetLastError();
 }
 
-// the HP-TPDF pass over the channels of [first, first+count) that dither (after K3)
-template <typename T>
-void launch_dither(bfhip_engine *e, int first, int count, uint8_t *raw, hipError_t *err, bool late = false) {
-    if (e->dither_channels.empty()) return;
-    // dither slots whose channel lies in [first, first+count) (the slots are sorted by channel), in
-    // runs of the requested phase: straight after K3, or after the N:1 mix / sub-sample filter
-    const int n = (int)e->dither_channels.size();
-    for (int s0 = 0; s0 < n;) {
-        const bool in = e->dither_channels[s0] >= first && e->dither_channels[s0] < first + count &&
-                        (bool)e->dither_late[s0] == late;
-        if (!in) { s0++; continue; }
-        int s1 = s0 + 1;
-        while (s1 < n && e->dither_channels[s1] < first + count && (bool)e->dither_late[s1] == late) s1++;
-        hipLaunchKernelGGL(dither_kernel<T>, dim3(s1 - s0), dim3(64), 0, e->ls,
-                           (const T *)e->d_timeout, (const int *)e->d_dither_ch + s0,
-                           (DitherState<T> *)e->d_dither_state + s0, (const int8_t *)e->d_dither_table,
-                           (int)e->dither_table.size(), (const T *)e->d_randmap + 256,
-                           e->d_fmt[1], e->d_over, raw, e->L, e->safety_limit, e->d_status);
-        if ((*err = hipGetLastError()) != hipSuccess) return;
-        s0 = s1;
-    }
-}
-
 template <typename T, int LOG2L>
 void launch_ifft_out(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks,
                      int first, int count, uint8_t *raw, hipError_t *err) {
@@ -305,8 +283,8 @@ void launch_ifft_out(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n
     *err = allow_lds(k, lds);
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(k, dim3(count), dim3(NT), lds, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, first, e->d_fmt[1], e->d_over, (const unsigned char *)e->d_skip_quant,
-                       raw, e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr,
+                       n_chunks, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
+                       raw, e->ch.timeout<T>(first, e->L),
                        (const c2<T> *)e->d_tw, e->safety_limit, e->d_status);
     *err = hipGetLastError();          // (the dither pass behind it: do_outputs)
 }
@@ -320,8 +298,8 @@ void launch_io(bfhip_engine *e, const void *z, int first, int count, uint8_t *ra
     *err = allow_lds(k, lds);
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(k, dim3(count + e->n_ch[0]), dim3(NT), lds, e->ls, count,
-                       (const c2<T> *)z, first, e->d_fmt[1], e->d_over, (const unsigned char *)e->d_skip_quant,
-                       rawout, e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr,
+                       (const c2<T> *)z, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
+                       rawout, e->ch.timeout<T>(first, e->L),
                        e->safety_limit, e->d_status,
                        rawin, e->d_fmt[0], (T *)e->d_prev, (c2<T> *)e->d_ring, e->R, slot, (const c2<T> *)e->d_tw, ps_arg(e));
     *err = hipGetLastError();
@@ -499,7 +477,7 @@ void launch_io_long(bfhip_engine *e, const void *Zp, int count, uint8_t *rawout,
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(k, dim3(count + n_in), dim3(NT), lds, e->ls, count, (const c2<float> *)Zp,
                        (size_t)e->n_out_padded * 2 * e->L, e->lw_chunks, 0, e->d_fmt[1], e->d_over,
-                       (const unsigned char *)e->d_skip_quant, rawout, e->safety_limit, e->d_status,
+                       e->ch.skip_quant(), rawout, e->safety_limit, e->d_status,
                        (const float *)e->d_prev, (float *)e->d_hist, (c2<float> *)e->d_lring, e->R, e->blockcounter,
                        (const c2<float> *)e->d_tw14, (const BlockState *)e->bs_arg);
     *err = hipGetLastError();
@@ -634,8 +612,8 @@ void launch_ifft_out_big(bfhip_engine *e, const void *Zp, size_t chunk_stride, i
     big_fft<T>(e, count, true, e->ls, err);
     if (*err != hipSuccess) return;
     hipLaunchKernelGGL(big_out_post<T>, dim3(count), dim3(1024), 0, e->ls, (const c2<T> *)e->b_big[2].p, first, e->d_fmt[1],
-                       e->d_over, (const unsigned char *)e->d_skip_quant, raw,
-                       e->d_timeout ? (T *)e->d_timeout + (size_t)first * e->L : (T *)nullptr, e->L, e->safety_limit,
+                       e->d_over, e->ch.skip_quant(), raw,
+                       e->ch.timeout<T>(first, e->L), e->L, e->safety_limit,
                        e->d_status);
     *err = hipGetLastError();          // (the dither pass behind it: do_outputs)
 }
@@ -700,51 +678,8 @@ size_t raw_extent(const std::vector<bfhip_format> &v, int n, int L) {
     return m;
 }
 
-DevFormat to_dev(const bfhip_format &f) {
-    DevFormat d;
-    d.isfloat = f.isfloat; d.swap = f.swap; d.bytes = f.bytes; d.sbytes = f.sbytes;
-    d.sample_spacing = f.sample_spacing; d.byte_offset = f.byte_offset;
-    d.alt = nullptr;
-    return d;
-}
-
 double overflow_max(const bfhip_format &f) {             // bfrun.c:2270-2277
     return f.isfloat ? 1.0 : (double)((uint64_t)1 << ((f.sbytes << 3) - 1)) - 1;
-}
-
-int upload_formats(bfhip_engine *e) {
-    for (int io = 0; io < 2; io++) {
-        // the device tables are indexed by VIRTUAL channel and hold the physical channel's format
-        std::vector<DevFormat> d;
-        for (int v = 0; v < e->n_ch[io]; v++) {
-            DevFormat f = to_dev(e->fmt[io][e->v2p[io][v]]);
-            if (io == 0 && e->n_vpp[0][e->v2p[0][v]] > 1) {
-                // a private, delayed copy of the samples (bfrun.c:1509-1531), contiguous
-                size_t k = 0;
-                while (e->vin_list[k] != v) k++;
-                f.alt = e->d_incopy + k * (size_t)e->L * 8;
-                f.sample_spacing = 1;
-                f.byte_offset = 0;
-            }
-            if (e->wide[io]) {
-                // the transforms read / write the planar copy: channel p's L words, contiguous
-                const int ph = e->v2p[io][v];
-                f.sample_spacing = 1;
-                if (io == 0) { f.alt = e->d_planar[0] + (size_t)ph * e->L * f.bytes; f.byte_offset = 0; }
-                else f.byte_offset = (int)((size_t)ph * e->L * f.bytes);       // relative to d_planar[1], the `raw` of the output kernels
-            }
-            if (io == 0 && e->sd_slot[0][v] >= 0) {
-                // sub-sample filtered: K1 reads the filtered reals (the conversion from the
-                // raw format happened in the filter pass)
-                f.alt = (const uint8_t *)e->d_sdin + (size_t)e->sd_slot[0][v] * e->L * e->rs;
-                f.isfloat = 1; f.swap = 0; f.bytes = e->rs; f.sbytes = e->rs;
-                f.sample_spacing = 1; f.byte_offset = 0;
-            }
-            d.push_back(f);
-        }
-        if (!d.empty()) HIPCHK(hipMemcpy(e->d_fmt[io], d.data(), d.size() * sizeof(DevFormat), hipMemcpyHostToDevice));
-    }
-    return BFHIP_OK;
 }
 
 int check_format(const bfhip_format *f) {
@@ -848,188 +783,8 @@ int ensure_ready(bfhip_engine *e) {
     return BFHIP_OK;
 }
 
-bool side_uses_subdelay(const bfhip_engine *e, int io) {
-    if (e->sdf_length <= 0) return false;
-    for (int s : e->sd_slot[io]) if (s >= 0) return true;
-    return false;
-}
-
-// sub-sample delay of the channels that have a filter (bfrun.c:1503-1508 apply_subdelay, :1921-1925)
-template <typename T>
-int do_subdelay_t(bfhip_engine *e, int io, const void *rawin_dev) {
-    std::vector<SdJob<T>> jobs;
-    for (int v = 0; v < e->n_ch[io]; v++) {
-        const int slot = e->sd_slot[io][v];
-        if (slot < 0) continue;
-        // an output another engine converts is not filtered here: nobody mixes or quantises it in this
-        // engine, and an engine that owns no such output at all has no time-sample buffer either
-        if (io == 1 && (!e->out_active[v] || e->d_timeout == nullptr)) continue;
-        SdJob<T> j;
-        memset(&j, 0, sizeof(j));
-        const int sd = e->subdelay[io][v];
-        j.taps = (sd > -100 && sd < 100) ? (const T *)e->d_sd_bank + (size_t)(99 + sd) * e->sd_flen : nullptr;
-        j.rest = (T *)e->d_sd_rest[io] + (size_t)slot * e->sd_bs;
-        if (io == 0) {
-            const bfhip_format &f = e->fmt[0][e->v2p[0][v]];
-            j.fmt = to_dev(f);
-            if (e->n_vpp[0][e->v2p[0][v]] > 1) {              // the delayed private copy
-                size_t k = 0;
-                while (e->vin_list[k] != v) k++;
-                j.raw = e->d_incopy + k * (size_t)e->L * 8;
-                j.fmt.sample_spacing = 1; j.fmt.byte_offset = 0;
-            } else {
-                j.raw = (const uint8_t *)rawin_dev;
-            }
-            j.dst = (T *)e->d_sdin + (size_t)slot * e->L;
-        } else {
-            j.src = (const T *)e->d_timeout + (size_t)v * e->L;
-            j.dst = (T *)e->d_timeout + (size_t)v * e->L;
-        }
-        jobs.push_back(j);
-    }
-    if (jobs.empty()) return BFHIP_OK;
-    uint8_t *pin = nullptr;
-    HIPCHK(e->st_sd[io].take(&pin));
-    memcpy(pin, jobs.data(), jobs.size() * sizeof(SdJob<T>));
-    HIPCHK(hipMemcpyAsync(e->d_sdjobs[io], pin, jobs.size() * sizeof(SdJob<T>), hipMemcpyHostToDevice, e->ls));
-    HIPCHK(e->st_sd[io].queued(e->ls));
-    const int tile = sd_tile_frames(e->L, e->sd_bs, (int)sizeof(T));        // > 0: enable_subdelay
-    const size_t lds = (size_t)(e->sd_bs + tile) * sizeof(T);
-    auto k = subdelay_fir_kernel<T>;
-    HIPCHK(allow_lds(k, lds));
-    hipLaunchKernelGGL(k, dim3((unsigned)jobs.size()), dim3(256), lds, e->ls, (const SdJob<T> *)e->d_sdjobs[io], e->L, e->sd_bs, e->sd_flen, tile);
-    HIPCHK(hipGetLastError());
-    return BFHIP_OK;
-}
-
-int do_subdelay(bfhip_engine *e, int io, const void *rawin_dev) {
-    if (e->sdf_length <= 0) return BFHIP_OK;
-    return e->rs == 4 ? do_subdelay_t<float>(e, io, rawin_dev) : do_subdelay_t<double>(e, io, rawin_dev);
-}
-
-// N:1 inputs: gather + mute + integer delay into the private copies K1 reads (bfrun.c:1509-1531)
-int do_vin(bfhip_engine *e, const void *rawin_dev) {
-    if (e->vin_list.empty()) return BFHIP_OK;
-    std::vector<VInJob> jobs;
-    std::vector<ByteOp> ops;
-    for (size_t k = 0; k < e->vin_list.size(); k++) {
-        const int v = e->vin_list[k];
-        const bfhip_format &f = e->fmt[0][e->v2p[0][v]];
-        VInJob j;
-        j.copy = e->d_incopy + k * (size_t)e->L * 8;
-        j.byte_offset = f.byte_offset; j.sample_spacing = f.sample_spacing; j.bytes = f.bytes;
-        j.muted = e->vmuted[0][v];
-        j.ops_off = (int)ops.size();
-        const int extra = (side_uses_subdelay(e, 0) && e->sd_slot[0][v] < 0) ? e->sdf_length : 0;   // bfrun.c:1512-1516
-        if (!j.muted) e->vline[0][v].update(j.copy, e->vdelay[0][v] + extra, ops);   // not advanced when muted
-        j.n_ops = (int)ops.size() - j.ops_off;
-        jobs.push_back(j);
-    }
-    const size_t jb = jobs.size() * sizeof(VInJob), ob = ops.size() * sizeof(ByteOp);
-    if (jb + ob > e->vjobs_slot) return fail(BFHIP_ESTATE, "virtual-channel job table overflow");
-    unsigned char *dev = (unsigned char *)e->d_vjobs;
-    uint8_t *pin = nullptr;
-    HIPCHK(e->st_vin.take(&pin));
-    memcpy(pin, jobs.data(), jb);
-    if (ob) memcpy(pin + jb, ops.data(), ob);
-    HIPCHK(hipMemcpyAsync(dev, pin, jb + ob, hipMemcpyHostToDevice, e->ls));
-    HIPCHK(e->st_vin.queued(e->ls));
-    hipLaunchKernelGGL(vchan_in_kernel<0>, dim3((unsigned)jobs.size()), dim3(256), 0, e->ls,
-                       (const VInJob *)dev, (const ByteOp *)(dev + jb), (const uint8_t *)rawin_dev, e->L);
-    HIPCHK(hipGetLastError());
-    return BFHIP_OK;
-}
-
-// N:1 outputs: integer delay of every member, mix of the un-muted ones, one requantisation
-// (bfrun.c:1938-2003); runs after K3 has left the members' time samples in d_timeout
-int do_vout(bfhip_engine *e, void *rawout_dev) {
-    if (e->vout_groups.empty()) return BFHIP_OK;
-    std::vector<VOutJob> jobs;
-    std::vector<VOutMember> mem;
-    std::vector<ByteOp> ops;
-    for (auto &g : e->vout_groups) {
-        VOutJob j;
-        j.first_member = (int)mem.size(); j.n_members = (int)g.size(); j.fmt_channel = g[0]; j.dither = 0;
-        for (size_t d = 0; d < e->dither_channels.size(); d++)
-            if (e->dither_channels[d] == g[0] && e->dither_late[d]) j.dither = 1;
-        for (int v : g) {
-            VOutMember m;
-            // a 1:1 output is here for its sub-sample filter only: its delay and mute are dai.c's business
-            // on the raw buffer (bfrun.c:1926-1936 converts it whatever icomm says)
-            const bool shared = g.size() > 1;
-            m.channel = v; m.muted = shared ? e->vmuted[1][v] : 0; m.ops_off = (int)ops.size();
-            uint8_t *row = (uint8_t *)e->d_timeout + (size_t)v * e->L * e->rs;
-            const int extra = (side_uses_subdelay(e, 1) && e->sd_slot[1][v] < 0 && shared) ? e->sdf_length : 0;
-            e->vline[1][v].update(row, shared ? e->vdelay[1][v] + extra : 0, ops);        // always advanced (:1948)
-            m.n_ops = (int)ops.size() - m.ops_off;
-            mem.push_back(m);
-        }
-        jobs.push_back(j);
-    }
-    const size_t jb = jobs.size() * sizeof(VOutJob), mb = mem.size() * sizeof(VOutMember), ob = ops.size() * sizeof(ByteOp);
-    if (jb + mb + ob > e->vjobs_slot) return fail(BFHIP_ESTATE, "virtual-channel job table overflow");
-    unsigned char *dev = (unsigned char *)e->d_vjobs + e->vjobs_slot;      // second half: output side
-    uint8_t *pin = nullptr;
-    HIPCHK(e->st_vout.take(&pin));
-    memcpy(pin, jobs.data(), jb);
-    memcpy(pin + jb, mem.data(), mb);
-    if (ob) memcpy(pin + jb + mb, ops.data(), ob);
-    HIPCHK(hipMemcpyAsync(dev, pin, jb + mb + ob, hipMemcpyHostToDevice, e->ls));
-    HIPCHK(e->st_vout.queued(e->ls));
-    if (e->rs == 4)
-        hipLaunchKernelGGL(vchan_out_kernel<float>, dim3((unsigned)jobs.size()), dim3(256), 0, e->ls,
-                           (const VOutJob *)dev, (const VOutMember *)(dev + jb), (const ByteOp *)(dev + jb + mb),
-                           (float *)e->d_timeout, e->d_fmt[1], e->d_over, (uint8_t *)rawout_dev, e->L, e->safety_limit, e->d_status);
-    else
-        hipLaunchKernelGGL(vchan_out_kernel<double>, dim3((unsigned)jobs.size()), dim3(256), 0, e->ls,
-                           (const VOutJob *)dev, (const VOutMember *)(dev + jb), (const ByteOp *)(dev + jb + mb),
-                           (double *)e->d_timeout, e->d_fmt[1], e->d_over, (uint8_t *)rawout_dev, e->L, e->safety_limit, e->d_status);
-    HIPCHK(hipGetLastError());
-    bool any_late = false;
-    for (char c : e->dither_late) any_late = any_late || c;
-    if (any_late) {
-        hipError_t err = hipSuccess;
-        if (e->rs == 4) launch_dither<float>(e, 0, e->n_ch[1], (uint8_t *)rawout_dev, &err, true);
-        else launch_dither<double>(e, 0, e->n_ch[1], (uint8_t *)rawout_dev, &err, true);
-        if (err != hipSuccess) return fail(BFHIP_EHIP, "dither launch: %s", hipGetErrorString(err));
-        hipLaunchKernelGGL(vout_spread_overflow_kernel<0>, dim3((unsigned)jobs.size()), dim3(64), 0, e->ls,
-                           (const VOutJob *)dev, (const VOutMember *)(dev + jb), e->d_over);
-        HIPCHK(hipGetLastError());
-    }
-    return BFHIP_OK;
-}
-
-// ---- wide interleaved sides: frames <-> planar copy (transpose_words_kernel)
-int launch_transpose(bfhip_engine *e, int io, const void *src, void *dst, int to_planar, int first, int count) {
-    const int rows = e->L, cols = e->n_phys[io], bytes = e->fmt[io][0].bytes;
-    const dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-    const unsigned char *skip = io == 1 ? e->d_phys_skip : nullptr;
-    if (bytes == 4)
-        hipLaunchKernelGGL(transpose_words_kernel<uint32_t>, grid, dim3(256), 0, e->ls, (const uint32_t *)src, (uint32_t *)dst, rows, cols, to_planar, skip, first, count);
-    else if (bytes == 2)
-        hipLaunchKernelGGL(transpose_words_kernel<uint16_t>, grid, dim3(256), 0, e->ls, (const uint16_t *)src, (uint16_t *)dst, rows, cols, to_planar, skip, first, count);
-    else
-        hipLaunchKernelGGL(transpose_words_kernel<uint64_t>, grid, dim3(256), 0, e->ls, (const uint64_t *)src, (uint64_t *)dst, rows, cols, to_planar, skip, first, count);
-    HIPCHK(hipGetLastError());
-    return BFHIP_OK;
-}
-// in front of every launch that transforms inputs
-int pre_inputs(bfhip_engine *e, const void *rawin_dev) {
-    return e->wide[0] ? launch_transpose(e, 0, rawin_dev, e->d_planar[0], 1, 0, e->n_phys[0]) : BFHIP_OK;
-}
-// what the output kernels get as `raw`, and the pass behind them (virtual channels [first, first+count))
-uint8_t *k3_target(bfhip_engine *e, void *rawout_dev) { return e->wide[1] ? e->d_planar[1] : (uint8_t *)rawout_dev; }
-int post_outputs(bfhip_engine *e, void *rawout_dev, int first, int count) {
-    if (!e->wide[1]) return BFHIP_OK;
-    int p0 = e->n_phys[1], p1 = -1;
-    for (int v = first; v < first + count; v++) { p0 = std::min(p0, e->v2p[1][v]); p1 = std::max(p1, e->v2p[1][v]); }
-    return p1 < p0 ? BFHIP_OK : launch_transpose(e, 1, e->d_planar[1], rawout_dev, 0, p0, p1 - p0 + 1);
-}
-
 int do_inputs(bfhip_engine *e, const void *rawin_dev, unsigned int ahead = 0u /* blocks ahead of the counter (block pairs) */) {
-    { int rv = pre_inputs(e, rawin_dev); if (rv != BFHIP_OK) return rv; }
-    { int rv = do_vin(e, rawin_dev); if (rv != BFHIP_OK) return rv; }
-    { int rv = do_subdelay(e, 0, rawin_dev); if (rv != BFHIP_OK) return rv; }
+    { int rv = channels_before_k1(e, rawin_dev); if (rv != BFHIP_OK) return rv; }
     hipError_t err = hipSuccess;
     const int slot = (int)((e->blockcounter + ahead) % (unsigned int)e->R);
     if (e->big) { int rr = big_reserve(e, (size_t)e->n_ch[0]); if (rr != BFHIP_OK) return rr; }
@@ -1103,7 +858,7 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
                int count, void *rawout_dev) {
     hipError_t err = hipSuccess;
     if (count <= 0) return BFHIP_OK;
-    if (!e->vout_groups.empty() && (first != 0 || count != e->n_ch[1]))
+    if (e->ch.outputs_at_once() && (first != 0 || count != e->n_ch[1]))
         return fail(BFHIP_EINVAL, "outputs that share a physical channel cannot be split over several calls");
     const bool lng = zp_is_long(e, Zp);
     if (lng && (first != 0 || count != e->n_ch[1]))
@@ -1116,32 +871,26 @@ int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunk
         { const int rr = sum_chunks(e, Zp, const_cast<void *>(Zp)); if (rr != BFHIP_OK) return rr; }
         n_chunks = 1;
     }
-    void *const user_out = rawout_dev;
-    rawout_dev = k3_target(e, rawout_dev);
+    uint8_t *const raw = k3_target(e, rawout_dev);
     if (e->big) { int rr = big_reserve(e, (size_t)count); if (rr != BFHIP_OK) return rr; }
-    // what follows the inverse transforms as launches of its own (dither chains, N:1 mix, sub-sample
-    // delay) is timed apart: the reference's real2raw column
-    const bool post = !e->dither_channels.empty() || !e->vout_groups.empty() || side_uses_subdelay(e, 1);
-    if (lng) launch_io_long(e, Zp, count, (uint8_t *)rawout_dev, false, &err);
-    else if (e->big) DISPATCH_BIG(launch_ifft_out_big, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
-    else if (e->wave) { DISPATCH_WAVE(launch_ifft_out_wave, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err) }
-    else DISPATCH(launch_ifft_out, e, Zp, chunk_stride, n_chunks, first, count, (uint8_t *)rawout_dev, &err);
+    if (lng) launch_io_long(e, Zp, count, raw, false, &err);
+    else if (e->big) DISPATCH_BIG(launch_ifft_out_big, e, Zp, chunk_stride, n_chunks, first, count, raw, &err);
+    else if (e->wave) { DISPATCH_WAVE(launch_ifft_out_wave, e, Zp, chunk_stride, n_chunks, first, count, raw, &err) }
+    else DISPATCH(launch_ifft_out, e, Zp, chunk_stride, n_chunks, first, count, raw, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "ifft_out launch: %s", hipGetErrorString(err));
+    // what the channel stage launches behind the inverse transforms is timed apart: the reference's real2raw column
+    const bool post = e->ch.follows_k3();
     if (post) { const int rr = record_begin(e, T_POST); if (rr != BFHIP_OK) return rr; }
-    if (e->rs == 4) launch_dither<float>(e, first, count, (uint8_t *)rawout_dev, &err);
-    else launch_dither<double>(e, first, count, (uint8_t *)rawout_dev, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "dither launch: %s", hipGetErrorString(err));
-    { int rv = do_subdelay(e, 1, nullptr); if (rv != BFHIP_OK) return rv; }
-    { int rv = do_vout(e, rawout_dev); if (rv != BFHIP_OK) return rv; }
-    { int rv = post_outputs(e, user_out, first, count); if (rv != BFHIP_OK) return rv; }
+    { int rv = channels_after_k3(e, rawout_dev, first, count); if (rv != BFHIP_OK) return rv; }
     return post ? record_end(e, T_POST) : BFHIP_OK;
 }
 
-// [K3 of an owed block | K1 of this block] in one launch, with the transposes of wide sides around it
+// [K3 of an owed block | K1 of this block] in one launch; callers take this path only when the channel stage is
+// plain(), so that its two calls add nothing around the launch but the transposes of wide sides
 int fused_outputs_inputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first, int count,
                          void *rawout_dev, const void *rawin_dev) {
     int r;
-    if ((r = pre_inputs(e, rawin_dev)) != BFHIP_OK) return r;
+    if ((r = channels_before_k1(e, rawin_dev)) != BFHIP_OK) return r;
     hipError_t err = hipSuccess;
     const int slot = (int)(e->blockcounter % (unsigned int)e->R);
     // an owed long-window block: its output pass rides with the long transforms of this block instead
@@ -1154,7 +903,7 @@ int fused_outputs_inputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, i
     if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
     if (e->lw_struct) launch_io_long(e, Zp, lng ? count : 0, k3_target(e, rawout_dev), true, &err);
     if (err != hipSuccess) return fail(BFHIP_EHIP, "long io launch: %s", hipGetErrorString(err));
-    return post_outputs(e, rawout_dev, first, count);
+    return channels_after_k3(e, rawout_dev, first, count);
 }
 
 // The three passes of a block with their timing records, each on e->ls: a schedule switches streams
@@ -1254,7 +1003,7 @@ void rt_release(bfhip_engine *e) {
 bool rt_graphable(const bfhip_engine *e) {
     if ((e->rt.flags & (BFHIP_RT_NO_GRAPH | BFHIP_RT_OVERLAP)) || e->big) return false;
     // N:1 channels and sub-sample delays upload a per-block job table; a cross-fade lasts one block
-    return !e->has_vchan && !side_uses_subdelay(e, 0) && !side_uses_subdelay(e, 1) && !e->any_fading;
+    return !e->ch.has_vchan && !e->any_fading;
 }
 
 // Throughput with host buffers: upload of period t+1 and download of period t-1 on the copy
@@ -1331,36 +1080,6 @@ int rt_capture(bfhip_engine *e, int p) {
 
 }  // namespace
 
-namespace {
-
-// (the filters themselves: subdelay_filter.h, shared with the non-uniform convolver)
-int subdelay_setup(bfhip_engine *e) {
-    if (e->sdf_length <= 0) return BFHIP_OK;
-    int n_slots[2] = {0, 0};
-    for (int io = 0; io < 2; io++)
-        for (int v = 0; v < e->n_ch[io]; v++)
-            e->sd_slot[io][v] = e->subdelay[io][v] != -100 ? n_slots[io]++ : -1;      // bfrun.c:1133-1142
-    if (n_slots[0] + n_slots[1] == 0) { e->sdf_length = 0; return BFHIP_OK; }
-    // bank: index 99 + subdelay, subdelay in (-100, 100) hundredths of a sample (BF_SAMPLE_SLOTS)
-    const std::vector<unsigned char> bank = sd_make_bank(e->sdf_length, e->rs);
-    HIPCHK(dev_alloc(&e->d_sd_bank, bank.size()));
-    HIPCHK(hipMemcpy(e->d_sd_bank, bank.data(), bank.size(), hipMemcpyHostToDevice));
-    for (int io = 0; io < 2; io++) {
-        if (n_slots[io] == 0) continue;
-        HIPCHK(dev_alloc(&e->d_sd_rest[io], (size_t)n_slots[io] * e->sd_bs * e->rs));
-        HIPCHK(hipMemset(e->d_sd_rest[io], 0, (size_t)n_slots[io] * e->sd_bs * e->rs));
-        HIPCHK(dev_alloc(&e->d_sdjobs[io], (size_t)n_slots[io] * 128));
-        HIPCHK(e->st_sd[io].init((size_t)n_slots[io] * 128));
-    }
-    if (n_slots[0] > 0) {
-        HIPCHK(dev_alloc(&e->d_sdin, (size_t)n_slots[0] * e->L * e->rs));
-        HIPCHK(hipMemset(e->d_sdin, 0, (size_t)n_slots[0] * e->L * e->rs));
-    }
-    return BFHIP_OK;
-}
-
-}  // namespace
-
 // ==================================================================== C ABI
 
 extern "C" {
@@ -1405,17 +1124,7 @@ bfhip_engine *bfhip_engine_create(int device, int length, int n_blocks, int real
             f.sample_spacing = 1; f.byte_offset = c * length * realsize;
         }
     }
-    for (int io = 0; io < 2; io++) {
-        e->n_phys[io] = e->n_ch[io];
-        e->v2p[io].resize(e->n_ch[io]);
-        for (int c = 0; c < e->n_ch[io]; c++) e->v2p[io][c] = c;
-        e->n_vpp[io].assign(e->n_ch[io], 1);
-        e->vdelay[io].assign(e->n_ch[io], 0);
-        e->vmaxdelay[io].assign(e->n_ch[io], 0);
-        e->vmuted[io].assign(e->n_ch[io], 0);
-        e->subdelay[io].assign(e->n_ch[io], -100);       // BF_UNDEFINED_SUBDELAY
-        e->sd_slot[io].assign(e->n_ch[io], -1);
-    }
+    e->ch.init(e->n_ch);
     bool ok = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess;
     e->own_stream = ok;
     // twiddles exp(-2 pi i m / (2L)), computed in double, + their thread-ordered copy (fft_lds.h)
@@ -1463,13 +1172,8 @@ void bfhip_engine_destroy(bfhip_engine *e) {
     if (e->coeff_arena) { for (auto &sl : e->slabs) if (sl.base) (void)hipFree(sl.base); }
     else { for (auto &c : e->coeffs) if (c.d_H) (void)hipFree(c.d_H); }
     for (void *p : e->promoted) if (p && p != PROMOTED_ELSEWHERE) (void)hipFree(p);
-    for (int io = 0; io < 2; io++) for (auto &dl : e->vline[io]) if (dl.arena) (void)hipFree(dl.arena);
-    if (e->d_incopy) (void)hipFree(e->d_incopy);
-    { void *sp[] = {e->d_sd_bank, e->d_sd_rest[0], e->d_sd_rest[1], e->d_sdin, e->d_sdjobs[0], e->d_sdjobs[1]};
-      for (void *q : sp) if (q) (void)hipFree(q); }
+    e->ch.release();
     rt_release(e);
-    if (e->d_vjobs) (void)hipFree(e->d_vjobs);
-    e->st_vin.release(); e->st_vout.release(); e->st_sd[0].release(); e->st_sd[1].release();
     for (void *z : e->d_Zp) if (z) (void)hipFree(z);
     for (int i = 0; i < 2; i++) {
         if (e->ev_in[i]) (void)hipEventDestroy(e->ev_in[i]);
@@ -1484,10 +1188,8 @@ void bfhip_engine_destroy(bfhip_engine *e) {
     void *ptrs[] = {e->d_tw, e->d_prev, e->d_ring, e->d_fmt[0], e->d_fmt[1], e->d_over, e->d_status,
                     e->d_bad, e->d_rawin, e->d_rawout,
                     e->d_fring, e->d_Y, e->d_Yold, e->d_evalprev,
-                    e->d_dither_ch, e->d_dither_state, e->d_dither_table, e->d_randmap, e->d_skip_quant, e->d_timeout,
                     e->d_tw13, e->d_tww,
                     e->d_ps_flags, e->d_ps_live, e->d_ps_scale, e->d_ps_acc,
-                    e->d_planar[0], e->d_planar[1], e->d_phys_skip,
                     e->d_hist, e->d_lring, e->d_tw14};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (DevBuf *b : {&e->b_entries, &e->b_chunks, &e->b_jobs, &e->b_stream, &e->b_where, &e->b_lentries, &e->b_lchunks,
@@ -1499,7 +1201,7 @@ void bfhip_engine_destroy(bfhip_engine *e) {
 }
 
 int bfhip_engine_set_format(bfhip_engine *e, int io, int ch, const bfhip_format *bf) {
-    if (!e || !bf || io < 0 || io > 1 || ch < 0 || ch >= e->n_phys[io]) return fail(BFHIP_EINVAL, "set_format: bad argument");
+    if (!e || !bf || io < 0 || io > 1 || ch < 0 || ch >= e->ch.n_phys[io]) return fail(BFHIP_EINVAL, "set_format: bad argument");
     if (!check_format(bf)) return fail(BFHIP_EINVAL, "Sample byte size %d is not supported.", bf->bytes);
     if (e->finalized) return fail(BFHIP_ESTATE, "set_format after finalize");
     e->fmt[io][ch] = *bf;
@@ -1536,30 +1238,26 @@ int bfhip_engine_map_channels(bfhip_engine *e, int io, int n_phys, const int vir
         cnt[virt2phys[v]]++;
     }
     for (int c = 0; c < n_phys; c++) if (cnt[c] == 0) return fail(BFHIP_EINVAL, "map_channels: physical channel %d unused", c);
-    e->n_phys[io] = n_phys;
-    e->v2p[io].assign(virt2phys, virt2phys + e->n_ch[io]);
-    e->n_vpp[io] = cnt;
+    e->ch.n_phys[io] = n_phys;
+    e->ch.v2p[io].assign(virt2phys, virt2phys + e->n_ch[io]);
+    e->ch.n_vpp[io] = cnt;
     return BFHIP_OK;
 }
 
+// one value of one virtual channel; `fixed`: not after finalize
+static int set_channel(bfhip_engine *e, int io, int ch, const char *what, bool fixed, std::vector<int> (Channels::*field)[2], int value) {
+    if (!e || io < 0 || io > 1 || ch < 0 || ch >= e->n_ch[io]) return fail(BFHIP_EINVAL, "%s: bad argument", what);
+    if (fixed && e->finalized) return fail(BFHIP_ESTATE, "%s after finalize", what);
+    (e->ch.*field)[io][ch] = value;
+    return BFHIP_OK;
+}
 int bfhip_engine_set_delay(bfhip_engine *e, int io, int ch, int delay) {
-    if (!e || io < 0 || io > 1 || ch < 0 || ch >= e->n_ch[io] || delay < 0) return fail(BFHIP_EINVAL, "set_delay: bad argument");
-    e->vdelay[io][ch] = delay;
-    return BFHIP_OK;
+    if (delay < 0) return fail(BFHIP_EINVAL, "set_delay: bad argument");
+    return set_channel(e, io, ch, "set_delay", false, &Channels::vdelay, delay);
 }
-
-int bfhip_engine_set_maxdelay(bfhip_engine *e, int io, int ch, int maxdelay) {
-    if (!e || io < 0 || io > 1 || ch < 0 || ch >= e->n_ch[io]) return fail(BFHIP_EINVAL, "set_maxdelay: bad argument");
-    if (e->finalized) return fail(BFHIP_ESTATE, "set_maxdelay after finalize");
-    e->vmaxdelay[io][ch] = maxdelay;
-    return BFHIP_OK;
-}
-
-int bfhip_engine_set_mute(bfhip_engine *e, int io, int ch, int muted) {
-    if (!e || io < 0 || io > 1 || ch < 0 || ch >= e->n_ch[io]) return fail(BFHIP_EINVAL, "set_mute: bad argument");
-    e->vmuted[io][ch] = muted != 0;
-    return BFHIP_OK;
-}
+int bfhip_engine_set_maxdelay(bfhip_engine *e, int io, int ch, int maxdelay) { return set_channel(e, io, ch, "set_maxdelay", true, &Channels::vmaxdelay, maxdelay); }
+int bfhip_engine_set_mute(bfhip_engine *e, int io, int ch, int muted) { return set_channel(e, io, ch, "set_mute", false, &Channels::vmuted, muted != 0); }
+int bfhip_engine_set_subdelay(bfhip_engine *e, int io, int ch, int subdelay) { return set_channel(e, io, ch, "set_subdelay", false, &Channels::subdelay, subdelay); }
 
 int bfhip_engine_enable_subdelay(bfhip_engine *e, int sdf_length, double kaiser_beta) {
     (void)kaiser_beta;       // parsed by the reference (sdf_beta) but its filters are built with 9 (delay.c:73)
@@ -1574,13 +1272,7 @@ int bfhip_engine_enable_subdelay(bfhip_engine *e, int sdf_length, double kaiser_
     if (sd_tile_frames(e->L, bs, e->rs) == 0)
         return fail(BFHIP_EINVAL, "sdf_length %d is too long for the sub-sample delay filter: its %d-frame history "
                                   "leaves no room in %d KiB of LDS.", sdf_length, bs, SD_LDS_BYTES / 1024);
-    e->sdf_length = sdf_length; e->sd_flen = 2 * sdf_length + 1; e->sd_bs = bs;
-    return BFHIP_OK;
-}
-
-int bfhip_engine_set_subdelay(bfhip_engine *e, int io, int ch, int subdelay) {
-    if (!e || io < 0 || io > 1 || ch < 0 || ch >= e->n_ch[io]) return fail(BFHIP_EINVAL, "set_subdelay: bad argument");
-    e->subdelay[io][ch] = subdelay;
+    e->ch.sdf_length = sdf_length; e->ch.sd_flen = 2 * sdf_length + 1; e->ch.sd_bs = bs;
     return BFHIP_OK;
 }
 
@@ -1590,26 +1282,15 @@ int bfhip_engine_enable_dither(bfhip_engine *e, const int out_channels[], int n,
     if (e->finalized) return fail(BFHIP_ESTATE, "enable_dither after finalize");
     std::vector<int> chs(out_channels, out_channels + n);
     for (int i = 0; i < n; i++) {
-        if (chs[i] < 0 || chs[i] >= e->n_phys[1]) return fail(BFHIP_EINVAL, "enable_dither: output channel %d", chs[i]);
+        if (chs[i] < 0 || chs[i] >= e->ch.n_phys[1]) return fail(BFHIP_EINVAL, "enable_dither: output channel %d", chs[i]);
         if (i > 0 && chs[i] <= chs[i - 1]) return fail(BFHIP_EINVAL, "enable_dither: channels must be ascending");
         if (e->fmt[1][chs[i]].isfloat) return fail(BFHIP_EINVAL, "cannot dither floating point format (output %d)", chs[i]);
     }
     // dither_init (dither.c:75-139): table spacing, Tausworthe bytes
-    const std::string msg = dither_make_table(n, sample_rate, max_size, e->L, &e->dither_spacing, &e->dither_table);
+    const std::string msg = dither_make_table(n, sample_rate, max_size, e->L, &e->ch.dither_spacing, &e->ch.dither_table);
     if (!msg.empty()) return fail(BFHIP_EINVAL, "%s", msg.c_str());
-    e->dither_channels = chs;
+    e->ch.dither_channels = chs;
     return BFHIP_OK;
-}
-
-static int dither_upload(bfhip_engine *e) {
-    const int n = (int)e->dither_channels.size();
-    if (n == 0) return BFHIP_OK;
-    HIPCHK(dev_alloc((void **)&e->d_dither_ch, n * sizeof(int)));
-    HIPCHK(hipMemcpy(e->d_dither_ch, e->dither_channels.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    // table, randmap, per-slot states (ptr = rank * spacing + 1, error feedback zero)
-    HIPCHK(dither_upload_tables(e->dither_table, e->dither_spacing, e->dither_rank, e->rs, &e->d_dither_table,
-                                &e->d_randmap, &e->d_dither_state));
-    return BFHIP_OK;             // d_skip_quant / d_timeout: allocated with the channel set-up in finalize
 }
 
 static int add_coeff_common(bfhip_engine *e, const void *taps, bool on_device, int n_taps,
@@ -2024,7 +1705,7 @@ static int resolve_shard(bfhip_engine *e) {
     // virtual outputs that share a physical channel are mixed in the time domain by ONE engine
     for (int o = 0; o < O; o++)
         for (int q = o + 1; q < O; q++)
-            if (e->v2p[1][o] == e->v2p[1][q] && e->out_active[o] != e->out_active[q])
+            if (e->ch.v2p[1][o] == e->ch.v2p[1][q] && e->out_active[o] != e->out_active[q])
                 return fail(BFHIP_EINVAL, "outputs %d and %d share a physical channel: one engine must own both", o, q);
     return BFHIP_OK;
 }
@@ -2035,9 +1716,9 @@ static void build_owned_runs(bfhip_engine *e) {
     e->owned_runs.clear();
     if (!e->sharded) return;
     std::vector<bfhip_engine::OwnedRun> runs;
-    std::vector<char> seen(e->n_phys[1], 0);
+    std::vector<char> seen(e->ch.n_phys[1], 0);
     for (int o = 0; o < e->n_ch[1]; o++) {
-        const int p = e->v2p[1][o];
+        const int p = e->ch.v2p[1][o];
         if (!e->out_active[o] || seen[p]) continue;
         seen[p] = 1;
         const bfhip_format &f = e->fmt[1][p];
@@ -2093,11 +1774,9 @@ static int choose_mode(const bfhip_engine *e) {
     // (the environment only moves the AUTOMATIC choice: an explicit bfhip_engine_set_overlap wins --
     // the non-uniform convolver depends on its segment engines running strictly in order)
     if (const char *env = e->overlap_mode < 0 ? getenv("BFHIP_OVERLAP") : nullptr) pipe = atoi(env) != 0;
-    bool one_to_one = true;
-    for (int io = 0; io < 2; io++) for (int c : e->n_vpp[io]) if (c > 1) one_to_one = false;
-    if (!one_to_one || e->big) pipe = false;   // one job table per side; one FFT scratch
+    if (!e->ch.one_to_one() || e->big) pipe = false;   // one job table per side; one FFT scratch
     // the fused [K3 | K1] launch of deferred output and ping-pong needs the plain 1:1 raw path
-    const bool plain = e->wave && !e->big && e->sdf_length <= 0 && e->dither_channels.empty() && one_to_one;
+    const bool plain = e->wave && !e->big && e->ch.configured_plain();
     // one stream and a MAC that fills the chip for a long time: deferred output.  (An explicit
     // bfhip_engine_set_overlap(e, 0) -- "strictly in order" -- beats the environment.)
     bool defer = !pipe && plain && e->overlap_mode != 0;
@@ -2148,7 +1827,7 @@ static int finalize_impl(bfhip_engine *e) {
         {
             std::vector<int> ones((size_t)e->n_ch[0] * e->R, 1);     // the zeroed rings are silence
             std::vector<double> sc(e->n_ch[0]);
-            for (int c = 0; c < e->n_ch[0]; c++) sc[c] = e->fmt[0][e->v2p[0][c]].scale;
+            for (int c = 0; c < e->n_ch[0]; c++) sc[c] = e->fmt[0][e->ch.v2p[0][c]].scale;
             HIPCHK(dev_alloc((void **)&e->d_ps_flags, ones.size() * sizeof(int)));
             HIPCHK(hipMemcpy(e->d_ps_flags, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
             HIPCHK(dev_alloc((void **)&e->d_ps_live, e->n_ch[0] * sizeof(int)));
@@ -2158,149 +1837,13 @@ static int finalize_impl(bfhip_engine *e) {
         }
     }
     for (int io = 0; io < 2; io++) HIPCHK(dev_alloc((void **)&e->d_fmt[io], e->n_ch[io] * sizeof(DevFormat)));
-    { int rs_ = subdelay_setup(e); if (rs_ != BFHIP_OK) return rs_; }
-    // channels that share a physical channel: private copies, delay lines, job tables
-    {
-        e->vin_list.clear(); e->vout_groups.clear();
-        for (int v = 0; v < e->n_ch[0]; v++) if (e->n_vpp[0][e->v2p[0][v]] > 1) e->vin_list.push_back(v);
-        // the members of a shared physical output are mixed in ascending virtual order, the order
-        // in which the reference walks phys2virt (bfrun.c:2322-2323, 1938-2003); any mapping is
-        // legal (bench4_config: `mapping: 0,1,0,1,0,1`)
-        std::map<int, std::vector<int>> shared;
-        for (int v = 0; v < e->n_ch[1]; v++) {
-            if (e->n_vpp[1][e->v2p[1][v]] <= 1) {
-                // a 1:1 output with a sub-sample filter is requantised after the filter: a group of one
-                if (e->sd_slot[1][v] >= 0) e->vout_groups.push_back({v});
-                continue;
-            }
-            shared[e->v2p[1][v]].push_back(v);
-        }
-        for (auto &kv : shared) e->vout_groups.push_back(kv.second);
-        // (groups of outputs another engine converts: not ours to mix -- resolve_shard made sure a
-        // group is owned as a whole)
-        e->vout_groups.erase(std::remove_if(e->vout_groups.begin(), e->vout_groups.end(),
-                                            [&](const std::vector<int> &g) { return !e->out_active[g[0]]; }),
-                             e->vout_groups.end());
-        e->has_vchan = !e->vin_list.empty() || !e->vout_groups.empty() || e->sdf_length > 0;
-        // enable_dither named PHYSICAL outputs (bfconf->dither_state[physch], bfrun.c:1933): from
-        // here on the list holds the virtual channel behind each of them
-        {
-            std::vector<std::pair<int, int>> byvirt;            // (virtual channel, rank in the physical list)
-            for (size_t i = 0; i < e->dither_channels.size(); i++) {
-                const int c = e->dither_channels[i];
-                if (c < 0 || c >= e->n_phys[1]) return fail(BFHIP_EINVAL, "dither: output %d does not exist", c);
-                int v = 0;
-                while (e->v2p[1][v] != c) v++;          // the first (lowest) virtual channel of the physical one
-                byvirt.push_back({v, (int)i});
-            }
-            std::sort(byvirt.begin(), byvirt.end());
-            e->dither_rank.clear(); e->dither_late.clear();
-            e->dither_channels.clear();
-            for (size_t j = 0; j < byvirt.size(); j++) {
-                const int v = byvirt[j].first;
-                // an output another engine converts keeps its rank (= where its walk through the
-                // random table starts, dither.c) but has no slot here
-                if (!e->out_active[v]) continue;
-                e->dither_channels.push_back(v);
-                e->dither_rank.push_back(byvirt[j].second);
-                // shared outputs and outputs with a sub-sample filter are requantised by the N:1
-                // pass (bfrun.c:1938-2003): their dither runs on what that pass leaves behind
-                e->dither_late.push_back(e->n_vpp[1][e->v2p[1][v]] > 1 || e->sd_slot[1][v] >= 0);
-            }
-        }
-        if (e->has_vchan) {
-            size_t n_ops_max = 0;
-            e->vline[0].assign(e->n_ch[0], DelayLine());
-            e->vline[1].assign(e->n_ch[1], DelayLine());
-            // The reference adds the sub-sample filter's integer part to the delay AND to maxdelay
-            // (bfrun.c:1152-1162, 1185-1197) -- also to maxdelay -1 ("cannot be changed"), which turns it
-            // into the limit sdf_length - 1, below the delay it allocates for: delay.c:357-374 then sizes
-            // the buffer for the limit and fills it with the delay (a heap overrun in the reference, found
-            // by tests/test_gpu_refloop.py).  Here a negative maxdelay stays negative (fixed delay), and a
-            // delay above a positive limit starts at the limit -- the clamp delay.c:358-360 means to make.
-            auto limits = [](int delay, int maxd, int extra, int *init_eff, int *max_eff) {
-                *max_eff = maxd < 0 ? maxd : maxd + extra;
-                *init_eff = delay + extra;
-                if (*max_eff > 0 && *init_eff > *max_eff) *init_eff = *max_eff;
-            };
-            for (int v : e->vin_list) {
-                const int extra = (side_uses_subdelay(e, 0) && e->sd_slot[0][v] < 0) ? e->sdf_length : 0;    // bfrun.c:1152-1162
-                int d0, m0;
-                limits(e->vdelay[0][v], e->vmaxdelay[0][v], extra, &d0, &m0);
-                int rr = e->vline[0][v].init(e->L, d0, m0, e->fmt[0][e->v2p[0][v]].bytes);
-                if (rr != BFHIP_OK) return fail(rr, "delay buffer allocation failed");
-                n_ops_max += e->vline[0][v].n_full_cap + 10;
-            }
-            for (auto &g : e->vout_groups) for (int v : g) {
-                const int extra = (side_uses_subdelay(e, 1) && e->sd_slot[1][v] < 0 && g.size() > 1) ? e->sdf_length : 0;
-                int d1, m1;
-                limits(e->vdelay[1][v], e->vmaxdelay[1][v], extra, &d1, &m1);
-                int rr = g.size() > 1 ? e->vline[1][v].init(e->L, d1, m1, e->rs)
-                                      : e->vline[1][v].init(e->L, 0, 0, e->rs);     // 1:1: dai.c delays it
-                if (rr != BFHIP_OK) return fail(rr, "delay buffer allocation failed");
-                n_ops_max += e->vline[1][v].n_full_cap + 10;
-            }
-            if (!e->vin_list.empty()) {
-                HIPCHK(dev_alloc((void **)&e->d_incopy, e->vin_list.size() * (size_t)e->L * 8));
-                HIPCHK(hipMemset(e->d_incopy, 0, e->vin_list.size() * (size_t)e->L * 8));
-            }
-            e->vjobs_slot = (n_ops_max + 8) * sizeof(ByteOp) + (e->n_ch[0] + e->n_ch[1] + 8) * 64;
-            HIPCHK(dev_alloc(&e->d_vjobs, 2 * e->vjobs_slot));
-            HIPCHK(e->st_vin.init(e->vjobs_slot));
-            HIPCHK(e->st_vout.init(e->vjobs_slot));
-            e->vline[0].resize(e->n_ch[0]); e->vline[1].resize(e->n_ch[1]);
-        }
-        // outputs K3 does not requantise itself (the dither pass or the N:1 mix does, from the time
-        // samples K3 leaves in d_timeout)
-        // ... and outputs another engine converts: nobody here writes them or their overflow state
-        if (!e->vout_groups.empty() || !e->dither_channels.empty() || e->sharded) {
-            std::vector<unsigned char> skip(e->n_ch[1], 0);
-            for (auto &g : e->vout_groups) for (int v : g) skip[v] = 1;
-            for (int c : e->dither_channels) skip[c] = 1;
-            for (int o = 0; o < e->n_ch[1]; o++) if (!e->out_active[o]) skip[o] = 1;
-            HIPCHK(dev_alloc((void **)&e->d_skip_quant, skip.size()));
-            HIPCHK(hipMemcpy(e->d_skip_quant, skip.data(), skip.size(), hipMemcpyHostToDevice));
-        }
-        if (!e->vout_groups.empty() || !e->dither_channels.empty()) {
-            HIPCHK(dev_alloc(&e->d_timeout, (size_t)e->n_ch[1] * e->L * e->rs));
-            HIPCHK(hipMemset(e->d_timeout, 0, (size_t)e->n_ch[1] * e->L * e->rs));
-        }
-    }
-    // wide interleaved sides: one uniform frame of >= 128 channels (words of 2, 4 or 8 bytes, channel p
-    // at byte p * bytes of the frame), nothing on that side that reads its samples from a private
-    // copy already (N:1 inputs, sub-sample delayed inputs); BFHIP_WIDE_IO=1 takes every eligible
-    // side, 0 none
-    for (int io = 0; io < 2; io++) {
-        const int n = e->n_phys[io];
-        bool ok = n >= 1 && !e->big;
-        for (int p = 0; p < n && ok; p++) {
-            const bfhip_format &f = e->fmt[io][p];
-            ok = (f.bytes == 2 || f.bytes == 4 || f.bytes == 8) && f.bytes == e->fmt[io][0].bytes &&
-                 f.sample_spacing == n && f.byte_offset == p * f.bytes;
-        }
-        if (io == 0) ok = ok && e->vin_list.empty() && !side_uses_subdelay(e, 0);
-        int want = 0;          // (measured on config D, 256 + 256 channels: no gain, DESIGN 6 -- kept as an option)
-        if (const char *env = getenv("BFHIP_WIDE_IO")) want = atoi(env) != 0;
-        e->wide[io] = ok && want;
-        if (e->wide[io]) {
-            const size_t bytes = (size_t)n * e->L * e->fmt[io][0].bytes;
-            HIPCHK(dev_alloc((void **)&e->d_planar[io], bytes));
-            HIPCHK(hipMemset(e->d_planar[io], 0, bytes));
-        }
-    }
-    if (e->wide[1] && e->sharded) {
-        std::vector<unsigned char> skip(e->n_phys[1], 0);
-        for (int v = 0; v < e->n_ch[1]; v++) if (!e->out_active[v]) skip[e->v2p[1][v]] = 1;
-        HIPCHK(dev_alloc((void **)&e->d_phys_skip, skip.size()));
-        HIPCHK(hipMemcpy(e->d_phys_skip, skip.data(), skip.size(), hipMemcpyHostToDevice));
-    }
-    int r = upload_formats(e);
+    int r = channels_setup(e);
     if (r != BFHIP_OK) return r;
     HIPCHK(dev_alloc((void **)&e->d_over, e->n_ch[1] * sizeof(DevOverflow)));
     HIPCHK(dev_alloc((void **)&e->d_status, sizeof(int)));
     HIPCHK(hipMemset(e->d_status, 0, sizeof(int)));
-    e->raw_bytes[0] = raw_extent(e->fmt[0], e->n_phys[0], e->L);
-    e->raw_bytes[1] = raw_extent(e->fmt[1], e->n_phys[1], e->L);
+    e->raw_bytes[0] = raw_extent(e->fmt[0], e->ch.n_phys[0], e->L);
+    e->raw_bytes[1] = raw_extent(e->fmt[1], e->ch.n_phys[1], e->L);
     build_owned_runs(e);
     HIPCHK(dev_alloc((void **)&e->d_rawin, e->raw_bytes[0] + 16));       // +16: staged in 16-byte words
     HIPCHK(dev_alloc((void **)&e->d_rawout, e->raw_bytes[1] + 16));
@@ -2336,7 +1879,7 @@ static int finalize_impl(bfhip_engine *e) {
         if ((r = zalloc(&e->d_Yold, (size_t)e->n_fadeable * L * e->csize())) != BFHIP_OK) return r;
         if ((r = zalloc(&e->d_evalprev, (size_t)e->n_sinks * L * e->rs)) != BFHIP_OK) return r;
     }
-    if ((r = dither_upload(e)) != BFHIP_OK) return r;
+    if ((r = channels_upload_dither(e)) != BFHIP_OK) return r;
     if (e->mode == BFHIP_MODE_PIPELINED || e->mode == BFHIP_MODE_PINGPONG) {
         HIPCHK(hipStreamCreateWithFlags(&e->s_in, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&e->s_out, hipStreamNonBlocking));
@@ -2368,8 +1911,7 @@ static int finalize_impl(bfhip_engine *e) {
         // (what the configuration fixes for good -- powersave, dither, wide / shared / sub-sample outputs --
         // is settled here: such an engine never runs the long transforms)
         e->lw_struct = want != 0 && e->rs == 4 && e->L == 8192 && e->wave && !e->big && e->N >= 8 && !e->pairs &&
-                       e->powersave <= 0.0 && e->dither_channels.empty() && !e->wide[1] && e->vout_groups.empty() &&
-                       !side_uses_subdelay(e, 1) && (want == 1 || vol >= 1073741824.0);
+                       e->powersave <= 0.0 && e->ch.k3_writes_raw() && (want == 1 || vol >= 1073741824.0);
         if (e->lw_struct) {
             const size_t hist_b = (size_t)e->n_ch[0] * e->R * L * sizeof(float);
             const size_t lring_b = (size_t)e->n_ch[0] * e->R * 2 * L * sizeof(c2<float>);
@@ -2404,7 +1946,7 @@ static int promote_filter(bfhip_engine *e, int fi) {
     HIPCHK(hipMemsetAsync(ring, 0, bytes, e->stream));
     const int ch = f.in_ch[0];
     const int delay = clamp_delay(e, f.delayblocks);
-    const double sc = f.in_scale[0] * e->fmt[0][e->v2p[0][ch]].scale;
+    const double sc = f.in_scale[0] * e->fmt[0][e->ch.v2p[0][ch]].scale;
     const int n_valid = (int)std::min<unsigned long long>(e->blocks_done, (unsigned long long)e->N);
     if (n_valid > 0) {
         const dim3 grid((e->L + 255) / 256, n_valid);
@@ -2527,7 +2069,7 @@ int bfhip_engine_outputs_inputs_dev(bfhip_engine *e, const void *z_dev, int firs
     if ((r = lw_drop(e)) != BFHIP_OK) return r;
     if (first < 0 || count < 0 || first + count > e->n_ch[1]) return fail(BFHIP_EINVAL, "outputs: channel range");
     if (!z_dev || !rawout_dev || !rawin_dev) return fail(BFHIP_EINVAL, "outputs_inputs: null buffer");
-    if (!e->dither_channels.empty() || e->has_vchan || count == 0 || e->big) {
+    if (!e->ch.plain() || count == 0 || e->big) {
         // the dither pass follows the inverse transforms: keep the two launches apart
         if ((r = bfhip_engine_outputs_dev(e, z_dev, first, count, rawout_dev)) != BFHIP_OK) return r;
         return bfhip_engine_inputs_dev(e, rawin_dev);
@@ -2671,7 +2213,7 @@ int bfhip_engine_block_pair_dev(bfhip_engine *e, const void *rawin0_dev, void *r
     if (r != BFHIP_OK) return r;
     if (!rawin0_dev || !rawout0_dev || !rawin1_dev || !rawout1_dev) return fail(BFHIP_EINVAL, "block_pair_dev: null buffer");
     bool plain = e->pairs && e->all_dense && !e->mac_diag && e->mac_nt && e->mac_unroll == 0 && !e->any_fading &&
-                 !e->has_vchan && !e->big && !e->rt.on && e->d_Zp[1] != nullptr && e->blocks_done >= (unsigned long long)e->N;
+                 !e->ch.has_vchan && !e->big && !e->rt.on && e->d_Zp[1] != nullptr && e->blocks_done >= (unsigned long long)e->N;
     for (auto &lj : e->level_jobs) plain = plain && !lj.n_fill && !lj.n_filt && !lj.n_fade;
     if (!plain) {
         if ((r = bfhip_engine_block_dev(e, rawin0_dev, rawout0_dev)) != BFHIP_OK) return r;
@@ -3021,7 +2563,7 @@ int bfhip_engine_reset_overflow(bfhip_engine *e) {
     std::vector<DevOverflow> v(e->n_ch[1]);
     for (int c = 0; c < e->n_ch[1]; c++) {
         memset(&v[c], 0, sizeof(DevOverflow));
-        v[c].max = overflow_max(e->fmt[1][e->v2p[1][c]]);
+        v[c].max = overflow_max(e->fmt[1][e->ch.v2p[1][c]]);
     }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     HIPCHK(hipMemcpy(e->d_over, v.data(), v.size() * sizeof(DevOverflow), hipMemcpyHostToDevice));

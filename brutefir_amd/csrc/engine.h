@@ -1,5 +1,6 @@
-// engine.h -- the engine's state, and the helpers that both host units of the engine use:
-// bfhip.hip (the C ABI of include/bfhip.h, the block schedules) and plan.hip (the plan builder).
+// engine.h -- the engine's state, and the helpers that the host units of the engine use: bfhip.hip (the
+// C ABI of include/bfhip.h, the block schedules), plan.hip (the plan builder) and channels.hip (the channel
+// stage, whose own state and interface are in channels.h).
 // Internal: nothing here is part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,7 +8,10 @@
 
 #include <array>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <set>
@@ -79,43 +83,6 @@ struct Coeff {
     bool lazy = false, watched = false;
 };
 
-// Pinned staging for the small per-block tables (N:1 channel jobs, delay-line moves, sub-sample
-// delay jobs) that go to the device with every block: K slots, one per block in flight, so the
-// upload is truly asynchronous and the host copy outlives the call that queued it.
-struct Stage {
-    static constexpr int K = 4;
-    uint8_t *base = nullptr;
-    size_t slot = 0;
-    unsigned int turn = 0;             // (unsigned: a stream of 64-frame blocks passes 2^31 in a month)
-    hipEvent_t done[K] = {nullptr, nullptr, nullptr, nullptr};
-    bool pending[K] = {false, false, false, false};
-
-    hipError_t init(size_t slot_bytes) {
-        slot = (slot_bytes + 63) & ~(size_t)63;
-        hipError_t r = pin_alloc((void **)&base, slot * K, hipHostMallocDefault);
-        for (int i = 0; i < K && r == hipSuccess; i++) r = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
-        return r;
-    }
-    void release() {
-        for (int i = 0; i < K; i++) if (done[i]) { (void)hipEventDestroy(done[i]); done[i] = nullptr; }
-        if (base) { (void)hipHostFree(base); base = nullptr; }
-    }
-    // next slot, free again once the copy queued from it K blocks ago has run
-    hipError_t take(uint8_t **p) {
-        const int i = (int)(turn++ % (unsigned int)K);
-        if (pending[i]) { const hipError_t r = hipEventSynchronize(done[i]); if (r != hipSuccess) return r; pending[i] = false; }
-        *p = base + (size_t)i * slot;
-        return hipSuccess;
-    }
-    // the copies out of the slot handed out last have been queued on st
-    hipError_t queued(hipStream_t st) {
-        const int i = (int)((turn - 1u) % (unsigned int)K);
-        const hipError_t r = hipEventRecord(done[i], st);
-        pending[i] = r == hipSuccess;
-        return r;
-    }
-};
-
 struct Filter {
     std::vector<int> in_ch, in_f, out_ch;
     std::vector<double> in_scale, in_fscale, out_scale;
@@ -137,98 +104,9 @@ constexpr int MAX_TIMED = 4096;
 enum { T_IN, T_MAC, T_OUT, T_POST, T_LEVELS, EV_PAIRS };
 constexpr int EV_PER_BLOCK = 2 * EV_PAIRS;
 
-// Host mirror of the reference's integer delay buffer (delay.c:29-45, 229-340, 346-411): same
-// state variables, same decisions; the byte moves themselves are emitted as ByteOps that a
-// device kernel executes on buffers in HBM.  Contiguous buffers only (how filter_process() uses
-// it for channels that share a physical channel, bfrun.c:1517-1521, 1948).
-struct DelayLine {
-    int F = 0, ss = 0, maxdelay = 0, curdelay = 0, cur = 0, n_full = 0, n_full_cap = 0, n_rest = 0;
-    uint8_t *arena = nullptr;
-    std::vector<uint8_t *> full;
-    uint8_t *rest = nullptr, *shrt[2] = {nullptr, nullptr}, *tmp = nullptr;
-
-    size_t frag() const { return (size_t)F * ss; }
-
-    bool host = false;                 // self test: arena in host memory, moves executed on the host
-
-    int init(int fragment, int initdelay, int maxd, int sample_size) {
-        F = fragment; ss = sample_size;
-        int delay = maxd <= 0 ? initdelay : maxd;                      // delay.c:357-360
-        if (maxd >= 0 && delay > maxd) delay = initdelay = maxd;
-        if (maxd > 0 && initdelay > maxd) initdelay = maxd;            // (the reference overruns its buffer here)
-        curdelay = initdelay; maxdelay = maxd;
-        n_full_cap = delay > F ? delay / F + 1 : 0;
-        const size_t total = (size_t)(n_full_cap + 4) * frag();
-        if (host) {
-            arena = (uint8_t *)calloc(total, 1);
-            if (!arena) return BFHIP_ENOMEM;
-        } else {
-            if (dev_alloc((void **)&arena, total) != hipSuccess) return BFHIP_ENOMEM;
-            if (hipMemset(arena, 0, total) != hipSuccess) return BFHIP_EHIP;
-        }
-        uint8_t *p = arena;
-        for (int i = 0; i < n_full_cap; i++) { full.push_back(p); p += frag(); }
-        rest = p; p += frag();
-        shrt[0] = p; p += frag();
-        shrt[1] = p; p += frag();
-        tmp = p;
-        if (delay == 0) return BFHIP_OK;
-        if (delay <= F) { n_rest = initdelay; return BFHIP_OK; }       // :365-374
-        n_rest = initdelay % F;
-        n_full = initdelay / F + 1;
-        if (n_full == 1) n_full = 0;
-        return BFHIP_OK;
-    }
-
-    static void op(std::vector<ByteOp> &ops, uint8_t *dst, const uint8_t *src, size_t n) {
-        if (n == 0) return;
-        ByteOp o; o.dst = dst; o.src = src; o.n = (unsigned int)n; o.pad = 0;
-        ops.push_back(o);
-    }
-
-    void retarget(int newdelay, std::vector<ByteOp> &ops) {           // change_delay, :283-318
-        if (newdelay == curdelay || newdelay > maxdelay) return;
-        if (newdelay <= F) {
-            n_rest = newdelay;
-            if (curdelay > F || curdelay < newdelay) {
-                op(ops, shrt[0], nullptr, (size_t)newdelay * ss);
-                op(ops, shrt[1], nullptr, (size_t)newdelay * ss);
-            }
-            n_full = 0; cur = 0; curdelay = newdelay;
-            return;
-        }
-        n_rest = newdelay % F;
-        n_full = newdelay / F + 1;
-        if (curdelay < newdelay) {
-            for (int i = 0; i < n_full; i++) op(ops, full[i], nullptr, frag());
-            if (n_rest != 0) op(ops, rest, nullptr, (size_t)n_rest * ss);
-        }
-        cur = 0; curdelay = newdelay;
-    }
-
-    void update(uint8_t *buf, int delay, std::vector<ByteOp> &ops) {  // delay_update, :320-340
-        retarget(delay, ops);
-        const size_t rr = (size_t)n_rest * ss;
-        if (n_full > 0) {                                              // update_delay_buffer
-            uint8_t *last = cur == n_full - 1 ? full[0] : full[cur + 1];
-            op(ops, full[cur], buf, frag());
-            if (rr != 0) {
-                op(ops, buf, rest, rr);
-                op(ops, rest, last + (frag() - rr), rr);
-            }
-            op(ops, buf + rr, last, frag() - rr);
-            if (++cur == n_full) cur = 0;
-        } else if (n_rest > 0) {                                       // update_delay_short_buffer
-            op(ops, shrt[cur], buf + (frag() - rr), rr);
-            op(ops, tmp, buf, frag() - rr);                            // shift_samples via a
-            op(ops, buf + rr, tmp, frag() - rr);                       // scratch copy
-            cur = !cur;
-            op(ops, buf, shrt[cur], rr);
-        }
-    }
-};
-
 }  // namespace bfhip_host
+
+#include "channels.h"
 
 using namespace bfhip_host;
 
@@ -358,50 +236,13 @@ struct bfhip_engine {
     size_t src_off = 0;
     bool any_fading = false;
 
-    // N:1 virtual -> physical channels (bfconf->virt2phys): fmt[] is indexed by PHYSICAL channel
-    int n_phys[2] = {0, 0};
-    std::vector<int> v2p[2], n_vpp[2], vdelay[2], vmaxdelay[2], vmuted[2];
-    std::vector<DelayLine> vline[2];
-    std::vector<int> vin_list;             // virtual inputs that share a physical one
-    std::vector<std::vector<int>> vout_groups;   // members of every shared physical output
-    uint8_t *d_incopy = nullptr;           // [vin_list.size()][L * 8]
-    void *d_vjobs = nullptr;               // per-block job/op tables (device): input half | output half
-    size_t vjobs_slot = 0;
-    Stage st_vin, st_vout, st_sd[2];       // their pinned staging, one slot per block in flight
-    bool has_vchan = false;
-
-    // sub-sample delay (sdf_length / sdf_beta / per-channel subdelay; delay.c:416-505)
-    int sdf_length = 0, sd_flen = 0, sd_bs = 0;
-    std::vector<int> subdelay[2];          // current value per virtual channel (-100 = undefined)
-    std::vector<int> sd_slot[2];           // filter slot of a channel, -1 = none (fixed at finalize)
-    void *d_sd_bank = nullptr;             // [199][flen] taps, index 99 + subdelay
-    void *d_sd_rest[2] = {nullptr, nullptr};
-    void *d_sdin = nullptr;                // [n filtered inputs][L] reals, what K1 reads
-    void *d_sdjobs[2] = {nullptr, nullptr};
-
-    // HP-TPDF dither (dither.c, dither.h)
-    std::vector<int> dither_channels;      // output channel of each dither slot (virtual, ascending, after finalize)
-    std::vector<int> dither_rank;          // its rank among the dithered PHYSICAL outputs: where its table walk starts
-    std::vector<char> dither_late;         // slot is the head of a shared / sub-sample-filtered output: dithered after the mix
-    std::vector<int8_t> dither_table;
-    int dither_spacing = 0;
-    int *d_dither_ch = nullptr;
-    void *d_dither_state = nullptr;
-    int8_t *d_dither_table = nullptr;
-    void *d_randmap = nullptr;             // 512 entries; centre at +256
-    unsigned char *d_skip_quant = nullptr; // [n_out] 1 = the dither pass writes this channel
-    void *d_timeout = nullptr;             // [n_out][L] time samples for the dither pass
+    Channels ch;                   // the channel stage (channels.h)
 
     // plan geometry
     int n_groups = 0, n_out_padded = 0, n_chunks = 1, n_tiles = 1, mac_threads = 256;
     int n_entries = 0;
     bool mac_nt = true;            // non-temporal coefficient loads (BFHIP_MAC_NT=0 turns them off)
     int mac_unroll = 0;            // 0: rotating three-stage pipeline; 1..4: plain unroll (BFHIP_MAC_UNROLL, tools/tune_mac.py)
-    // wide interleaved sides (>= 128 channels in one uniform frame; BFHIP_WIDE_IO=0/1): the raw frames are
-    // transposed to / from a planar copy by a coalesced pass of their own (transpose_words_kernel)
-    bool wide[2] = {false, false};
-    uint8_t *d_planar[2] = {nullptr, nullptr};     // [n_phys][L] words of the side's sample size
-    unsigned char *d_phys_skip = nullptr;          // [n_phys out] 1 = another engine's channel (shards)
     // two blocks per pass over the coefficients (bfhip_engine_enable_pairs / bfhip_engine_block_pair_dev)
     bool pairs = false;
     unsigned long long n_pair_launches = 0;

@@ -2380,7 +2380,7 @@ coeff_long_kernel(const MacEntry<T> *__restrict__ entries, const StreamWhere *__
 
 // The reference's integer delay (delay.c:78-340) is a little machine of memcpy/memset between a
 // ring of whole-fragment buffers, a rest buffer and two short buffers; which copies happen
-// depends on the delay history.  The host mirrors that machine (DelayLine in bfhip.hip) and
+// depends on the delay history.  The host mirrors that machine (DelayLine in channels.h) and
 // emits, per update, the list of byte moves; the device only executes them, in order.
 struct ByteOp {
     uint8_t *dst;

@@ -351,7 +351,7 @@ void collect_fill_job(const bfhip_engine *e, Plan<T> &pl, int fi, const FilterVi
     for (size_t i = 0; i < f.in_ch.size(); i++) {
         MixSrc<T> m;
         m.spec = (const c2<T> *)e->d_ring + (size_t)f.in_ch[i] * e->R * L;
-        m.scale = (T)(f.in_scale[i] * e->fmt[0][e->v2p[0][f.in_ch[i]]].scale);      // bfrun.c:1641 (virtscales)
+        m.scale = (T)(f.in_scale[i] * e->fmt[0][e->ch.v2p[0][f.in_ch[i]]].scale);      // bfrun.c:1641 (virtscales)
         m.R = e->R;
         pl.srcs.push_back(m);
     }
@@ -403,7 +403,7 @@ void collect_outputs(const bfhip_engine *e, Plan<T> &pl, int fi, const FilterVie
     for (size_t oi = 0; oi < f.out_ch.size(); oi++) {
         const int o = f.out_ch[oi];
         const int g = o / OG, j = o % OG;
-        const double s_out = f.out_scale[oi] / e->fmt[1][e->v2p[1][o]].scale;            // bfrun.c:1850
+        const double s_out = f.out_scale[oi] / e->fmt[1][e->ch.v2p[1][o]].scale;            // bfrun.c:1850
         const std::pair<long, int> key = v.needY ? std::make_pair((long)(I + pl.n_names + filter_name(e, fi)), 0)
                                                  : std::make_pair(v.ring_id, v.rdelay);
         auto &slots = pl.index[g][key];
@@ -485,7 +485,7 @@ int plan_collect(const bfhip_engine *e, Plan<T> &pl) {
             const int ch = f.in_ch[0];
             v.ring = (const c2<T> *)e->d_ring + (size_t)ch * e->R * L;
             v.ring_id = ch; v.rdelay = v.delay;
-            v.rscale = f.in_scale[0] * e->fmt[0][e->v2p[0][ch]].scale;                         // bfrun.c:1664
+            v.rscale = f.in_scale[0] * e->fmt[0][e->ch.v2p[0][ch]].scale;                         // bfrun.c:1664
         }
         if (f.active) {
             auto &u = pl.ring_used[v.ring_id];
@@ -823,7 +823,7 @@ void plan_commit(bfhip_engine *e, const Plan<T> &pl) {
     double bytes_ring = 0, raw = 0;
     for (auto &kv : pl.ring_used) for (char u : kv.second) bytes_ring += u ? C : 0;
     for (int io = 0; io < 2; io++)
-        for (int c = 0; c < e->n_phys[io]; c++) raw += (double)e->L * e->fmt[io][c].bytes;
+        for (int c = 0; c < e->ch.n_phys[io]; c++) raw += (double)e->L * e->fmt[io][c].bytes;
     int O_here = 0;
     for (int o = 0; o < e->n_ch[1]; o++) O_here += e->out_active.empty() || e->out_active[o] ? 1 : 0;
     e->alg_bytes_mac = pl.bytes_H + bytes_ring + C * O_here;
