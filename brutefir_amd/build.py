@@ -22,7 +22,8 @@ PUBLIC = [os.path.join("..", "..", "include", h) for h in ("bfhip.h", "bfhip_con
 DEVICE = ["kernels.h", "fft_lds.h", "fft_wave.h", "bigfft.h"] + PUBLIC
 # translation unit -> what it includes
 UNITS = {
-    "bfhip.hip": DEVICE + ["engine.h", "channels.h", "conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],
+    "bfhip.hip": DEVICE + ["engine.h", "channels.h", "passes.h", "conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],
+    "passes.hip": DEVICE + ["engine.h", "channels.h", "passes.h", "alloc.h"],
     "plan.hip": DEVICE + ["engine.h", "channels.h", "alloc.h"],
     "channels.hip": DEVICE + ["engine.h", "channels.h", "alloc.h", "dither_init.h", "subdelay_filter.h"],
     "convolver_abi.hip": DEVICE + ["conv_shared.h"],

@@ -1,5 +1,6 @@
 // bfhip.hip -- host side of the engine + the C ABI of include/bfhip.h (the plan builder: plan.hip; the
-// channel stage around the transforms: channels.hip).
+// channel stage around the transforms: channels.hip; every kernel launch: passes.hip -- this unit names no
+// kernel and holds no device code).
 //
 // What the reference's filter_process() does with host buffers and a chain of convolver_*
 // calls per filter (bfrun.c:1493-2008) is turned into a static device plan here:
@@ -31,6 +32,7 @@
 #include <type_traits>
 
 #include "engine.h"
+#include "passes.h"
 #include "coeff_async.h"
 #include "conv_shared.h"
 #include "dither_init.h"
@@ -154,401 +156,6 @@ void coeff_release(bfhip_engine *e, void *p, size_t bytes) {
     if (sl.used >= need && (unsigned char *)sl.base + sl.used - need == (unsigned char *)p) sl.used -= need;
 }
 
-// ---------------------------------------------------------------- template dispatch
-
-#define DISPATCH_LOG2L(T, FN, ...)                        \
-    switch (e->log2L) {                                   \
-    case 2: FN<T, 2>(__VA_ARGS__); break;                 \
-    case 3: FN<T, 3>(__VA_ARGS__); break;                 \
-    case 4: FN<T, 4>(__VA_ARGS__); break;                 \
-    case 5: FN<T, 5>(__VA_ARGS__); break;                 \
-    case 6: FN<T, 6>(__VA_ARGS__); break;                 \
-    case 7: FN<T, 7>(__VA_ARGS__); break;                 \
-    case 8: FN<T, 8>(__VA_ARGS__); break;                 \
-    case 9: FN<T, 9>(__VA_ARGS__); break;                 \
-    case 10: FN<T, 10>(__VA_ARGS__); break;               \
-    case 11: FN<T, 11>(__VA_ARGS__); break;               \
-    case 12: FN<T, 12>(__VA_ARGS__); break;               \
-    case 13: FN<T, 13>(__VA_ARGS__); break;               \
-    default: break;                                       \
-    }
-
-#define DISPATCH(FN, ...)                                                   \
-    do {                                                                    \
-        if (e->rs == 4) { DISPATCH_LOG2L(float, FN, __VA_ARGS__) }          \
-        else { DISPATCH_LOG2L(double, FN, __VA_ARGS__) }                    \
-    } while (0)
-
-inline PowerSave ps_arg(const bfhip_engine *e) {
-    PowerSave ps;
-    ps.thr = e->d_ps_flags ? e->powersave : 0.0;
-    ps.scale = e->d_ps_scale; ps.flags = e->d_ps_flags; ps.live = e->d_ps_live;
-    return ps;
-}
-
-
-template <typename T, int LOG2L>
-void launch_fft_in(bfhip_engine *e, const uint8_t *raw, int slot, hipError_t *err) {
-    constexpr int NT = fft_threads<T>(LOG2L);
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = fft_in_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(e->n_ch[0]), dim3(NT), lds, e->ls, raw, e->d_fmt[0],
-                       (T *)e->d_prev, (c2<T> *)e->d_ring, (const c2<T> *)e->d_tw, e->R, slot,
-                       (const BlockState *)e->bs_arg, ps_arg(e));
-    *err = hipGetLastError();
-}
-
-#define DISPATCH_WAVE_T(T, FN, ...)                        \
-    switch (e->log2L) {                                    \
-    case 10: FN<T, 10>(__VA_ARGS__); break;                \
-    case 11: FN<T, 11>(__VA_ARGS__); break;                \
-    case 12: FN<T, 12>(__VA_ARGS__); break;                \
-    case 13: FN<T, 13>(__VA_ARGS__); break;                \
-    default: break;                                        \
-    }
-#define DISPATCH_WAVE(FN, ...)                                              \
-    do {                                                                    \
-        if (e->rs == 4) { DISPATCH_WAVE_T(float, FN, __VA_ARGS__) }         \
-        else { DISPATCH_WAVE_T(double, FN, __VA_ARGS__) }                   \
-    } while (0);
-
-template <typename T, int LOG2L>
-void launch_fft_in_wave(bfhip_engine *e, const uint8_t *raw, int slot, hipError_t *err) {
-    constexpr int NT = WaveGeo<LOG2L>::NT;
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = fft_in_wave_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(e->n_ch[0]), dim3(NT), lds, e->ls, raw, e->d_fmt[0],
-                       (T *)e->d_prev, (c2<T> *)e->d_ring, (const c2<T> *)e->d_tww, e->R, slot,
-                       (const BlockState *)e->bs_arg, ps_arg(e));
-    *err = hipGetLastError();
-}
-
-template <typename T, int LOG2L>
-void launch_ifft_out_wave(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks,
-                          int first, int count, uint8_t *raw, hipError_t *err) {
-    constexpr int NT = WaveGeo<LOG2L>::NT;
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = ifft_out_wave_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(count), dim3(NT), lds, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
-                       raw, e->ch.timeout<T>(first, e->L),
-                       (const c2<T> *)e->d_tww, e->safety_limit, e->d_status);
-    *err = hipGetLastError();
-}
-
-// K3 of an earlier block (count channels from Zp) + K1 of the current block in one launch
-template <typename T, int LOG2L>
-void launch_io_wave(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first, int count,
-                    uint8_t *rawout, const uint8_t *rawin, int slot, hipError_t *err) {
-    constexpr int NT = WaveGeo<LOG2L>::NT;
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = io_wave_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(count + e->n_ch[0]), dim3(NT), lds, e->ls, count,
-                       (const c2<T> *)Zp, chunk_stride, n_chunks, first, e->d_fmt[1], e->d_over,
-                       e->ch.skip_quant(), rawout,
-                       e->ch.timeout<T>(first, e->L),
-                       e->safety_limit, e->d_status,
-                       rawin, e->d_fmt[0], (T *)e->d_prev, (c2<T> *)e->d_ring, e->R, slot,
-                       (const c2<T> *)e->d_tww, ps_arg(e), (const BlockState *)e->bs_arg);
-    *err = hipGetLastError();
-}
-
-template <typename T, int LOG2L>
-void launch_coeff_prep(bfhip_engine *e, const void *taps, int n_taps, double scale, void *H,
-                       int n_blocks, hipError_t *err) {
-    constexpr int NT = fft_threads<T>(LOG2L);
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = coeff_prep_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(n_blocks), dim3(NT), lds, e->stream, (const T *)taps, n_taps,
-                       (T)scale, (c2<T> *)H, (const c2<T> *)e->d_tw, e->d_bad);
-    *err = hipGetLastError();
-}
-
-template <typename T, int LOG2L>
-void launch_ifft_out(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks,
-                     int first, int count, uint8_t *raw, hipError_t *err) {
-    constexpr int NT = fft_threads<T>(LOG2L);
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = ifft_out_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(count), dim3(NT), lds, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
-                       raw, e->ch.timeout<T>(first, e->L),
-                       (const c2<T> *)e->d_tw, e->safety_limit, e->d_status);
-    *err = hipGetLastError();          // (the dither pass behind it: do_outputs)
-}
-
-template <typename T, int LOG2L>
-void launch_io(bfhip_engine *e, const void *z, int first, int count, uint8_t *rawout,
-               const uint8_t *rawin, int slot, hipError_t *err) {
-    constexpr int NT = fft_threads<T>(LOG2L);
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto k = io_kernel<T, LOG2L>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(count + e->n_ch[0]), dim3(NT), lds, e->ls, count,
-                       (const c2<T> *)z, first, e->d_fmt[1], e->d_over, e->ch.skip_quant(),
-                       rawout, e->ch.timeout<T>(first, e->L),
-                       e->safety_limit, e->d_status,
-                       rawin, e->d_fmt[0], (T *)e->d_prev, (c2<T> *)e->d_ring, e->R, slot, (const c2<T> *)e->d_tw, ps_arg(e));
-    *err = hipGetLastError();
-}
-
-// the grid mac_decode (kernels.h) takes apart: n_tc (tile, chunk) pairs rounded up to the 8 XCDs, times the groups
-int mac_grid(int n_tc, int n_groups) { return ((n_tc + 7) / 8) * n_groups * 8; }
-// blocks the rings will hold of the block `ahead` after this one, itself included (procblocks, bfrun.c:1745)
-int block_age(const bfhip_engine *e, int ahead = 0) {
-    return (int)std::min<unsigned long long>(e->blocks_done + 1 + (unsigned long long)ahead, (unsigned long long)e->N);
-}
-
-template <typename T>
-void launch_mac(bfhip_engine *e, void *Zp, hipError_t *err) {
-    const int n_tc = e->n_tiles * e->n_chunks;
-    const int grid = mac_grid(n_tc, e->n_groups);
-    const int age = block_age(e);
-#define BFHIP_LAUNCH_MAC(NTFLAG, U)                                                                   \
-    hipLaunchKernelGGL((mac_xbar_kernel<T, NTFLAG, U>), dim3(grid), dim3(e->mac_threads), 0, e->ls,      \
-                       (const MacEntry<T> *)e->b_entries.p, (const ChunkRange *)e->b_chunks.p,               \
-                       (c2<T> *)Zp, e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc,               \
-                       e->blockcounter, age, (const BlockState *)e->bs_arg,                              \
-                       (NTFLAG && U == 0) ? e->hstream : StreamLayout{nullptr, 0, 0, 0})
-    if (e->mac_diag) {
-        const int n_jobs = e->n_chunks * e->n_out_padded;
-        // the spectrum of a job goes to `tsplit` workgroups (consecutive runs of tiles): ~512 workgroups
-        // in all, no partial sums -- runs of 16 - 64 KiB either way (BFHIP_DIAG_TSPLIT: 1, 2, 4 ...)
-        const int all_tiles = std::max(1, e->L / (256 * (int)(16 / sizeof(c2<T>))));
-        int tsplit = 1;
-        while (tsplit < all_tiles && tsplit < 8 && n_jobs * tsplit < 512) tsplit *= 2;
-        if (const char *env = getenv("BFHIP_DIAG_TSPLIT")) {
-            tsplit = 1;
-            while (tsplit * 2 <= std::min(all_tiles, atoi(env))) tsplit *= 2;
-        }
-        while (all_tiles / tsplit > 16) tsplit *= 2;            // float64 at L = 8192: 32 tiles, 16 per workgroup
-        const int tiles = all_tiles / tsplit;
-#define BFHIP_LAUNCH_DIAG(NTFLAG, TL)                                                                                  \
-        hipLaunchKernelGGL((mac_diag_kernel<T, NTFLAG, TL>), dim3(n_jobs * tsplit), dim3(256), 0, e->ls,               \
-                           (const MacEntry<T> *)e->b_entries.p, e->d_diag_jobs, (c2<T> *)Zp, e->L, e->n_out_padded,      \
-                           e->blockcounter, age, (const BlockState *)e->bs_arg, tsplit)
-#define BFHIP_DIAG_TILES(NTFLAG)                                              \
-        switch (tiles) {                                                      \
-        case 1: BFHIP_LAUNCH_DIAG(NTFLAG, 1); break;                          \
-        case 2: BFHIP_LAUNCH_DIAG(NTFLAG, 2); break;                          \
-        case 4: BFHIP_LAUNCH_DIAG(NTFLAG, 4); break;                          \
-        case 8: BFHIP_LAUNCH_DIAG(NTFLAG, 8); break;                          \
-        default: BFHIP_LAUNCH_DIAG(NTFLAG, 16); break;                        \
-        }
-        if (e->mac_nt) { BFHIP_DIAG_TILES(true) } else { BFHIP_DIAG_TILES(false) }
-#undef BFHIP_DIAG_TILES
-#undef BFHIP_LAUNCH_DIAG
-    }
-    else if (!e->mac_nt) BFHIP_LAUNCH_MAC(false, 2);
-    // the pipelined variant needs ~290 VGPRs: worth it for the pure crossbar, a loss of occupancy
-    // for plans that (also) run the latency-bound per-term paths
-    else if (e->mac_unroll == 0 && e->all_dense) BFHIP_LAUNCH_MAC(true, 0);
-    else if (e->mac_unroll == 0) BFHIP_LAUNCH_MAC(true, 2);
-    else if (e->mac_unroll == 4) BFHIP_LAUNCH_MAC(true, 4);
-    else if (e->mac_unroll == 3) BFHIP_LAUNCH_MAC(true, 3);
-    else if (e->mac_unroll == 1) BFHIP_LAUNCH_MAC(true, 1);
-    else BFHIP_LAUNCH_MAC(true, 2);
-#undef BFHIP_LAUNCH_MAC
-    *err = hipGetLastError();
-}
-
-template <typename T>
-void launch_mac2(bfhip_engine *e, void *Zp0, void *Zp1, hipError_t *err) {
-    const int n_tc = e->n_tiles * e->n_chunks;
-    e->zp_is_sum = false;
-    hipLaunchKernelGGL((mac_xbar2_kernel<T, true>), dim3(mac_grid(n_tc, e->n_groups)), dim3(e->mac_threads), 0, e->ls,
-                       (const MacEntry<T> *)e->b_entries.p, (const ChunkRange *)e->b_chunks.p, (c2<T> *)Zp0, (c2<T> *)Zp1,
-                       e->L, e->n_out_padded, e->n_groups, e->n_chunks, n_tc, e->blockcounter, e->hstream);
-    *err = hipGetLastError();
-}
-
-// the long-window MAC (kernels.h): the crossbar kernel over the long entries, ring step 3
-void launch_mac_long(bfhip_engine *e, void *Zp, hipError_t *err) {
-    const int n_tc = e->lw_tiles * e->lw_chunks;
-    hipLaunchKernelGGL((mac_xbar_kernel<float, true, 0, 3>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,
-                       (const MacEntry<float> *)e->b_lentries.p, (const ChunkRange *)e->b_lchunks.p, (c2<float> *)Zp,
-                       2 * e->L, e->n_out_padded, e->n_groups, e->lw_chunks, n_tc, e->blockcounter, block_age(e),
-                       (const BlockState *)e->bs_arg, e->lstream);
-    *err = hipGetLastError();
-}
-
-// the look-ahead passes (kernels.h): ahead buffer of (block mod 4, slice)
-c2<float> *la_buffer(bfhip_engine *e, unsigned long long block, int slice) {
-    const size_t one = (size_t)e->n_out_padded * 2 * e->L;
-    return (c2<float> *)e->b_ahead.p + ((size_t)(block & 3ull) * 3 + (size_t)slice) * one;
-}
-// head: the head pass of this block (its three ahead buffers are current) and the tail pass of this call's slice
-// in one launch; else the tail pass alone, behind a full long MAC
-c2<float> *far_buffer(bfhip_engine *e, unsigned long long block, int slice) {
-    const size_t one = (size_t)e->n_out_padded * 2 * e->L;
-    return (c2<float> *)e->b_far.p + ((size_t)(block % 7ull) * LA_FAR + (size_t)slice) * one;
-}
-void launch_mac_la(bfhip_engine *e, void *Zp, bool head, hipError_t *err) {
-    const int n_tc = e->lw_tiles;
-    const unsigned long long T = e->blocks_done;
-    const int slice = (int)(T % 3ull);
-    const bool two = e->far_active && e->b_far.p != nullptr;
-    LaFar<float> far = {};
-    if (two) {
-        far.slice = (int)(T % (unsigned long long)LA_FAR);
-        for (int k = 0; k < LA_FAR; k++) {
-            far.A[k] = far_buffer(e, T, k);
-            far.Z[k] = far_buffer(e, T + 1 + k, far.slice);
-            far.age[k] = block_age(e, k + 1);
-        }
-    }
-#define BFHIP_LAUNCH_LA(PHASES)                                                                                        \
-    hipLaunchKernelGGL((mac_la_kernel<float, PHASES>), dim3(mac_grid(n_tc, e->n_groups)), dim3(256), 0, e->ls,         \
-                       (const MacEntry<float> *)e->b_lentries.p, (const ChunkRange *)e->b_lchunks.p, (c2<float> *)Zp,      \
-                       (const c2<float> *)la_buffer(e, T, 0), (const c2<float> *)la_buffer(e, T, 1),                   \
-                       (const c2<float> *)la_buffer(e, T, 2),                                                          \
-                       la_buffer(e, T + 1, slice), la_buffer(e, T + 2, slice), la_buffer(e, T + 3, slice),             \
-                       2 * e->L, e->n_groups, n_tc, e->blockcounter, block_age(e), block_age(e, 1), block_age(e, 2),   \
-                       block_age(e, 3), slice, e->lstream, far)
-    if (two) { if (head) BFHIP_LAUNCH_LA(7); else BFHIP_LAUNCH_LA(6); }
-    else if (head) BFHIP_LAUNCH_LA(3); else BFHIP_LAUNCH_LA(2);
-#undef BFHIP_LAUNCH_LA
-    *err = hipGetLastError();
-    if (*err != hipSuccess) return;
-    e->n_mac_launches++;
-    for (int k = 1; k <= 3; k++) {
-        e->la_for[(T + k) & 3ull][slice] = T + k;
-        e->la_at[(T + k) & 3ull][slice] = e->la_epoch;
-    }
-    if (two)
-        for (int k = 1; k <= LA_FAR; k++) {
-            e->far_for[(T + k) % 7ull][far.slice] = T + k;
-            e->far_at[(T + k) % 7ull][far.slice] = e->la_epoch;
-        }
-}
-}  // namespace
-
-BFHIP_HOST_NS {
-// No block has been processed (or prewarm has just declared the zero-initialised rings N blocks of
-// silence): every window the tails of the next three blocks read is silence, so their ahead buffers
-// are zeros.  Store that instead of running three full MACs first.
-int la_prime(bfhip_engine *e) {
-    if (!e->la_active || e->b_ahead.p == nullptr) return BFHIP_OK;
-    HIPCHK(hipMemsetAsync(e->b_ahead.p, 0, e->b_ahead.cap, e->stream));
-    for (unsigned long long T = e->blocks_done; T < e->blocks_done + 3; T++)
-        for (int j = 0; j < 3; j++) { e->la_for[T & 3ull][j] = T; e->la_at[T & 3ull][j] = e->la_epoch; }
-    if (!e->far_active || e->b_far.p == nullptr) return BFHIP_OK;
-    // the far tails of the next six blocks read silence alone as well
-    HIPCHK(hipMemsetAsync(e->b_far.p, 0, e->b_far.cap, e->stream));
-    for (unsigned long long T = e->blocks_done; T < e->blocks_done + LA_FAR; T++)
-        for (int j = 0; j < LA_FAR; j++) { e->far_for[T % 7ull][j] = T; e->far_at[T % 7ull][j] = e->la_epoch; }
-    return BFHIP_OK;
-}
-}  // namespace bfhip_host
-
-namespace {
-// are the three ahead buffers of the block about to run current?
-bool la_block_valid(const bfhip_engine *e) {
-    const unsigned long long T = e->blocks_done;
-    for (int j = 0; j < 3; j++)
-        if (e->la_for[T & 3ull][j] != T || e->la_at[T & 3ull][j] != e->la_epoch) return false;
-    if (e->far_active && e->b_far.p != nullptr)
-        for (int j = 0; j < LA_FAR; j++)
-            if (e->far_for[T % 7ull][j] != T || e->far_at[T % 7ull][j] != e->la_epoch) return false;
-    return true;
-}
-
-// [long K3 of `count` outputs from the long partial sums Zp | long K1 of this block's inputs (inputs)]
-void launch_io_long(bfhip_engine *e, const void *Zp, int count, uint8_t *rawout, bool inputs, hipError_t *err) {
-    constexpr int NT = fft_threads<float>(LW_LOG2);
-    const int n_in = inputs ? e->n_ch[0] : 0;
-    if (count + n_in == 0) return;
-    const size_t lds = lds_fft_bytes(LW_LOG2, sizeof(c2<float>));
-    auto k = io_long_kernel<float, LW_LOG2>;
-    *err = allow_lds(k, lds);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(k, dim3(count + n_in), dim3(NT), lds, e->ls, count, (const c2<float> *)Zp,
-                       (size_t)e->n_out_padded * 2 * e->L, e->lw_chunks, 0, e->d_fmt[1], e->d_over,
-                       e->ch.skip_quant(), rawout, e->safety_limit, e->d_status,
-                       (const float *)e->d_prev, (float *)e->d_hist, (c2<float> *)e->d_lring, e->R, e->blockcounter,
-                       (const c2<float> *)e->d_tw14, (const BlockState *)e->bs_arg);
-    *err = hipGetLastError();
-}
-
-// which of the engine's partial-sum buffers Zp is (-1: a caller's buffer) and whether it holds long spectra
-int zp_index(const bfhip_engine *e, const void *Zp) {
-    for (int i = 0; i < 3; i++) if (Zp != nullptr && Zp == e->d_Zp[i]) return i;
-    return -1;
-}
-bool zp_is_long(const bfhip_engine *e, const void *Zp) {
-    const int i = zp_index(e, Zp);
-    return i >= 0 && e->zp_long[i];
-}
-
-template <typename T>
-void launch_sum(bfhip_engine *e, const void *Zp, void *Z, hipError_t *err) {
-    const size_t n_per_chunk = (size_t)e->n_out_padded * e->L;
-    const size_t n_valid = (size_t)e->n_ch[1] * e->L;
-    const int grid = (int)((n_valid + 255) / 256);
-    hipLaunchKernelGGL(sum_partials_kernel<T>, dim3(grid), dim3(256), 0, e->ls,
-                       (const c2<T> *)Zp, (c2<T> *)Z, n_per_chunk, n_valid, e->n_chunks);
-    if (Z == Zp) e->zp_is_sum = true;
-    *err = hipGetLastError();
-}
-
-template <typename T, int LOG2L>
-void launch_levels(bfhip_engine *e, hipError_t *err) {
-    constexpr int NT = fft_threads<T>(LOG2L);
-    const size_t lds = lds_fft_bytes(LOG2L, sizeof(c2<T>));
-    auto kf = ring_fill_kernel<T, LOG2L>;
-    auto kx = crossfade_kernel<T, LOG2L>;
-    const int age = block_age(e);
-    const unsigned char *base = (const unsigned char *)e->b_jobs.p;
-    const int V = 16 / (int)sizeof(c2<T>);
-    const int threads = e->mac_threads;
-    const int tiles = (e->L + threads * V - 1) / (threads * V);
-    for (auto &lj : e->level_jobs) {
-        if (lj.n_fill > 0) {
-            if ((*err = allow_lds(kf, lds)) != hipSuccess) return;
-            hipLaunchKernelGGL(kf, dim3(lj.n_fill), dim3(NT), lds, e->ls,
-                               (const FillJob<T> *)(base + lj.fill_off),
-                               (const MixSrc<T> *)(base + e->src_off), (const c2<T> *)e->d_tw,
-                               e->N, e->blockcounter, (const BlockState *)e->bs_arg);
-        }
-        if (lj.n_filt > 0) {
-            hipLaunchKernelGGL(mac_filter_kernel<T>, dim3(tiles, lj.n_filt), dim3(threads), 0, e->ls,
-                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, age,
-                               (const BlockState *)e->bs_arg);
-        }
-        if (lj.n_fade > 0) {
-            if ((*err = allow_lds(kx, lds)) != hipSuccess) return;
-            hipLaunchKernelGGL(kx, dim3(lj.n_fade), dim3(NT), lds, e->ls,
-                               (const FadeJob<T> *)(base + lj.fade_off), (const c2<T> *)e->d_tw);
-        }
-        if ((*err = hipGetLastError()) != hipSuccess) return;
-    }
-}
-
-
-// ---------------------------------------------------------------- block lengths above 8192 (bigfft.h)
-
-// scratch for n_tr transforms of L complex points each (zin, zmid, zout)
-int big_reserve(bfhip_engine *e, size_t n_tr) {
-    if (n_tr <= e->big_cap) return BFHIP_OK;
-    { int r = sync_all(e); if (r != BFHIP_OK) return r; }
-    for (DevBuf &b : e->b_big) HIPCHK(b.grow(n_tr * (size_t)e->L * e->csize()));
-    e->big_cap = n_tr;
-    return BFHIP_OK;
-}
-
 // the staging buffer for taps and processed blocks on their way to or from a set: `bytes` of it, and
 // nothing on the device still reading the one it replaces
 int taps_reserve(bfhip_engine *e, size_t bytes) {
@@ -557,116 +164,6 @@ int taps_reserve(bfhip_engine *e, size_t bytes) {
     HIPCHK(e->b_taps.grow(bytes));
     return BFHIP_OK;
 }
-
-// zin -> zout: complex FFT of L points for n_tr transforms on `st`
-template <typename T>
-void big_fft(bfhip_engine *e, int n_tr, bool inv, hipStream_t st, hipError_t *err) {
-    const c2<T> *zin = (const c2<T> *)e->b_big[0].p;
-    c2<T> *zmid = (c2<T> *)e->b_big[1].p, *zout = (c2<T> *)e->b_big[2].p;
-    const c2<T> *tw13 = (const c2<T> *)e->d_tw13, *twL = (const c2<T> *)e->d_tw;
-    *err = inv ? big_fft_run<T, true>(zin, zmid, zout, e->log2L, n_tr, tw13, twL, st)
-               : big_fft_run<T, false>(zin, zmid, zout, e->log2L, n_tr, tw13, twL, st);
-}
-
-inline dim3 big_grid_half(const bfhip_engine *e, int n_tr) { return dim3((unsigned)(e->L / 2 / 256 + 1), (unsigned)n_tr); }
-
-template <typename T>
-void launch_fft_in_big(bfhip_engine *e, const uint8_t *raw, int slot, hipError_t *err) {
-    const int n = e->n_ch[0];
-    const int parity = (int)(e->blocks_done & 1);
-    const bool ps_on = e->d_ps_flags != nullptr;
-    hipLaunchKernelGGL(big_in_pre<T>, big_grid_half(e, n), dim3(256), 0, e->ls, raw, e->d_fmt[0], (T *)e->d_prev,
-                       (c2<T> *)e->b_big[0].p, e->L, ps_on ? e->d_ps_acc : (unsigned long long *)nullptr, n, parity,
-                       e->powersave >= 1.0 ? 1 : 0);
-    big_fft<T>(e, n, false, e->ls, err);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n), dim3(256), 0, e->ls, (const c2<T> *)e->b_big[2].p,
-                       (c2<T> *)e->d_ring + (size_t)slot * e->L, (size_t)e->R * e->L, (const c2<T> *)e->d_tw, e->L, (T)1);
-    if (ps_on)
-        hipLaunchKernelGGL(big_ps_finish<T>, dim3((unsigned)(e->L / 256), (unsigned)n), dim3(256), 0, e->ls,
-                           (const unsigned long long *)e->d_ps_acc, n, parity, ps_arg(e), (c2<T> *)e->d_ring, e->R, slot, e->L);
-    *err = hipGetLastError();
-}
-
-template <typename T>
-void launch_coeff_prep_big(bfhip_engine *e, const void *taps, int n_taps, double scale, void *H,
-                           int n_blocks, hipError_t *err) {
-    hipStream_t keep = e->ls;
-    e->ls = e->stream;
-    hipLaunchKernelGGL(big_coeff_pre<T>, big_grid_half(e, n_blocks), dim3(256), 0, e->stream, (const T *)taps, n_taps,
-                       (T)scale, (c2<T> *)e->b_big[0].p, e->L, e->d_bad);
-    big_fft<T>(e, n_blocks, false, e->stream, err);
-    if (*err == hipSuccess) {
-        hipLaunchKernelGGL(big_untangle<T>, big_grid_half(e, n_blocks), dim3(256), 0, e->stream, (const c2<T> *)e->b_big[2].p,
-                           (c2<T> *)H, (size_t)e->L, (const c2<T> *)e->d_tw, e->L, (T)1.0 / (T)(2 * e->L));
-        *err = hipGetLastError();
-    }
-    e->ls = keep;
-}
-
-template <typename T>
-void launch_ifft_out_big(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks,
-                         int first, int count, uint8_t *raw, hipError_t *err) {
-    hipLaunchKernelGGL(big_out_pre<T>, big_grid_half(e, count), dim3(256), 0, e->ls, (const c2<T> *)Zp, chunk_stride,
-                       n_chunks, (c2<T> *)e->b_big[0].p, (const c2<T> *)e->d_tw, e->L);
-    big_fft<T>(e, count, true, e->ls, err);
-    if (*err != hipSuccess) return;
-    hipLaunchKernelGGL(big_out_post<T>, dim3(count), dim3(1024), 0, e->ls, (const c2<T> *)e->b_big[2].p, first, e->d_fmt[1],
-                       e->d_over, e->ch.skip_quant(), raw,
-                       e->ch.timeout<T>(first, e->L), e->L, e->safety_limit,
-                       e->d_status);
-    *err = hipGetLastError();          // (the dither pass behind it: do_outputs)
-}
-
-template <typename T>
-void launch_levels_big(bfhip_engine *e, hipError_t *err) {
-    const int age = block_age(e);
-    const unsigned char *base = (const unsigned char *)e->b_jobs.p;
-    const int V = 16 / (int)sizeof(c2<T>);
-    const int threads = e->mac_threads;
-    const int tiles = (e->L + threads * V - 1) / (threads * V);
-    const c2<T> *twL = (const c2<T> *)e->d_tw;
-    for (auto &lj : e->level_jobs) {
-        if (lj.n_fill > 0) {
-            const FillJob<T> *jobs = (const FillJob<T> *)(base + lj.fill_off);
-            const MixSrc<T> *src = (const MixSrc<T> *)(base + e->src_off);
-            hipLaunchKernelGGL(big_fill_pre<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs, src,
-                               (c2<T> *)e->b_big[0].p, twL, e->L);
-            big_fft<T>(e, lj.n_fill, true, e->ls, err);
-            if (*err != hipSuccess) return;
-            hipLaunchKernelGGL(big_fill_slide<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs,
-                               (const c2<T> *)e->b_big[2].p, (c2<T> *)e->b_big[0].p, e->L);
-            big_fft<T>(e, lj.n_fill, false, e->ls, err);
-            if (*err != hipSuccess) return;
-            hipLaunchKernelGGL(big_fill_post<T>, big_grid_half(e, lj.n_fill), dim3(256), 0, e->ls, jobs, src,
-                               (const c2<T> *)e->b_big[2].p, twL, e->N, e->blockcounter, e->L, (const BlockState *)e->bs_arg);
-        }
-        if (lj.n_filt > 0) {
-            hipLaunchKernelGGL(mac_filter_kernel<T>, dim3(tiles, lj.n_filt), dim3(threads), 0, e->ls,
-                               (const FilterJob<T> *)(base + lj.filt_off), e->L, e->blockcounter, age,
-                               (const BlockState *)e->bs_arg);
-        }
-        if (lj.n_fade > 0) {
-            const FadeJob<T> *jobs = (const FadeJob<T> *)(base + lj.fade_off);
-            hipLaunchKernelGGL(big_fade_pre<T>, big_grid_half(e, 2 * lj.n_fade), dim3(256), 0, e->ls, jobs,
-                               (c2<T> *)e->b_big[0].p, twL, e->L);
-            big_fft<T>(e, 2 * lj.n_fade, true, e->ls, err);
-            if (*err != hipSuccess) return;
-            hipLaunchKernelGGL(big_fade_mix<T>, dim3((unsigned)(e->L / 256), (unsigned)lj.n_fade), dim3(256), 0, e->ls,
-                               (const c2<T> *)e->b_big[2].p, (c2<T> *)e->b_big[0].p, e->L);
-            big_fft<T>(e, lj.n_fade, false, e->ls, err);
-            if (*err != hipSuccess) return;
-            hipLaunchKernelGGL(big_fade_post<T>, big_grid_half(e, lj.n_fade), dim3(256), 0, e->ls, jobs,
-                               (const c2<T> *)e->b_big[2].p, twL, e->L);
-        }
-        if ((*err = hipGetLastError()) != hipSuccess) return;
-    }
-}
-
-#define DISPATCH_BIG(FN, ...)                                               \
-    do {                                                                    \
-        if (e->rs == 4) FN<float>(__VA_ARGS__); else FN<double>(__VA_ARGS__); \
-    } while (0)
 
 size_t raw_extent(const std::vector<bfhip_format> &v, int n, int L) {
     size_t m = 0;
@@ -691,16 +188,6 @@ int check_format(const bfhip_format *f) {
     return f->sample_spacing >= 1 && f->byte_offset >= 0;
 }
 
-int record(bfhip_engine *e, int stage, bool end) {
-    if (!e->timed_now) return BFHIP_OK;
-    if (e->bs_arg != nullptr) return BFHIP_OK;           // a graph is being captured: replayed blocks are not timed
-    HIPCHK(hipEventRecord(e->ev[(size_t)e->ev_used * EV_PER_BLOCK + 2 * stage + end], e->ls));
-    if (end) e->timed_mask |= 1 << stage;
-    return BFHIP_OK;
-}
-int record_begin(bfhip_engine *e, int stage) { return record(e, stage, false); }
-int record_end(bfhip_engine *e, int stage) { return record(e, stage, true); }
-
 // is the block in progress one of the timed ones?  Decided once per block, by whichever entry
 // point touches it first (block_dev, or the phase calls of a multi-GPU host).
 void timing_begin(bfhip_engine *e) {
@@ -711,8 +198,6 @@ void timing_begin(bfhip_engine *e) {
 }
 
 int poll_coeff_changes(bfhip_engine *e);
-int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first,
-               int count, void *rawout_dev);
 
 // restores "the next launch goes to the main stream" on every return path of a schedule that sends
 // launches to a side stream (an error in the middle must not leave e->ls pointing there: the do_*
@@ -781,129 +266,6 @@ int ensure_ready(bfhip_engine *e) {
         return build_plan(e);
     }
     return BFHIP_OK;
-}
-
-int do_inputs(bfhip_engine *e, const void *rawin_dev, unsigned int ahead = 0u /* blocks ahead of the counter (block pairs) */) {
-    { int rv = channels_before_k1(e, rawin_dev); if (rv != BFHIP_OK) return rv; }
-    hipError_t err = hipSuccess;
-    const int slot = (int)((e->blockcounter + ahead) % (unsigned int)e->R);
-    if (e->big) { int rr = big_reserve(e, (size_t)e->n_ch[0]); if (rr != BFHIP_OK) return rr; }
-    if (e->big) DISPATCH_BIG(launch_fft_in_big, e, (const uint8_t *)rawin_dev, slot, &err);
-    else if (e->wave) { DISPATCH_WAVE(launch_fft_in_wave, e, (const uint8_t *)rawin_dev, slot, &err) }
-    else DISPATCH(launch_fft_in, e, (const uint8_t *)rawin_dev, slot, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "fft_in launch: %s", hipGetErrorString(err));
-    if (e->lw_struct) launch_io_long(e, nullptr, 0, nullptr, true, &err);       // behind it: it reads prev
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "long fft_in launch: %s", hipGetErrorString(err));
-    return BFHIP_OK;
-}
-
-int do_levels(bfhip_engine *e) {
-    bool any = false;
-    for (auto &lj : e->level_jobs) any = any || lj.n_fill || lj.n_filt || lj.n_fade;
-    if (!any) return BFHIP_OK;
-    hipError_t err = hipSuccess;
-    { const int rr = record_begin(e, T_LEVELS); if (rr != BFHIP_OK) return rr; }
-    if (e->big) {
-        size_t need = 1;
-        for (auto &lj : e->level_jobs) need = std::max(need, std::max((size_t)lj.n_fill, (size_t)2 * lj.n_fade));
-        int rr = big_reserve(e, need);
-        if (rr != BFHIP_OK) return rr;
-    }
-    if (e->big) DISPATCH_BIG(launch_levels_big, e, &err);
-    else DISPATCH(launch_levels, e, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "level kernels: %s", hipGetErrorString(err));
-    return record_end(e, T_LEVELS);
-}
-
-int do_mac(bfhip_engine *e, void *Zp, bool may_long = true) {
-    hipError_t err = hipSuccess;
-    e->zp_is_sum = false;
-    // the long plan covers blocks whose partial sums stay in the engine's own buffers and are converted
-    // by its own output pass (not the phase calls, which hand standard spectra to the caller)
-    const int zi = zp_index(e, Zp);
-    const bool lng = e->lw_active && zi >= 0 && may_long;
-    if (zi >= 0) e->zp_long[zi] = lng;
-    // look-ahead (not under a captured graph or in real-time mode, whose launch arguments are frozen):
-    // the head pass when the block's three ahead buffers are current, else the full long MAC; either way
-    // the tail pass of this call's slice for the next three blocks behind it (in the head pass's launch)
-    const bool la = lng && e->la_active && e->bs_arg == nullptr && !e->rt.on;
-    if (la && la_block_valid(e)) {
-        launch_mac_la(e, Zp, true, &err);
-        if (err != hipSuccess) return fail(BFHIP_EHIP, "look-ahead mac launch: %s", hipGetErrorString(err));
-        e->n_la_head++;
-        return BFHIP_OK;
-    }
-    if (lng) { launch_mac_long(e, Zp, &err); if (la) e->n_la_full++; }
-    else if (e->rs == 4) launch_mac<float>(e, Zp, &err); else launch_mac<double>(e, Zp, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "mac launch: %s", hipGetErrorString(err));
-    e->n_mac_launches++;
-    if (la) {
-        launch_mac_la(e, nullptr, false, &err);
-        if (err != hipSuccess) return fail(BFHIP_EHIP, "look-ahead mac launch: %s", hipGetErrorString(err));
-    } else {
-        e->la_epoch++;             // a block without a tail pass: what is stored ahead no longer lines up
-    }
-    return BFHIP_OK;
-}
-
-// the sum over the chunks of Zp into Z (Z == Zp: in place, into chunk 0)
-int sum_chunks(bfhip_engine *e, const void *Zp, void *Z) {
-    hipError_t err = hipSuccess;
-    if (e->rs == 4) launch_sum<float>(e, Zp, Z, &err); else launch_sum<double>(e, Zp, Z, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "sum_partials launch: %s", hipGetErrorString(err));
-    return BFHIP_OK;
-}
-
-int do_outputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first,
-               int count, void *rawout_dev) {
-    hipError_t err = hipSuccess;
-    if (count <= 0) return BFHIP_OK;
-    if (e->ch.outputs_at_once() && (first != 0 || count != e->n_ch[1]))
-        return fail(BFHIP_EINVAL, "outputs that share a physical channel cannot be split over several calls");
-    const bool lng = zp_is_long(e, Zp);
-    if (lng && (first != 0 || count != e->n_ch[1]))
-        return fail(BFHIP_EINVAL, "a long-window block's outputs are converted all at once");
-    if (!lng && n_chunks > 2 && n_chunks == e->n_chunks && first == 0 && count == e->n_ch[1] &&
-        chunk_stride == (size_t)e->n_out_padded * e->L) {
-        // many partials (few long filters): the one-workgroup-per-channel output pass would walk
-        // them one dependent load after the other; add them up with the whole chip first
-        // (in place, same order) and hand over a single spectrum per channel
-        { const int rr = sum_chunks(e, Zp, const_cast<void *>(Zp)); if (rr != BFHIP_OK) return rr; }
-        n_chunks = 1;
-    }
-    uint8_t *const raw = k3_target(e, rawout_dev);
-    if (e->big) { int rr = big_reserve(e, (size_t)count); if (rr != BFHIP_OK) return rr; }
-    if (lng) launch_io_long(e, Zp, count, raw, false, &err);
-    else if (e->big) DISPATCH_BIG(launch_ifft_out_big, e, Zp, chunk_stride, n_chunks, first, count, raw, &err);
-    else if (e->wave) { DISPATCH_WAVE(launch_ifft_out_wave, e, Zp, chunk_stride, n_chunks, first, count, raw, &err) }
-    else DISPATCH(launch_ifft_out, e, Zp, chunk_stride, n_chunks, first, count, raw, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "ifft_out launch: %s", hipGetErrorString(err));
-    // what the channel stage launches behind the inverse transforms is timed apart: the reference's real2raw column
-    const bool post = e->ch.follows_k3();
-    if (post) { const int rr = record_begin(e, T_POST); if (rr != BFHIP_OK) return rr; }
-    { int rv = channels_after_k3(e, rawout_dev, first, count); if (rv != BFHIP_OK) return rv; }
-    return post ? record_end(e, T_POST) : BFHIP_OK;
-}
-
-// [K3 of an owed block | K1 of this block] in one launch; callers take this path only when the channel stage is
-// plain(), so that its two calls add nothing around the launch but the transposes of wide sides
-int fused_outputs_inputs(bfhip_engine *e, const void *Zp, size_t chunk_stride, int n_chunks, int first, int count,
-                         void *rawout_dev, const void *rawin_dev) {
-    int r;
-    if ((r = channels_before_k1(e, rawin_dev)) != BFHIP_OK) return r;
-    hipError_t err = hipSuccess;
-    const int slot = (int)(e->blockcounter % (unsigned int)e->R);
-    // an owed long-window block: its output pass rides with the long transforms of this block instead
-    const bool lng = zp_is_long(e, Zp);
-    if (lng && (first != 0 || count != e->n_ch[1]))
-        return fail(BFHIP_EINVAL, "a long-window block's outputs are converted all at once");
-    const int n_std = lng ? 0 : count;
-    if (e->wave) { DISPATCH_WAVE(launch_io_wave, e, Zp, chunk_stride, n_chunks, first, n_std, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err) }
-    else DISPATCH(launch_io, e, Zp, first, n_std, k3_target(e, rawout_dev), (const uint8_t *)rawin_dev, slot, &err);   // (one chunk)
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "io launch: %s", hipGetErrorString(err));
-    if (e->lw_struct) launch_io_long(e, Zp, lng ? count : 0, k3_target(e, rawout_dev), true, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "long io launch: %s", hipGetErrorString(err));
-    return channels_after_k3(e, rawout_dev, first, count);
 }
 
 // The three passes of a block with their timing records, each on e->ls: a schedule switches streams
@@ -1020,9 +382,7 @@ int rt_enqueue_overlap(bfhip_engine *e, int p) {
     if ((r = block_in_order(e, rt.d_in[p], 0, rt.d_out[p])) != BFHIP_OK) return r;
     RtCopy none;
     none.dst = nullptr; none.src = nullptr; none.n16 = 0; none.pad = 0;
-    hipLaunchKernelGGL(rt_tail_kernel<0>, dim3(1), dim3(256), 0, e->stream, none, e->d_bs, e->N,
-                       (const DevOverflow *)e->d_over, rt.h_over[p], e->n_ch[1], e->d_status, rt.h_status[p], e->d_rt_arrive);
-    HIPCHK(hipGetLastError());
+    if ((r = rt_tail(e, 1u, none, p)) != BFHIP_OK) return r;
     HIPCHK(hipEventRecord(rt.ev_cmp[p], e->stream));
     HIPCHK(hipStreamWaitEvent(rt.s_d2h, rt.ev_cmp[p], 0));
     HIPCHK(hipMemcpyAsync(rt.h_out[p], rt.d_out[p], e->raw_bytes[1], hipMemcpyDeviceToHost, rt.s_d2h));
@@ -1044,19 +404,14 @@ int rt_enqueue(bfhip_engine *e, int p) {
     cout.n16 = nodes ? 0u : (unsigned int)((e->raw_bytes[1] + 15) / 16); cout.pad = 0;
     if (nodes) {
         HIPCHK(hipMemcpyAsync(e->d_rawin, rt.h_in[p], e->raw_bytes[0], hipMemcpyHostToDevice, e->stream));
-    } else {
-        hipLaunchKernelGGL(rt_copy_in_kernel<0>, dim3((cin.n16 + 255) / 256), dim3(256), 0, e->stream, cin);
-        HIPCHK(hipGetLastError());
+    } else if ((r = rt_copy_in(e, cin)) != BFHIP_OK) {
+        return r;
     }
     // (plain launches of a timed engine -- bfhip_engine_enable_timing; `benchmark: true` hosts ask for
     // BFHIP_RT_NO_GRAPH -- are bracketed by events like bfhip_engine_block_dev's; captured ones are not)
     if ((r = block_in_order(e, e->d_rawin, 0, e->d_rawout)) != BFHIP_OK) return r;
     if (nodes) HIPCHK(hipMemcpyAsync(rt.h_out[p], e->d_rawout, e->raw_bytes[1], hipMemcpyDeviceToHost, e->stream));
-    hipLaunchKernelGGL(rt_tail_kernel<0>, dim3(nodes ? 1u : (cout.n16 + 255) / 256), dim3(256), 0, e->stream, cout,
-                       e->d_bs, e->N, (const DevOverflow *)e->d_over, rt.h_over[p], e->n_ch[1], e->d_status,
-                       rt.h_status[p], e->d_rt_arrive);
-    HIPCHK(hipGetLastError());
-    return BFHIP_OK;
+    return rt_tail(e, nodes ? 1u : (cout.n16 + 255) / 256, cout, p);
 }
 
 int rt_capture(bfhip_engine *e, int p) {
@@ -1321,12 +676,7 @@ static int add_coeff_common(bfhip_engine *e, const void *taps, bool on_device, i
     const size_t h_bytes = (size_t)n_blocks * L * e->csize();
     if ((c.d_H = coeff_alloc(e, h_bytes)) == nullptr)
         return fail(BFHIP_ENOMEM, "out of device memory for coefficient set");
-    hipError_t err = hipSuccess;
-    if (e->big) {
-        { int rr = big_reserve(e, (size_t)n_blocks); if (rr != BFHIP_OK) { coeff_release(e, c.d_H, h_bytes); return rr; } }
-        DISPATCH_BIG(launch_coeff_prep_big, e, src, n_taps, scale, c.d_H, n_blocks, &err);
-    } else DISPATCH(launch_coeff_prep, e, src, n_taps, scale, c.d_H, n_blocks, &err);
-    if (err != hipSuccess) { coeff_release(e, c.d_H, h_bytes); return fail(BFHIP_EHIP, "coeff_prep launch: %s", hipGetErrorString(err)); }
+    { const int rp = coeff_prep(e, src, n_taps, scale, c.d_H, n_blocks); if (rp != BFHIP_OK) { coeff_release(e, c.d_H, h_bytes); return rp; } }
     if (on_device) { int _r = sync_all(e); if (_r != BFHIP_OK) { coeff_release(e, c.d_H, h_bytes); return _r; } }
     if (!on_device) {
         // host-taps path is synchronous, like convolver_coeffs2cbuf: report NaN/Inf now
@@ -1381,12 +731,7 @@ static int upload_processed_block(bfhip_engine *e, Coeff &c, int block, const vo
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }      // d_taps is reused; nothing may still read H
     HIPCHK(hipMemcpy(e->b_taps.p, cbuf, bytes, hipMemcpyHostToDevice));
     void *H = (unsigned char *)c.d_H + (size_t)block * e->L * e->csize();
-    const dim3 grid((e->L + 255) / 256, 1);
-    if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->b_taps.p, (c2<float> *)H, e->L, 1, (float *)nullptr);
-    else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->b_taps.p, (c2<double> *)H, e->L, 1, (double *)nullptr);
-    HIPCHK(hipGetLastError());
+    { int _r = coeff_reorder(e, e->b_taps.p, H, 1, true); if (_r != BFHIP_OK) return _r; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     return e->rs == 4 ? stream_refresh_block<float>(e, c.d_H, block) : stream_refresh_block<double>(e, c.d_H, block);
 }
@@ -1500,12 +845,7 @@ int bfhip_engine_add_coeff_processed(bfhip_engine *e, const void *cbufs, int n_b
     c.n_blocks = n_blocks;
     if ((c.d_H = coeff_alloc(e, (size_t)n_blocks * e->L * e->csize())) == nullptr)
         return fail(BFHIP_ENOMEM, "out of device memory for coefficient set");
-    const dim3 grid((e->L + 255) / 256, n_blocks);
-    if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)e->b_taps.p, (c2<float> *)c.d_H, e->L, 1, (float *)nullptr);
-    else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)e->b_taps.p, (c2<double> *)c.d_H, e->L, 1, (double *)nullptr);
-    HIPCHK(hipGetLastError());
+    { int _r = coeff_reorder(e, e->b_taps.p, c.d_H, n_blocks, true); if (_r != BFHIP_OK) return _r; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     e->coeffs.push_back(c);
     return (int)e->coeffs.size() - 1;
@@ -1519,12 +859,7 @@ int bfhip_engine_read_coeff_processed(bfhip_engine *e, int coeff, void *cbufs) {
     const int nb = e->coeffs[coeff].n_blocks;
     const size_t bytes = (size_t)nb * 2 * e->L * e->rs;
     { const int rt = taps_reserve(e, bytes); if (rt != BFHIP_OK) return rt; }
-    const dim3 grid((e->L + 255) / 256, nb);
-    if (e->rs == 4)
-        hipLaunchKernelGGL(reorder_kernel<float>, grid, dim3(256), 0, e->stream, (const float *)nullptr, (c2<float> *)e->coeffs[coeff].d_H, e->L, 0, (float *)e->b_taps.p);
-    else
-        hipLaunchKernelGGL(reorder_kernel<double>, grid, dim3(256), 0, e->stream, (const double *)nullptr, (c2<double> *)e->coeffs[coeff].d_H, e->L, 0, (double *)e->b_taps.p);
-    HIPCHK(hipGetLastError());
+    { int _r = coeff_reorder(e, e->b_taps.p, e->coeffs[coeff].d_H, nb, false); if (_r != BFHIP_OK) return _r; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     HIPCHK(hipMemcpy(cbufs, e->b_taps.p, bytes, hipMemcpyDeviceToHost));
     return nb;
@@ -1542,12 +877,7 @@ int bfhip_engine_update_coeff_block(bfhip_engine *e, int coeff, int block, const
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     HIPCHK(hipMemcpy(e->b_taps.p, taps, bytes, hipMemcpyHostToDevice));
     void *H = (unsigned char *)e->coeffs[coeff].d_H + (size_t)block * e->L * e->csize();
-    hipError_t err = hipSuccess;
-    if (e->big) {
-        { int rr = big_reserve(e, 1); if (rr != BFHIP_OK) return rr; }
-        DISPATCH_BIG(launch_coeff_prep_big, e, e->b_taps.p, e->L, 1.0, H, 1, &err);
-    } else DISPATCH(launch_coeff_prep, e, e->b_taps.p, e->L, 1.0, H, 1, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "coeff_prep launch: %s", hipGetErrorString(err));
+    { const int rp = coeff_prep(e, e->b_taps.p, e->L, 1.0, H, 1); if (rp != BFHIP_OK) return rp; }
     { int _r = sync_all(e); if (_r != BFHIP_OK) return _r; }
     return e->rs == 4 ? stream_refresh_block<float>(e, e->coeffs[coeff].d_H, block)
                       : stream_refresh_block<double>(e, e->coeffs[coeff].d_H, block);
@@ -1587,10 +917,8 @@ int bfhip_internal_engine_update_coeff_dev_async(bfhip_engine *e, int coeff, con
     HIPCHK(hipSetDevice(e->device));
     if ((long)n_taps > (long)n_blocks * e->L) n_taps = n_blocks * e->L;
     HIPCHK(hipMemsetAsync(e->d_bad, 0, sizeof(int), e->stream));
-    hipError_t err = hipSuccess;
-    if (e->big) DISPATCH_BIG(launch_coeff_prep_big, e, taps_dev, n_taps, 1.0, c.d_H, n_blocks, &err);
-    else DISPATCH(launch_coeff_prep, e, taps_dev, n_taps, 1.0, c.d_H, n_blocks, &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "coeff_prep launch: %s", hipGetErrorString(err));
+    // (the scratch above 8192 points was checked above: nothing is reserved, nothing waits)
+    { const int rp = coeff_prep(e, taps_dev, n_taps, 1.0, c.d_H, n_blocks); if (rp != BFHIP_OK) return rp; }
     HIPCHK(hipMemcpyAsync(bad_host, e->d_bad, sizeof(int), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemsetAsync(e->d_bad, 0, sizeof(int), e->stream));
     // the layouts compare sets by pointer, which an in-place rewrite does not change
@@ -1949,15 +1277,9 @@ static int promote_filter(bfhip_engine *e, int fi) {
     const double sc = f.in_scale[0] * e->fmt[0][e->ch.v2p[0][ch]].scale;
     const int n_valid = (int)std::min<unsigned long long>(e->blocks_done, (unsigned long long)e->N);
     if (n_valid > 0) {
-        const dim3 grid((e->L + 255) / 256, n_valid);
         const unsigned char *src = (const unsigned char *)e->d_ring + (size_t)ch * e->R * e->L * e->csize();
-        if (e->rs == 4)
-            hipLaunchKernelGGL(promote_ring_kernel<float>, grid, dim3(256), 0, e->stream, (const c2<float> *)src, e->R,
-                               (c2<float> *)ring, e->N, e->L, e->blockcounter, delay, (float)sc, n_valid);
-        else
-            hipLaunchKernelGGL(promote_ring_kernel<double>, grid, dim3(256), 0, e->stream, (const c2<double> *)src, e->R,
-                               (c2<double> *)ring, e->N, e->L, e->blockcounter, delay, sc, n_valid);
-        HIPCHK(hipGetLastError());
+        const int r = promote_ring(e, src, ring, delay, sc, n_valid);
+        if (r != BFHIP_OK) return r;
     }
     e->promoted[fi] = ring;
     e->plan_dirty = true;
@@ -2228,9 +1550,7 @@ int bfhip_engine_block_pair_dev(bfhip_engine *e, const void *rawin0_dev, void *r
     if ((r = do_inputs(e, rawin1_dev, 1u)) != BFHIP_OK) return r;
     if ((r = record_end(e, T_IN)) != BFHIP_OK) return r;
     if ((r = record_begin(e, T_MAC)) != BFHIP_OK) return r;
-    hipError_t err = hipSuccess;
-    if (e->rs == 4) launch_mac2<float>(e, e->d_Zp[0], e->d_Zp[1], &err); else launch_mac2<double>(e, e->d_Zp[0], e->d_Zp[1], &err);
-    if (err != hipSuccess) return fail(BFHIP_EHIP, "mac2 launch: %s", hipGetErrorString(err));
+    if ((r = do_mac_pair(e, e->d_Zp[0], e->d_Zp[1])) != BFHIP_OK) return r;
     e->zp_last = 1;
     if ((r = record_end(e, T_MAC)) != BFHIP_OK) return r;
     if ((r = record_begin(e, T_OUT)) != BFHIP_OK) return r;

@@ -1,6 +1,6 @@
 // engine.h -- the engine's state, and the helpers that the host units of the engine use: bfhip.hip (the
-// C ABI of include/bfhip.h, the block schedules), plan.hip (the plan builder) and channels.hip (the channel
-// stage, whose own state and interface are in channels.h).
+// C ABI of include/bfhip.h, the block schedules), plan.hip (the plan builder), channels.hip (the channel
+// stage, whose own state and interface are in channels.h) and passes.hip (every kernel launch; passes.h).
 // Internal: nothing here is part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,7 +31,7 @@ static inline hipError_t dev_alloc(void **p, size_t bytes) { return bfhip_intern
 template <typename P> static hipError_t dev_alloc(P **p, size_t bytes) { return bfhip_internal_dev_alloc((void **)p, bytes); }
 static inline hipError_t pin_alloc(void **p, size_t bytes, unsigned int flags) { return bfhip_internal_pin_alloc(p, bytes, flags); }
 
-// What the two units share by name lives in this namespace: hidden, so that the dynamic symbols of
+// What the units share by name lives in this namespace: hidden, so that the dynamic symbols of
 // the library stay those of the C ABI.
 #define BFHIP_HOST_NS namespace bfhip_host __attribute__((visibility("hidden")))
 
@@ -215,7 +215,7 @@ struct bfhip_engine {
     size_t zp_bytes = 0;
     DevBuf b_entries;                  // MacEntry per entry
     DevBuf b_chunks;                   // ChunkRange per (group, chunk) | d_diag_jobs
-    bool zp_is_sum = false;            // chunk 0 of the last block's partial-sum buffer holds the sum over all chunks (launch_sum in place)
+    bool zp_is_sum = false;            // chunk 0 of the last block's partial-sum buffer holds the sum over all chunks (sum_chunks in place)
     uint8_t *d_rawin = nullptr, *d_rawout = nullptr;
     size_t raw_bytes[2] = {0, 0};
     DevBuf b_taps;
@@ -360,8 +360,10 @@ template <typename K> hipError_t allow_lds(K kernel, size_t bytes) {
 // bfhip.hip
 int sync_all(bfhip_engine *e);
 int zp_depth(const bfhip_engine *e);
-int la_prime(bfhip_engine *e);
 int coeff_make_resident(bfhip_engine *e, int ci);
+
+// passes.hip (what the plan builder needs of it; the rest: passes.h)
+int la_prime(bfhip_engine *e);
 
 // plan.hip
 int clamp_delay(const bfhip_engine *e, int d);

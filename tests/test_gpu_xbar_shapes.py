@@ -312,10 +312,10 @@ def test_integer_outputs_on_the_big_transform(monkeypatch, L, fmt):
 # ------------------------------------------------------------------ e. one-to-one plans
 
 def diag_tiles(L, rs, tsplit_env):
-    """(TL, tsplit) for a one-to-one plan under BFHIP_DIAG_TSPLIT: a copy of launch_mac's choice in
-    bfhip.hip (the mac_diag_kernel launch), which the engine does not report.  It only turns the
+    """(TL, tsplit) for a one-to-one plan under BFHIP_DIAG_TSPLIT: a copy of diag_geometry in
+    passes.hip (the mac_diag_kernel launch), which the engine does not report.  It only turns the
     table below (DIAG: the TL and tsplit each case is meant to reach) into the environment that
-    reaches it; if launch_mac's choice changes, this copy and the table have to follow it"""
+    reaches it; if diag_geometry's choice changes, this copy and the table have to follow it"""
     all_tiles = max(1, L // (256 * (2 if rs == 4 else 1)))
     ts = 1
     while ts * 2 <= min(all_tiles, tsplit_env):

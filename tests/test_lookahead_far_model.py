@@ -1,5 +1,5 @@
 """float64 model of the two-tier look-ahead schedule of the long-window MAC (kernels.h: mac_la_kernel with
-its third phase bit, la_far_phase; bfhip.hip: do_mac, la_prime and the two validity tables), against direct
+its third phase bit, la_far_phase; passes.hip: do_mac, la_prime and the two validity tables), against direct
 convolution.
 
 Call t runs, for the entries of near slice t mod 3, partition 1 of blocks t+1 .. t+3 into

@@ -1,5 +1,5 @@
 """float64 model of the look-ahead schedule of the long-window MAC (kernels.h: mac_la_head_kernel,
-mac_la_tail_kernel; bfhip.hip: do_mac and its validity table), against direct convolution.
+mac_la_tail_kernel; passes.hip: do_mac and its validity table), against direct convolution.
 
 Call t runs, for the entries of slice t mod 3, the tail partitions (p >= 1) of blocks t+1, t+2, t+3 and
 stores them in the ahead buffers A[(t+k) mod 4][t mod 3]; the block's own output is the head pass

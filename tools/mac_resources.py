@@ -3,8 +3,8 @@
 
     python3 tools/mac_resources.py [--parent OTHER_TREE] > profiles/mac_lean_resources.json
 
-Compiles brutefir_amd/csrc/bfhip.hip for gfx950 to assembly (device side only; no GPU needed) and
-reads, per kernel whose name starts with `mac_`: the register counts and the scratch size from the
+Compiles brutefir_amd/csrc/passes.hip, the unit that launches (and so instantiates) the MAC kernels, for
+gfx950 to assembly (device side only; no GPU needed; a tree from before that unit existed: bfhip.hip) and reads, per kernel whose name starts with `mac_`: the register counts and the scratch size from the
 kernel metadata, and the instruction mix of its steady loop -- the innermost multiplying loop (label .. backward
 branch) that holds the most fused multiply-adds.  With --parent the same is done for another checkout
 and the two are put side by side (the format of profiles/mac_refactor_resources.json, plus "loops").
@@ -21,12 +21,16 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-o
 COLUMNS = ["vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count"]
 
 
+def unit(tree):
+    src = os.path.join(tree, "brutefir_amd", "csrc", "passes.hip")
+    return src if os.path.exists(src) else os.path.join(tree, "brutefir_amd", "csrc", "bfhip.hip")
+
+
 def assembly(tree):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "bfhip.s")
-        subprocess.check_call([hipcc if os.path.exists(hipcc) else "hipcc"] + FLAGS +
-                              [os.path.join(tree, "brutefir_amd", "csrc", "bfhip.hip"), "-o", out])
+        out = os.path.join(d, "unit.s")
+        subprocess.check_call([hipcc if os.path.exists(hipcc) else "hipcc"] + FLAGS + [unit(tree), "-o", out])
         return open(out).read()
 
 
@@ -114,7 +118,7 @@ def per_stage(rows):
 
 def main(argv):
     new = kernels(assembly(ROOT))
-    res = {"flags": "hipcc " + " ".join(FLAGS) + " brutefir_amd/csrc/bfhip.hip",
+    res = {"flags": "hipcc " + " ".join(FLAGS) + " " + os.path.relpath(unit(ROOT), ROOT),
            "columns": COLUMNS + ["agpr_count", "loops: the steady loops (innermost multiplying loops with the most fused multiply-adds and loads), leanest first"]}
     if "--parent" in argv:
         par = kernels(assembly(argv[argv.index("--parent") + 1]))
