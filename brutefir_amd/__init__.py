@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libbfhip.so")
 
 IN, OUT = 0, 1
 EQ_LINEAR, EQ_MINIMUM = 0, 1                       # include/bfhip_nupc.h: BFHIP_EQ_*
+SWITCH_ALIGNED, SWITCH_STAGGERED = 0, 1            # include/bfhip_nupc.h: BFHIP_NUPC_SWITCH_*
 EQ_MODES = {"linear": EQ_LINEAR, "minimum": EQ_MINIMUM}
 RT_SPIN, RT_NO_GRAPH, RT_COPY_ENGINE, RT_OVERLAP = 1, 2, 4, 8      # bfhip_engine_rt_begin flags
 COEFF_WATCH, COEFF_LAZY = 1, 2                                       # bfhip_engine_add_coeff_processed_blocks flags
@@ -212,6 +213,10 @@ def lib():
     L.bfhip_nupc_switch_frame.restype = C.c_long
     L.bfhip_nupc_switch_frame.argtypes = [vp]
     L.bfhip_nupc_switch_busy.argtypes = [vp]
+    L.bfhip_nupc_set_switch_mode.argtypes = [vp, ci]
+    L.bfhip_nupc_get_switch_mode.argtypes = [vp]
+    L.bfhip_nupc_switch_frame_segment.restype = C.c_long
+    L.bfhip_nupc_switch_frame_segment.argtypes = [vp, ci]
     L.bfhip_nupc_update_coeff.argtypes = [vp, ci, ci, vp, C.c_long]
     L.bfhip_nupc_set_output_gain.argtypes = [vp, ci, cd]
     L.bfhip_nupc_reserve_filter_gain.argtypes = [vp]
@@ -724,6 +729,19 @@ class Nupc:
 
     def switch_busy(self):
         return bool(self._chk(lib().bfhip_nupc_switch_busy(self.h)))
+
+    # staggered switches: every segment switches at its own next launch (include/bfhip_nupc.h)
+    def set_switch_mode(self, mode):
+        """SWITCH_ALIGNED (default) or SWITCH_STAGGERED, for the switches committed from now on"""
+        self._chk(lib().bfhip_nupc_set_switch_mode(self.h, mode))
+
+    def switch_mode(self):
+        return self._chk(lib().bfhip_nupc_get_switch_mode(self.h))
+
+    def switch_frame_segment(self, segment):
+        """segment's switch frame t_k of the last committed switch, -1 if none yet"""
+        r = lib().bfhip_nupc_switch_frame_segment(self.h, segment)
+        return self._chk(r) if r != -1 else -1
 
     def update_coeff(self, filt, coeff, taps):
         taps = np.ascontiguousarray(taps, self.dt)

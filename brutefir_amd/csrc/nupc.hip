@@ -60,6 +60,29 @@ nupc_accumulate_kernel(T *__restrict__ acc, const T *__restrict__ seg, T *__rest
     if (acc2) acc2[cell] += seg2[i];
 }
 
+// a staggered switch (BFHIP_NUPC_SWITCH_STAGGERED): segment k fades at its own switch frame t_k, so
+// the blend happens here, per segment block, and not in the emit step.  A block that ran under both
+// assignments adds  (1 - w) seg + w seg2  into the live ring, w the weight emit_take gives frame
+// rel = pos + j - t_k: 0 below the switch frame, rel / (F - 1) on the ramp, 1 from F on.  One thread
+// per [frame][out] cell, adjacent threads on adjacent cells of all three arrays.
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_accumulate_fade_kernel(T *__restrict__ acc, const T *__restrict__ seg, const T *__restrict__ seg2,
+                            unsigned long long pos, int A, int n_out, int n_frames, long long rel0, int F) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_frames * n_out) return;
+    const size_t j = i / n_out, o = i % n_out;
+    const size_t cell = (size_t)((pos + j) % (unsigned long long)A) * n_out + o;
+    const long long rel = rel0 + (long long)j;
+    T y = seg[i];
+    if (rel >= F) y = seg2[i];
+    else if (rel >= 0) {
+        const T w = (T)((double)rel / (double)(F - 1));
+        y = ((T)1 - w) * y + w * seg2[i];
+    }
+    acc[cell] += y;
+}
+
 // frame n of output block b out of the ring(s), its cells cleared.  Outside a coefficient switch
 // (acc_new == nullptr) only the live ring is read.  Inside one, acc_old holds the old assignment's
 // output and acc_new the new one's; frame t of the block (rel = t - t_sw) is old before the switch
@@ -521,6 +544,11 @@ struct Seg {
     bool pending = false, consumed_once = false;
     unsigned long long pending_pos = 0, due_block = 0;
     void *pending_acc[2] = {nullptr, nullptr};   // the rings d_out / d_out2 of the pending block go to
+    // a pending block of a staggered switch carries its own fade: by the time it is accumulated the
+    // switch may have left busy and another may have been committed
+    bool pending_fade = false;
+    long long pending_tk = 0;
+    int pending_F = 0;
     // coefficient switches (only allocated when some filter has more than one set)
     void *d_out2 = nullptr;     // [L][n_out]: the second assignment's output of a block run under both
     void *d_z = nullptr;        // spectra between the split-phase MAC and output calls
@@ -580,6 +608,11 @@ struct bfhip_nupc {
     int sw_F = 0;                          // its fade length
     long long old_hi = 0;                  // end of the frames the old assignment has written
     std::vector<Asg> sw_old;               // the old assignment (the new one is `live`)
+    // staggered switches (bfhip_nupc_set_switch_mode): every segment switches at its own frame, the
+    // fade is blended into the live ring per segment block; the spare ring and `cur` play no part
+    int switch_mode = BFHIP_NUPC_SWITCH_ALIGNED;   // for the switches committed from now on
+    bool sw_stag = false;                  // the switch in flight (sw) is a staggered one
+    std::vector<long long> t_seg;          // per segment: switch frame of the last committed switch
     // output gain: `gain` is the value asked for last, gain_len the ramp length in force at that
     // call; a block call that finds gain != ramp.g starts a ramp (or steps) from the gain of the last
     // emitted frame.  `ramp` mirrors the device records: they are a pure function of the calls.
@@ -1107,6 +1140,20 @@ int nupc_accumulate(bfhip_nupc *n, const Seg &s, unsigned long long pos, void *a
     return BFHIP_OK;
 }
 
+// a block of a staggered switch that ran under both assignments: blended into the live ring
+int nupc_accumulate_fade(bfhip_nupc *n, const Seg &s, unsigned long long pos, void *acc, long long t_k, int F) {
+    const size_t cnt = (size_t)s.L * n->n_out;
+    const long long rel0 = (long long)pos - t_k;
+    if (n->rs == 4)
+        hipLaunchKernelGGL(nupc_accumulate_fade_kernel<float>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->stream,
+                           (float *)acc, (const float *)s.d_out, (const float *)s.d_out2, pos, n->A, n->n_out, s.L, rel0, F);
+    else
+        hipLaunchKernelGGL(nupc_accumulate_fade_kernel<double>, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, n->stream,
+                           (double *)acc, (const double *)s.d_out, (const double *)s.d_out2, pos, n->A, n->n_out, s.L, rel0, F);
+    NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
 // this period's delay / mute step of one side on its raw block; no launch if no channel of the
 // side is muted or has a delay line with work
 int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
@@ -1237,6 +1284,24 @@ void nupc_commit(bfhip_nupc *n, unsigned long long t_req) {
     std::fill(n->queued.begin(), n->queued.end(), Asg{-1, NAN});
     if (asg == n->live) return;                                   // nothing changes
     const unsigned long long L0 = (unsigned long long)n->seg[0].L;
+    n->t_seg.resize(n->seg.size());
+    if (n->switch_mode == BFHIP_NUPC_SWITCH_STAGGERED) {
+        // segment k switches at the first frame its next launch writes: t_k = e_k - L_k + off_k >= t_req
+        // (off_k >= L_k - L0), t_0 = t_req.  A hard switch needs no block under both assignments: every
+        // segment simply runs the new one from its next launch on, and there is nothing to be busy with.
+        for (size_t k = 0; k < n->seg.size(); k++) {
+            const unsigned long long L = (unsigned long long)n->seg[k].L;
+            const unsigned long long e = (t_req + L0 + L - 1) / L * L;
+            n->t_seg[k] = (long long)(e - L) + n->seg[k].off;
+        }
+        n->sw_old = n->live;
+        n->live = asg;
+        n->t_sw = (long long)t_req;
+        n->sw_F = n->crossfade;
+        n->sw_stag = true;
+        n->sw = n->sw_F > 0;
+        return;
+    }
     long long t_sw = (long long)t_req;
     for (const Seg &s : n->seg) {
         // segment k's first block launched from now on computes frames from e_k - L_k + off_k on
@@ -1250,6 +1315,18 @@ void nupc_commit(bfhip_nupc *n, unsigned long long t_req) {
     n->t_sw = t_sw;
     n->sw_F = n->crossfade;
     n->old_hi = t_sw;          // what was launched before wrote frames < t_sw only
+    n->sw_stag = false;
+    std::fill(n->t_seg.begin(), n->t_seg.end(), t_sw);
+}
+
+// a staggered switch after the block call that received `end` frames: does some segment's next
+// block start before the segment's own fade ends?
+bool nupc_stagger_left(const bfhip_nupc *n, unsigned long long end) {
+    for (size_t k = 0; k < n->seg.size(); k++) {
+        const unsigned long long L = (unsigned long long)n->seg[k].L;
+        if ((long long)(end / L * L) + n->seg[k].off < n->t_seg[k] + n->sw_F) return true;
+    }
+    return false;
 }
 
 // after the block call that emitted frames up to `end`: is old-assignment work or fade left?
@@ -1440,7 +1517,13 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
         // which assignment(s) this block's frames [pos, pos + L) need, and into which ring
         int mode = 1;
         void *acc = n->ring(n->cur), *acc2 = nullptr;
-        if (n->sw) {
+        bool fade = false;
+        const size_t k = (size_t)(&s - n->seg.data());
+        if (n->sw && n->sw_stag) {
+            // the segment's own switch frame decides; everything goes into the live ring
+            fade = (long long)pos < n->t_seg[k] + n->sw_F && (long long)(pos + s.L) > n->t_seg[k];
+            mode = fade ? 2 : 1;
+        } else if (n->sw) {
             const bool need_old = (long long)pos < old_end, need_new = (long long)(pos + s.L) > n->t_sw;
             mode = need_old && need_new ? 2 : need_old ? 0 : 1;
             if (mode == 1) acc = n->ring(1 - n->cur);
@@ -1450,7 +1533,8 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
         const uint8_t *in = n->in_real ? n->d_in_real + rpos * (size_t)n->n_in * n->rs : n->d_in + rpos * n->frame_bytes[0];
         if (s.delay_steps == 0) {
             { const int r = seg_run(n, s, in, mode); if (r < 0) return r; }
-            { const int r = nupc_accumulate(n, s, pos, acc, acc2); if (r < 0) return r; }
+            { const int r = fade ? nupc_accumulate_fade(n, s, pos, acc, n->t_seg[k], n->sw_F) : nupc_accumulate(n, s, pos, acc, acc2);
+              if (r < 0) return r; }
             continue;
         }
         if (s.pending) return nfail(BFHIP_ESTATE, "nupc: a background segment block was never collected");
@@ -1463,20 +1547,27 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
         s.pending_pos = pos;
         s.pending_acc[0] = acc;
         s.pending_acc[1] = acc2;
+        s.pending_fade = fade;
+        s.pending_tk = n->t_seg.empty() ? 0 : n->t_seg[k];
+        s.pending_F = n->sw_F;
         s.due_block = n->block + (unsigned long long)s.delay_steps;
     }
     for (auto &s : n->seg) {
         if (!s.pending || s.due_block != n->block) continue;
         NCHK(hipStreamWaitEvent(n->stream, s.ev_done, 0));
-        { const int r = nupc_accumulate(n, s, s.pending_pos, s.pending_acc[0], s.pending_acc[1]); if (r < 0) return r; }
+        { const int r = s.pending_fade ? nupc_accumulate_fade(n, s, s.pending_pos, s.pending_acc[0], s.pending_tk, s.pending_F)
+                                       : nupc_accumulate(n, s, s.pending_pos, s.pending_acc[0], s.pending_acc[1]);
+          if (r < 0) return r; }
         NCHK(hipEventRecord(s.ev_consumed, n->stream));
         s.pending = false;
         s.consumed_once = true;
     }
     const unsigned long long opos = end - L0;
     // inside a switch window the old assignment's ring is read beside the new one's
-    void *acc_old = n->ring(n->cur), *acc_new = n->sw ? n->ring(1 - n->cur) : nullptr;
-    const long long rel0 = n->sw ? (long long)opos - n->t_sw : 0;
+    // (a staggered switch has blended its fades into the live ring already: the single-ring path)
+    const bool two_rings = n->sw && !n->sw_stag;
+    void *acc_old = n->ring(n->cur), *acc_new = two_rings ? n->ring(1 - n->cur) : nullptr;
+    const long long rel0 = two_rings ? (long long)opos - n->t_sw : 0;
     if (n->rs == 4) {
         if (n->sd_use[1]) nupc_emit_launch<float, true>(n, acc_old, acc_new, opos, rel0, rawout_dev);
         else nupc_emit_launch<float, false>(n, acc_old, acc_new, opos, rel0, rawout_dev);
@@ -1489,7 +1580,9 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     // output delay and mute on the quantised block (block() copies it out behind this)
     { const int r = nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev); if (r < 0) return r; }
     n->block++;
-    if (n->sw && !nupc_switch_left(n, end)) {
+    if (n->sw && n->sw_stag) {
+        if (!nupc_stagger_left(n, end)) n->sw = false;            // the live ring stays the live ring
+    } else if (n->sw && !nupc_switch_left(n, end)) {
         // the old ring has been emitted and cleared down to its last written frame: it is the spare now
         n->sw = false;
         n->cur = 1 - n->cur;
@@ -1580,6 +1673,29 @@ long bfhip_nupc_switch_frame(const bfhip_nupc *n) {
 int bfhip_nupc_switch_busy(const bfhip_nupc *n) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     return n->sw ? 1 : 0;
+}
+
+int bfhip_nupc_set_switch_mode(bfhip_nupc *n, int mode) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (mode != BFHIP_NUPC_SWITCH_ALIGNED && mode != BFHIP_NUPC_SWITCH_STAGGERED)
+        return nfail(BFHIP_EINVAL, "nupc_set_switch_mode: BFHIP_NUPC_SWITCH_ALIGNED or BFHIP_NUPC_SWITCH_STAGGERED");
+    if (n->sw) return nfail(BFHIP_ESTATE, "nupc_set_switch_mode: the previous switch is still in flight (bfhip_nupc_switch_busy)");
+    for (const Asg &q : n->queued)
+        if (q.set >= 0 || !std::isnan(q.gain))
+            return nfail(BFHIP_ESTATE, "nupc_set_switch_mode: a set_coeff / set_filter_gain request is queued");
+    n->switch_mode = mode;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_get_switch_mode(const bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    return n->switch_mode;
+}
+
+long bfhip_nupc_switch_frame_segment(const bfhip_nupc *n, int segment) {
+    if (!n) return nfail(BFHIP_ESTATE, "null");                 // not -1: that means "no switch yet"
+    if (segment < 0 || segment >= (int)n->seg.size()) return nfail(BFHIP_ESTATE, "nupc_switch_frame_segment: bad segment");
+    return n->t_seg.empty() ? -1 : (long)n->t_seg[segment];
 }
 
 // rewrite every partition of an idle set in every segment engine

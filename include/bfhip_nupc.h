@@ -138,6 +138,59 @@ int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff);
 long bfhip_nupc_switch_frame(const bfhip_nupc *n);
 /* 1 while a committed switch has old-coefficient work or fade frames left, else 0 */
 int bfhip_nupc_switch_busy(const bfhip_nupc *n);
+/* ---- staggered switches: heard within one period (an opt-in mode) ---------------------------
+ * The aligned switch above waits for the first frame ALL of whose contributions were launched
+ * after the request: up to max_k off_k frames, and until then every segment block runs twice.
+ * In staggered mode every segment switches as soon as its own next block is launched, as
+ * time-varying partitioned convolvers usually do: the head of the impulse response changes in the
+ * very next period, the tail follows as its blocks come due.
+ *
+ * Switch frames.  A request group committed by the block call whose first output frame is t_req
+ * gives segment k the switch frame
+ *     t_k = e_k - L_k + off_k,   e_k = first multiple of L_k >= t_req + L0,
+ * the first frame segment k's next launch writes.  off_k >= L_k - L0 gives t_k >= t_req, and
+ * t_0 = t_req always.
+ *
+ * Output, in front of output gain, 1/scale, sub-delay FIR, dither and quantisation (unchanged):
+ *     y(t)   = sum_k [ (1 - w_k(t)) y_old,k(t) + w_k(t) y_new,k(t) ]
+ *     w_k(t) = 0 for t < t_k,  (t - t_k) / (F - 1) for t_k <= t < t_k + F,  1 from t_k + F on
+ * (F = 0: a step at t_k).  y_A,k is the full-history convolution of the inputs with segment k's
+ * slice [off_k, off_k + N_k L_k) of the taps under assignment A (a (set, gain) pair per filter,
+ * in and out scales included); sum_k y_A,k is y_A of the aligned contract.  F is
+ * bfhip_nupc_set_crossfade's, with its meaning and limits.  During the fade of segment k the
+ * output is a blend of two assignments that is neither y_old nor y_new in any band: that is what
+ * "the tail follows" means.
+ *
+ * bfhip_nupc_switch_frame returns t_0 = t_req of the last committed switch in this mode, and
+ * bfhip_nupc_switch_frame_segment t_k (in aligned mode: t_sw for every segment).
+ *
+ * bfhip_nupc_switch_busy, after a block call that has received `end` frames, is 1 iff some
+ * segment's NEXT block starts before the segment's own fade ends:
+ *     floor(end / L_k) L_k + off_k < t_k + F   for some k.
+ * Only blocks that overlap [t_k, t_k + F) run under both assignments (the split-phase MAC +
+ * inverse transform twice); they are blended into the one accumulator ring by one kernel.  With
+ * F = 0 a staggered switch is never busy and there is no block under two assignments at all:
+ * every segment runs the new assignment from its next launch on.  A second F = 0 switch committed
+ * before a long segment's e_k therefore REPLACES the first one for that segment: the same t_k,
+ * and the later assignment wins there (the first is never heard from that segment).
+ * Overlapping cross-fades are not offered: set_coeff / set_filter_gain answer BFHIP_ESTATE while
+ * busy, as in aligned mode.  The state rules of update_coeff* and render_eq* keep their wording:
+ * live set, queued set, set of an in-flight (busy) switch.
+ * The mode needs what a switch needs anyway (a second set or bfhip_nupc_reserve_filter_gain) and
+ * allocates nothing.  A convolver that never selects it allocates, launches and computes exactly
+ * as before.  Cost: DESIGN.md section 4.
+ */
+#define BFHIP_NUPC_SWITCH_ALIGNED   0   /* default: one switch frame t_sw for all segments */
+#define BFHIP_NUPC_SWITCH_STAGGERED 1
+/* for the switches committed from now on; before or after finalize.  BFHIP_ESTATE, and nothing
+   changes, while bfhip_nupc_switch_busy is 1 or a set_coeff / set_filter_gain request is queued;
+   BFHIP_EINVAL on a NULL handle or any other mode */
+int bfhip_nupc_set_switch_mode(bfhip_nupc *n, int mode);
+int bfhip_nupc_get_switch_mode(const bfhip_nupc *n);
+/* t_k of the last committed switch (aligned mode: t_sw for every segment); -1 if none yet; a NULL
+   handle or a segment out of range: BFHIP_ESTATE, like bfhip_nupc_switch_frame (BFHIP_EINVAL is -1,
+   which means "no switch yet" here) */
+long bfhip_nupc_switch_frame_segment(const bfhip_nupc *n, int segment);
 /* rewrite a set that is neither live nor part of a queued / in-flight switch (BFHIP_ESTATE
    otherwise), at run time (bflogic_eq's "render into the inactive set, then switch").  Sets added
    by add_coeff cover the whole schedule; set 0 keeps add_filter's length, and taps past it must
