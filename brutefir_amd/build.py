@@ -20,6 +20,7 @@ LIB = os.path.join(HERE, "libbfhip.so")
 INC = os.path.join(HERE, "..", "include")
 PUBLIC = [os.path.join("..", "..", "include", h) for h in ("bfhip.h", "bfhip_convolver.h", "bfhip_nupc.h")]
 DEVICE = ["kernels.h", "fft_lds.h", "fft_wave.h", "bigfft.h"] + PUBLIC
+NUPC = DEVICE + ["nupc.h", "nupc_sched.h", "alloc.h", "eq_render.h", "eq_minphase.h"]
 # translation unit -> what it includes
 UNITS = {
     "bfhip.hip": DEVICE + ["engine.h", "channels.h", "passes.h", "conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],
@@ -27,7 +28,8 @@ UNITS = {
     "plan.hip": DEVICE + ["engine.h", "channels.h", "alloc.h"],
     "channels.hip": DEVICE + ["engine.h", "channels.h", "alloc.h", "dither_init.h", "subdelay_filter.h"],
     "convolver_abi.hip": DEVICE + ["conv_shared.h"],
-    "nupc.hip": DEVICE + ["alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h", "eq_render.h", "eq_minphase.h"],
+    "nupc.hip": NUPC + ["nupc_kernels.h", "dither_init.h", "subdelay_filter.h"],
+    "nupc_update.hip": NUPC + ["coeff_async.h"],
     "host_ops.cpp": ["host_fft.h", "conv_shared.h"] + PUBLIC,
 }
 

@@ -1,6 +1,6 @@
 // coeff_async.h -- the engine half of the non-uniform convolver's asynchronous set rewrite
 // (bfhip_nupc_update_coeff_async, include/bfhip_nupc.h).  Internal to libbfhip.so: defined in
-// bfhip.hip, called from nupc.hip.  bfhip_engine_update_coeff_block (include/bfhip.h) is the
+// bfhip.hip, called from nupc_update.hip.  bfhip_engine_update_coeff_block (include/bfhip.h) is the
 // synchronous, one-partition counterpart.
 #pragma once
 #include "../../include/bfhip.h"

@@ -1,0 +1,483 @@
+// nupc_kernels.h -- every kernel of the non-uniform convolver, its device helpers, and the host wrappers
+// that launch them: accumulate (plain and fading), the delay / mute step, the input conversion with
+// sub-delay, and the emit step (plain and dithering).  Included by nupc.hip only: the kernels live in an
+// anonymous namespace.  The host decides (nupc_sched.h); nothing here does.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+
+#include "nupc.h"
+
+namespace {
+
+// acc[(pos + j) mod A][o] += seg[j][o] for an L_k x n_out block of a segment's output; during a
+// coefficient switch a block that ran under both assignments adds its second output (seg2) into
+// the other ring (acc2) in the same pass
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_accumulate_kernel(T *__restrict__ acc, const T *__restrict__ seg, T *__restrict__ acc2,
+                       const T *__restrict__ seg2, unsigned long long pos, int A, int n_out, int n_frames) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_frames * n_out) return;
+    const size_t j = i / n_out, o = i % n_out;
+    const size_t cell = (size_t)((pos + j) % (unsigned long long)A) * n_out + o;
+    acc[cell] += seg[i];
+    if (acc2) acc2[cell] += seg2[i];
+}
+
+// a staggered switch (BFHIP_NUPC_SWITCH_STAGGERED): segment k fades at its own switch frame t_k, so
+// the blend happens here, per segment block, and not in the emit step.  A block that ran under both
+// assignments adds  (1 - w) seg + w seg2  into the live ring, w the weight emit_take gives frame
+// rel = pos + j - t_k: 0 below the switch frame, rel / (F - 1) on the ramp, 1 from F on.  One thread
+// per [frame][out] cell, adjacent threads on adjacent cells of all three arrays.
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_accumulate_fade_kernel(T *__restrict__ acc, const T *__restrict__ seg, const T *__restrict__ seg2,
+                            unsigned long long pos, int A, int n_out, int n_frames, long long rel0, int F) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_frames * n_out) return;
+    const size_t j = i / n_out, o = i % n_out;
+    const size_t cell = (size_t)((pos + j) % (unsigned long long)A) * n_out + o;
+    const long long rel = rel0 + (long long)j;
+    T y = seg[i];
+    if (rel >= F) y = seg2[i];
+    else if (rel >= 0) {
+        const T w = (T)((double)rel / (double)(F - 1));
+        y = ((T)1 - w) * y + w * seg2[i];
+    }
+    acc[cell] += y;
+}
+
+// frame n of output block b out of the ring(s), its cells cleared.  Outside a coefficient switch
+// (acc_new == nullptr) only the live ring is read.  Inside one, acc_old holds the old assignment's
+// output and acc_new the new one's; frame t of the block (rel = t - t_sw) is old before the switch
+// frame, new from t_sw + F on, and the linear ramp (1 - w) old + w new, w = rel / (F - 1), in
+// between.
+template <typename T>
+__device__ __forceinline__ T emit_take(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos,
+                                       int A, int n_out, int ch, int n, long long rel0, int F) {
+    const size_t c = (size_t)((pos + n) % (unsigned long long)A) * n_out + ch;
+    T y = acc_old[c];
+    acc_old[c] = (T)0;
+    if (acc_new) {
+        const T y_new = acc_new[c];
+        acc_new[c] = (T)0;
+        const long long rel = rel0 + n;
+        if (rel >= F) y = y_new;
+        else if (rel >= 0) {
+            const T w = (T)((double)rel / (double)(F - 1));
+            y = ((T)1 - w) * y + w * y_new;
+        }
+    }
+    return y;
+}
+
+// thread 0 of every emit workgroup, after its channel's status bits are in *status: the last
+// channel to finish hands the status bits of all segments (they OR into the same word) to the
+// host's pinned word: no device-to-host copy after the sync
+__device__ __forceinline__ void emit_hand_off(int *__restrict__ status, unsigned int *__restrict__ arrive,
+                                              int *__restrict__ host_status) {
+    __threadfence();
+    if (atomicAdd(arrive, 1u) + 1u == gridDim.x) {
+        *arrive = 0;
+        const int all_bits = atomicExch(status, 0);
+        if (all_bits) *host_status = *host_status | all_bits;
+        __threadfence_system();
+    }
+}
+
+// ---- per-output factor: 1/scale of the format times the output gain, which may be on a ramp
+// (the record, NupcGain, and the host's mirror of it are in nupc_sched.h)
+// what a thread of the emit step keeps of its channel's record for one period: at(n) is the factor
+// of the period's frame n, a pure function of n
+template <typename T> struct GainFactor {
+    T sc;                          // off the ramp
+    double inv, a, d, len;
+    int done, on;                  // frames n < on of this period are on the ramp
+    __device__ __forceinline__ void load(const NupcGain &r, int L0) {
+        sc = (T)(r.inv * r.g);
+        inv = r.inv; a = r.a; d = r.g - r.a; len = (double)r.len; done = r.done;
+        const int left = r.len - 1 - r.done;
+        on = left < 0 ? 0 : left < L0 ? left : L0;
+    }
+    __device__ __forceinline__ T at(int n) const {
+        if (n >= on) return sc;
+        return (T)(inv * (a + d * ((double)(done + n + 1) / len)));
+    }
+};
+// thread 0, after every thread of the workgroup has loaded the record: the period has been emitted
+__device__ __forceinline__ void gain_advance(NupcGain *__restrict__ r, int L0) {
+    const int done = r->done, len = r->len;
+    if (done < len) r->done = len - done < L0 ? len : done + L0;
+}
+
+// ---- per-channel sub-sample delay (subdelay: / sdf_length; delay.c:416-442 at a period of L0)
+//
+// What the reference computes per period is the causal FIR  y[t] = sum_k h[k] x[t - k]  over the
+// channel's stream, h one of the 199 filters of the bank (subdelay_filter.h) and the last `bs`
+// unfiltered samples carried from period to period.  This period's value of every channel of a
+// side travels in the kernel arguments (-100: the channel has no filter), so a change needs no
+// host wait and reaches the device with the block call it was made before.
+constexpr int kSdChannels = 256;   // channels per side when the side uses sub-delay (BF_MAXCHANNELS)
+constexpr int kSdTile = 2048;      // frames filtered per pass through LDS
+constexpr int kSdMaxBs = 1024;     // largest filter block size: 4 history samples per thread
+struct NupcSdVals { signed char v[kSdChannels]; };
+template <typename T> struct NupcSd {
+    const T *bank;                 // [199][flen] taps, index 99 + value
+    T *hist;                       // [channels of the side][bs]: the last bs unfiltered samples
+    int bs, flen, tile;            // tile = min(L0, kSdTile); bs <= tile, both powers of two
+    NupcSdVals vals;
+};
+static size_t nupc_sd_lds(int bs, int flen, int tile, int rs) { return (size_t)(bs + tile + flen) * rs; }
+
+// One channel's period, by its whole workgroup (256 threads, every thread calls): src(n) is the
+// unfiltered sample of frame n, each asked for once and in order of the tiles; sink(n, y) takes
+// the filtered one.  LDS: xx[bs + tile] = [history | tile], hh[flen] the taps, so no tap and no
+// sample is read from global memory more than once.  L0 above the tile is filtered tile by tile
+// with the history moved down in between.
+template <typename T, typename Src, typename Sink>
+__device__ __forceinline__ void
+sd_fir_period(unsigned char *smem, const NupcSd<T> &sd, int ch, int L0, Src src, Sink sink) {
+    const int tid = threadIdx.x, bs = sd.bs, flen = sd.flen, tile = sd.tile;
+    T *xx = reinterpret_cast<T *>(smem), *hh = xx + bs + tile;
+    const T *taps = sd.bank + (size_t)(99 + sd.vals.v[ch]) * flen;
+    T *hist = sd.hist + (size_t)ch * bs;
+    for (int k = tid; k < flen; k += 256) hh[k] = taps[k];
+    for (int n = tid; n < bs; n += 256) xx[n] = hist[n];
+    for (int t0 = 0; t0 < L0; t0 += tile) {
+        for (int n = tid; n < tile; n += 256) xx[bs + n] = src(t0 + n);
+        __syncthreads();
+        for (int n = tid; n < tile; n += 256) {
+            T acc = (T)0;
+            for (int k = 0; k < flen; k++) acc += hh[k] * xx[bs + n - k];      // flen <= bs: index >= 1
+            sink(t0 + n, acc);
+        }
+        T keep[kSdMaxBs / 256];
+#pragma unroll
+        for (int i = 0; i < kSdMaxBs / 256; i++) { const int n = tid + i * 256; if (n < bs) keep[i] = xx[tile + n]; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kSdMaxBs / 256; i++) { const int n = tid + i * 256; if (n < bs) xx[n] = keep[i]; }
+    }
+    for (int n = tid; n < bs; n += 256) hist[n] = xx[n];          // each thread's own writes: no barrier
+}
+
+// Input side, one launch per period behind the delay / mute step: one workgroup per input channel
+// converts the period's L0 raw samples with load_raw -- the conversion the engines' input transform
+// uses -- into the ring of reals the segment engines read ([frame][n_in], interleaved), through the
+// FIR for a channel that has a filter.  Each channel has its own format, offset and stride in `raw`
+// (a frame slot of the raw ring, or the staged period buffer of a side with planes or several
+// devices); adjacent threads take adjacent samples, so a contiguous plane is read coalesced.
+template <typename T>
+__global__ __launch_bounds__(256) void
+nupc_subdelay_in_kernel(const uint8_t *__restrict__ raw, const DevFormat *__restrict__ fmt, T *__restrict__ real,
+                        int n_in, int L0, const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
+    const int ch = blockIdx.x;
+    const DevFormat f = fmt[ch];
+    const uint8_t *base = raw + f.byte_offset;
+    const size_t stride = (size_t)f.sample_spacing * f.bytes;
+    if (sd.vals.v[ch] == -100) {
+        for (int n = threadIdx.x; n < L0; n += 256) real[(size_t)n * n_in + ch] = load_raw<T>(base + (size_t)n * stride, f);
+        return;
+    }
+    sd_fir_period<T>(sd_smem, sd, ch, L0, [&](int n) { return load_raw<T>(base + (size_t)n * stride, f); },
+                     [&](int n, T y) { real[(size_t)n * n_in + ch] = y; });
+}
+
+// output block b: L_0 frames out of the ring (emit_take), scaled into output units (1/scale times
+// the output gain of the frame, GainFactor), requantised like convolver_cbuf2raw (real2raw.h / dither_funs.h:71-114),
+// ring region cleared.  One workgroup per output channel.  SD: the output side uses sub-delay; a
+// channel that has a filter runs the FIR over the scaled reals -- the values it would have been
+// quantised from -- and quantises the result (sd_fir_period); the others take the plain path.
+template <typename T, bool SD>
+__global__ __launch_bounds__(256) void
+nupc_emit_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
+                 long long rel0, int F, const DevFormat *__restrict__ fmt, NupcGain *__restrict__ gain,
+                 DevOverflow *__restrict__ over, uint8_t *__restrict__ raw, double safety_limit,
+                 int *__restrict__ status, unsigned int *__restrict__ arrive, int *__restrict__ host_status,
+                 const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const DevFormat f = fmt[ch];
+    DevOverflow of = over[ch];
+    uint8_t *base = raw + f.byte_offset;
+    const size_t stride = (size_t)f.sample_spacing * f.bytes;
+    GainFactor<T> sc;
+    sc.load(gain[ch], L0);
+    Quantiser<T> qz;
+    qz.init(f, of, safety_limit);
+    if (SD && sd.vals.v[ch] != -100)
+        sd_fir_period<T>(sd_smem, sd, ch, L0,
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
+                         [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
+    else
+        for (int n = tid; n < L0; n += 256)
+            qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n), base + (size_t)n * stride);
+    qz.reduce(tid, 256);
+    if (tid == 0) {
+        qz.commit(of);
+        over[ch] = of;
+        gain_advance(gain + ch, L0);
+        if (qz.st) atomicOr(status, qz.st);
+        emit_hand_off(status, arrive, host_status);
+    }
+}
+
+// the emit step of a convolver with dithered outputs (launched instead of nupc_emit_kernel, same
+// grid).  A channel without a dither slot (slot[ch] < 0) is requantised exactly as there.  A
+// dithered one stages its L_0 blended, scaled reals -- the very values nupc_emit_kernel would
+// hand to the quantiser, behind the sub-delay FIR if the channel has a filter -- in
+// stage[slot][L0], and wave 0 runs the HP-TPDF chain over them (dither_chain, kernels.h: the
+// uniform engine's dither pass).  The chain ORs its status bits in before thread 0 takes part in
+// the hand-off, so they reach the host with this block's call.
+template <typename T, bool SD>
+__global__ __launch_bounds__(256) void
+nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out,
+                        int L0, long long rel0, int F, const DevFormat *__restrict__ fmt,
+                        NupcGain *__restrict__ gain, DevOverflow *__restrict__ over, uint8_t *__restrict__ raw,
+                        double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
+                        int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
+                        DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
+                        const T *__restrict__ randmap /* index -256..255 (centre pointer) */, const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
+    __shared__ T rmap[512];
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const int slot = dslot[ch];
+    const DevFormat f = fmt[ch];
+    GainFactor<T> sc;
+    sc.load(gain[ch], L0);
+    const bool fir = SD && sd.vals.v[ch] != -100;
+    if (slot < 0) {
+        DevOverflow of = over[ch];
+        uint8_t *base = raw + f.byte_offset;
+        const size_t stride = (size_t)f.sample_spacing * f.bytes;
+        Quantiser<T> qz;
+        qz.init(f, of, safety_limit);
+        if (fir)
+            sd_fir_period<T>(sd_smem, sd, ch, L0,
+                             [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
+                             [&](int n, T y) { qz.put(y, base + (size_t)n * stride); });
+        else
+            for (int n = tid; n < L0; n += 256)
+                qz.put(emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n), base + (size_t)n * stride);
+        qz.reduce(tid, 256);
+        if (tid == 0) {
+            qz.commit(of);
+            over[ch] = of;
+            gain_advance(gain + ch, L0);
+            if (qz.st) atomicOr(status, qz.st);
+            emit_hand_off(status, arrive, host_status);
+        }
+        return;
+    }
+    T *x = stage + (size_t)slot * L0;
+    if (fir)
+        sd_fir_period<T>(sd_smem, sd, ch, L0,
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
+                         [&](int n, T y) { x[n] = y; });
+    else
+        for (int n = tid; n < L0; n += 256) x[n] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n);
+    for (int i = tid; i < 512; i += 256) rmap[i] = randmap[i - 256];
+    __syncthreads();                  // the staged samples are visible to wave 0 (same workgroup)
+    if (tid < 64) {
+        dither_chain<T>(x, dstate + slot, table, table_size, rmap, f, over + ch, raw, L0, safety_limit, status, tid);
+        if (tid == 0) {
+            gain_advance(gain + ch, L0);               // behind the barrier: every thread has its copy
+            emit_hand_off(status, arrive, host_status);
+        }
+    }
+}
+
+// ---- per-channel integer delay and mute on the raw I/O blocks: the device half of the delay machine
+// (the job, NupcDelayJob, and the host half that makes it, NupcDelay, are in nupc_sched.h)
+constexpr int kDelayJobs = 32;     // jobs per launch (2048 bytes of kernel arguments)
+static_assert(sizeof(NupcDelayJob) <= 64, "32 jobs must stay well inside the 4 KB of kernel arguments");
+struct NupcDelayJobs { NupcDelayJob j[kDelayJobs]; };
+
+__device__ __forceinline__ unsigned long long smp_ld(const uint8_t *p, int ss) {
+    unsigned long long v = 0;
+    for (int b = 0; b < ss; b++) v |= (unsigned long long)p[b] << (8 * b);
+    return v;
+}
+__device__ __forceinline__ void smp_st(uint8_t *p, unsigned long long v, int ss) {
+    for (int b = 0; b < ss; b++) p[b] = (uint8_t)(v >> (8 * b));
+}
+// p is 16-byte aligned (arena fragments)
+__device__ __forceinline__ void zero_bytes(uint8_t *p, unsigned long long n) {
+    const unsigned long long n16 = n / 16;
+    for (unsigned long long i = threadIdx.x; i < n16; i += blockDim.x) ((uint4 *)p)[i] = make_uint4(0, 0, 0, 0);
+    for (unsigned long long i = n16 * 16 + threadIdx.x; i < n; i += blockDim.x) p[i] = 0;
+}
+
+// One workgroup per job, on the raw block `raw` of F frames (the job's stride apart, ss-byte
+// samples).  mute_first: input side (do_mute before update_delay: zeros enter the line); else
+// output side (the delayed block is muted).  Every thread reads and writes only its own samples of
+// the raw block; the exchange between samples goes through the arena's scratch fragment.
+__global__ __launch_bounds__(256) void
+nupc_delay_kernel(const NupcDelayJobs jobs, uint8_t *__restrict__ raw, int F, int mute_first) {
+    const NupcDelayJob j = jobs.j[blockIdx.x];
+    uint8_t *buf = raw + j.byte_offset;
+    const int ss = j.ss;
+    const size_t stride = (size_t)j.stride, fragp = (size_t)j.fragp;
+    if (j.kind == 0) {                                             // no delay in force: a muted channel
+        for (int n = threadIdx.x; n < F; n += blockDim.x) smp_st(buf + n * stride, 0, ss);
+        return;
+    }
+    uint8_t *rest = j.line + (size_t)j.rest_frag * fragp, *sh0 = rest + fragp, *sh1 = sh0 + fragp, *tmp = sh1 + fragp;
+    // change_delay's zero-fills, and the block into the scratch (zeros if muted before the line)
+    zero_bytes(j.line, j.zfull);
+    zero_bytes(rest, (unsigned long long)j.zrest);
+    zero_bytes(sh0, (unsigned long long)j.zshort);
+    zero_bytes(sh1, (unsigned long long)j.zshort);
+    const bool mute_in = mute_first && j.muted, mute_out = !mute_first && j.muted;
+    for (int n = threadIdx.x; n < F; n += blockDim.x)
+        smp_st(tmp + (size_t)n * ss, mute_in ? 0ull : smp_ld(buf + n * stride, ss), ss);
+    __syncthreads();                                               // scratch and zero-fills are visible
+    __threadfence_block();
+    const int rr = j.rr;
+    if (j.kind == 1) {                                             // update_delay_buffer, delay.c:229-262
+        uint8_t *fcur = j.line + (size_t)j.cur * fragp;
+        const uint8_t *last = j.line + (size_t)j.last * fragp;
+        for (int n = threadIdx.x; n < F; n += blockDim.x) {
+            smp_st(fcur + (size_t)n * ss, smp_ld(tmp + (size_t)n * ss, ss), ss);
+            unsigned long long y;
+            if (n < rr) {
+                y = smp_ld(rest + (size_t)n * ss, ss);
+                smp_st(rest + (size_t)n * ss, smp_ld(last + (size_t)(F - rr + n) * ss, ss), ss);
+            } else
+                y = smp_ld(last + (size_t)(n - rr) * ss, ss);
+            smp_st(buf + n * stride, mute_out ? 0ull : y, ss);
+        }
+    } else {                                                       // update_delay_short_buffer, :264-281
+        uint8_t *shw = j.cur ? sh1 : sh0;
+        const uint8_t *shr = j.last ? sh1 : sh0;
+        for (int n = threadIdx.x; n < F; n += blockDim.x) {
+            const unsigned long long y = n < rr ? smp_ld(shr + (size_t)n * ss, ss) : smp_ld(tmp + (size_t)(n - rr) * ss, ss);
+            if (n < rr) smp_st(shw + (size_t)n * ss, smp_ld(tmp + (size_t)(F - rr + n) * ss, ss), ss);
+            smp_st(buf + n * stride, mute_out ? 0ull : y, ss);
+        }
+    }
+}
+
+// ---- host: the launches
+
+// the kernels are instantiated per real type, the emit kernels also per "the output side uses sub-delay":
+// f(T(), std::bool_constant<SD>()) with the convolver's two
+template <typename F> void nupc_dispatch(const bfhip_nupc *n, F f) {
+    const bool sd = n->sd.use[1];
+    if (n->rs == 4) { if (sd) f(float(), std::true_type()); else f(float(), std::false_type()); }
+    else { if (sd) f(double(), std::true_type()); else f(double(), std::false_type()); }
+}
+
+// a segment block's output into the ring(s) its plan names: a block that ran under both assignments adds
+// its second output into the second ring (aligned switch) or blends the two into the one (staggered)
+int nupc_accumulate(bfhip_nupc *n, const Seg &s, const BlockPlan &b) {
+    const size_t cnt = (size_t)s.L * n->n_out;
+    const dim3 grid((unsigned)((cnt + 255) / 256));
+    nupc_dispatch(n, [&](auto t, auto) {
+        using T = decltype(t);
+        if (b.fade)
+            hipLaunchKernelGGL(nupc_accumulate_fade_kernel<T>, grid, dim3(256), 0, n->stream, (T *)n->ring(b.ring),
+                               (const T *)s.d_out, (const T *)s.d_out2, b.pos, n->A, n->n_out, s.L,
+                               (long long)b.pos - b.t_k, b.F);
+        else
+            hipLaunchKernelGGL(nupc_accumulate_kernel<T>, grid, dim3(256), 0, n->stream, (T *)n->ring(b.ring),
+                               (const T *)s.d_out, (T *)(b.ring2 < 0 ? nullptr : n->ring(b.ring2)), (const T *)s.d_out2,
+                               b.pos, n->A, n->n_out, s.L);
+    });
+    NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+// this period's delay / mute step of one side on its raw block; no launch if no channel of the
+// side is muted or has a delay line with work
+int nupc_delay_side(bfhip_nupc *n, int io, uint8_t *raw) {
+    // (a side with a declared buffer had every channel's samples checked against it at finalize)
+    for (size_t ch = 0; ch < n->dl[io].size() && !n->io.buf_bytes[io]; ch++) {
+        const bfhip_format &f = n->io.fmt[io][ch];
+        if ((n->dl[io][ch].arena || n->dl[io][ch].muted) &&
+            (f.byte_offset < 0 || (size_t)f.byte_offset + f.bytes > n->io.frame_bytes[io]))
+            return nfail(BFHIP_EINVAL, "nupc: delay / mute on a channel whose samples lie outside the raw frame");
+    }
+    NupcDelayJobs args;
+    int cnt = 0;
+    auto launch = [&]() {
+        hipLaunchKernelGGL(nupc_delay_kernel, dim3(cnt), dim3(256), 0, n->stream, args, raw, n->L0(), io == BFHIP_IN ? 1 : 0);
+        cnt = 0;
+        return hipGetLastError();
+    };
+    for (size_t ch = 0; ch < n->dl[io].size(); ch++) {
+        if (cnt == 0) memset(&args, 0, sizeof(args));
+        NupcDelayJob &jb = args.j[cnt];
+        if (!n->dl[io][ch].step(jb)) continue;
+        const bfhip_format &f = n->io.fmt[io][ch];
+        jb.byte_offset = f.byte_offset;
+        jb.ss = f.bytes;
+        jb.stride = f.sample_spacing * f.bytes;
+        if (++cnt == kDelayJobs) NCHK(launch());
+    }
+    if (cnt > 0) NCHK(launch());
+    return BFHIP_OK;
+}
+
+// this period's sub-delay arguments of one side: the values in force now
+template <typename T> NupcSd<T> nupc_sd_args(const bfhip_nupc *n, int io) {
+    NupcSd<T> a;
+    memset(&a, 0, sizeof(a));
+    memset(a.vals.v, -100, sizeof(a.vals.v));                     // no channel has a filter
+    if (!n->sd.use[io]) return a;
+    a.bank = (const T *)n->sd.d_bank;
+    a.hist = (T *)n->sd.d_hist[io];
+    a.bs = n->sd.bs; a.flen = n->sd.flen; a.tile = std::min(n->L0(), kSdTile);
+    for (size_t ch = 0; ch < n->sd.val[io].size(); ch++) a.vals.v[ch] = (signed char)n->sd.val[io][ch];
+    return a;
+}
+size_t nupc_sd_smem(const bfhip_nupc *n, int io) {
+    return n->sd.use[io] ? nupc_sd_lds(n->sd.bs, n->sd.flen, std::min(n->L0(), kSdTile), n->rs) : 0;
+}
+
+// input side with sub-delay or a declared buffer: the period's raw samples (delayed and muted
+// already; the raw ring's slot, or the stage) become the reals of slot wpos of the ring the segment
+// engines read
+int nupc_subdelay_in(bfhip_nupc *n, const uint8_t *raw_slot, size_t wpos) {
+    uint8_t *real = n->d_in_real + wpos * (size_t)n->n_in * n->rs;
+    nupc_dispatch(n, [&](auto t, auto) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(nupc_subdelay_in_kernel<T>, dim3(n->n_in), dim3(256), nupc_sd_smem(n, 0), n->stream, raw_slot,
+                           n->io.d_fmt[0], (T *)real, n->n_in, n->L0(), nupc_sd_args<T>(n, 0));
+    });
+    NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+// the emit step of the period whose first frame is opos: the four kernels (dither or not, sub-delay on the
+// output side or not) share their leading arguments; the schedule says which rings are read
+int nupc_emit(bfhip_nupc *n, unsigned long long opos, void *rawout_dev) {
+    const Switcher &sw = n->sets.sched;
+    void *acc_old = n->ring(sw.cur), *acc_new = sw.two_rings() ? n->ring(1 - sw.cur) : nullptr;
+    const long long rel0 = sw.rel0(opos);
+    const int L0 = n->L0();
+    nupc_dispatch(n, [&](auto t, auto sd_side) {
+        using T = decltype(t);
+        constexpr bool SD = decltype(sd_side)::value;
+        const NupcSd<T> sd = nupc_sd_args<T>(n, 1);
+        const size_t smem = SD ? nupc_sd_smem(n, 1) : 0;
+        if (!n->dither.ch.empty())
+            hipLaunchKernelGGL((nupc_emit_dither_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old,
+                               (T *)acc_new, opos, n->A, n->n_out, L0, rel0, sw.sw_F, n->io.d_fmt[1], n->og.d,
+                               n->st.d_over, (uint8_t *)rawout_dev, n->safety_limit, n->st.d_status, n->st.d_arrive,
+                               n->st.h_status, n->dither.d_slot, (T *)n->dither.d_stage,
+                               (DitherState<T> *)n->dither.d_state, n->dither.d_table, (int)n->dither.table.size(),
+                               (const T *)n->dither.d_randmap + 256, sd);
+        else
+            hipLaunchKernelGGL((nupc_emit_kernel<T, SD>), dim3(n->n_out), dim3(256), smem, n->stream, (T *)acc_old,
+                               (T *)acc_new, opos, n->A, n->n_out, L0, rel0, sw.sw_F, n->io.d_fmt[1], n->og.d, n->st.d_over,
+                               (uint8_t *)rawout_dev, n->safety_limit, n->st.d_status, n->st.d_arrive, n->st.h_status, sd);
+    });
+    NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+}  // namespace

@@ -1,0 +1,358 @@
+// nupc_update.hip -- the non-uniform convolver's set rewrites (synchronous and asynchronous) and its
+// equaliser renders (include/bfhip_nupc.h; state in nupc.h).  None of this is on the audio path and none of
+// it launches a kernel of nupc_kernels.h: a rewrite uploads the taps and has every segment engine prepare
+// its slice on the engine's own stream, in order with the segment's blocks; a render (eq_render.h,
+// eq_minphase.h) is a producer in front of a rewrite, on the loader stream.  Which sets may be rewritten is
+// the switch schedule's answer (Switcher::set_in_use).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "coeff_async.h"
+#include "nupc.h"
+
+namespace {
+
+bool set_ok(const bfhip_nupc *n, int filter, int coeff) {
+    return filter >= 0 && filter < (int)n->sets.coeff.size() && coeff >= 0 && coeff < (int)n->sets.coeff[filter].size();
+}
+
+// set 0 keeps the partitions add_filter gave it: do these taps reach past them?  Host taps may, with
+// zeros; a device source cannot be looked at without a wait: it must not reach past them at all
+bool past_set(const bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps) {
+    for (const Seg &s : n->seg) {
+        const long covered = s.off + (long)s.n_blocks[filter][coeff] * s.L;
+        const long from = std::min(covered, n_taps), to = std::min(s.off + (long)s.L * s.N, n_taps);
+        if (on_device && from < to) return true;
+        for (long i = from; i < to && !on_device; i++)
+            if (n->rs == 4 ? ((const float *)taps)[i] != 0.0f : ((const double *)taps)[i] != 0.0) return true;
+    }
+    return false;
+}
+
+hipError_t eq_launch(const bfhip_nupc *n, const EqBands &b, long taps, int mode) {
+    if (mode == BFHIP_EQ_MINIMUM)
+        return n->rs == 4 ? eq_minphase_launch<float>(n->eq.lin, n->eq.min, b, taps, n->upd.stream)
+                          : eq_minphase_launch<double>(n->eq.lin, n->eq.min, b, taps, n->upd.stream);
+    return n->rs == 4 ? eq_render_launch<float>(n->eq.lin, b, taps, n->upd.stream)
+                      : eq_render_launch<double>(n->eq.lin, b, taps, n->upd.stream);
+}
+
+// enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
+// no allocation.  Host source: the pinned staging buffer.  Device source: the loader (and the main
+// stream, for its own slices) waits on ready_event.
+int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event) {
+    NupcUpdate &u = n->upd;
+    const size_t rs = (size_t)n->rs;
+    const uint8_t *src = on_device ? (const uint8_t *)taps : u.h_taps;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    bool main_waits = false;
+    if (on_device && ready_event) NCHK(hipStreamWaitEvent(u.stream, (hipEvent_t)ready_event, 0));
+    // upload: a segment that runs on the main stream gets its own slice there (the high-priority
+    // stream never waits for the whole upload); the rest goes through the loader, adjacent slices
+    // in one copy
+    long run_from = -1, run_to = -1;
+    auto flush = [&]() -> hipError_t {
+        if (run_from < 0 || run_to <= run_from) { run_from = run_to = -1; return hipSuccess; }
+        const hipError_t e = hipMemcpyAsync(u.d_taps + (size_t)run_from * rs, src + (size_t)run_from * rs,
+                                            (size_t)(run_to - run_from) * rs, kind, u.stream);
+        run_from = run_to = -1;
+        return e;
+    };
+    for (const Seg &s : n->seg) {
+        const long from = s.off, to = std::min(s.off + (long)s.L * s.N, n_taps);
+        if (to <= from) continue;
+        if (s.delay_steps > 0) {
+            if (run_to != from) { NCHK(flush()); run_from = from; }
+            run_to = to;
+            continue;
+        }
+        if (on_device && ready_event && !main_waits) { NCHK(hipStreamWaitEvent(n->stream, (hipEvent_t)ready_event, 0)); main_waits = true; }
+        NCHK(hipMemcpyAsync(u.d_taps + (size_t)from * rs, src + (size_t)from * rs, (size_t)(to - from) * rs, kind, n->stream));
+    }
+    NCHK(flush());
+    NCHK(hipEventRecord(u.ev_load, u.stream));
+    // preparation: one launch per segment engine on the engine's own stream, in order with its blocks
+    for (size_t k = 0; k < n->seg.size(); k++) {
+        Seg &s = n->seg[k];
+        const long cap = (long)s.L * s.N;
+        const long left = std::max(0L, std::min(n_taps - s.off, cap));
+        if (s.delay_steps > 0) NCHK(hipStreamWaitEvent(s.stream, u.ev_load, 0));
+        ECHK(bfhip_internal_engine_update_coeff_dev_async(s.eng, n->sets.coeff[filter][coeff], u.d_taps + (size_t)s.off * rs,
+                                                          (int)left, s.n_blocks[filter][coeff], u.h_bad + k));
+        if (s.delay_steps > 0) NCHK(hipEventRecord(s.ev_upd, s.stream));
+    }
+    NCHK(hipEventRecord(u.ev_main, n->stream));
+    return BFHIP_OK;
+}
+
+// the checks of an asynchronous rewrite, then upd_enqueue.  Host source: `taps` is the pinned staging
+// buffer or is copied into it.  eq: the taps are rendered from this curve (in mode eq_mode) into eq.lin.taps
+// on the loader stream first, and eq.ev is the ready event (the caller passes taps = eq.lin.taps, on_device).
+int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event,
+              const EqBands *eq = nullptr, int eq_mode = BFHIP_EQ_LINEAR) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!set_ok(n, filter, coeff) || !taps || n_taps < 1 || n_taps > n->taps())
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: bad argument");
+    NupcUpdate &u = n->upd;
+    if (!n->finalized || !u.reserve)
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: needs bfhip_nupc_reserve_update before finalize, and finalize");
+    if (n->sets.sched.set_in_use(filter, coeff))
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: the set is live or part of a queued / in-flight switch");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (u.inflight) return nfail(BFHIP_ESTATE, "nupc_update_coeff_async: a rewrite is in flight (bfhip_nupc_update_busy)");
+    if (past_set(n, filter, coeff, taps, on_device, n_taps))
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: set 0 of this filter is shorter than these taps (add_filter's length)");
+    if (!on_device && taps != (const void *)u.h_taps) memcpy(u.h_taps, taps, (size_t)n_taps * n->rs);
+    NCHK(hipSetDevice(n->device));
+    if (eq) {
+        // a failure here has touched eq.lin.taps only: the set is as it was
+        NCHK(eq_launch(n, *eq, n_taps, eq_mode));
+        NCHK(hipEventRecord(n->eq.ev, u.stream));
+        ready_event = n->eq.ev;
+    }
+    // from here on work may be enqueued: a failure leaves the set's contents unknown
+    u.inflight = true;
+    u.filter = filter; u.set = coeff;
+    u.bad[filter][coeff] = 1;
+    u.failed = false;
+    const int r = upd_enqueue(n, filter, coeff, taps, on_device, n_taps, ready_event);
+    if (r < 0) u.failed = true;
+    return r;
+}
+
+// state and curve checks shared by the render calls; fills the kernel-argument copy of the bands
+int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+             const double phase[], int mode, EqBands *b) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->eq.reserve)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq: needs bfhip_nupc_reserve_eq before finalize, and finalize");
+    if (mode != BFHIP_EQ_LINEAR && mode != BFHIP_EQ_MINIMUM)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: mode must be BFHIP_EQ_LINEAR or BFHIP_EQ_MINIMUM");
+    if (mode == BFHIP_EQ_MINIMUM && !n->eq.min.reserved)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq: minimum phase needs bfhip_nupc_reserve_eq_minimum before finalize");
+    if (taps < 8 || (taps & (taps - 1)) || taps > n->eq.reserve)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: taps must be a power of two, 8 .. max_taps");
+    if (!freq || !mag || !phase || n_bands < 2 || n_bands > kEqMaxBands)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: 2 .. 130 bands");
+    if (freq[0] != 0.0 || freq[n_bands - 1] != 0.5)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq: the first band must be at 0 and the last at 0.5");
+    for (int i = 0; i < n_bands; i++) {
+        if (i > 0 && !(freq[i] > freq[i - 1])) return nfail(BFHIP_EINVAL, "nupc_render_eq: band frequencies must ascend");
+        if (!std::isfinite(mag[i]) || mag[i] < 0.0 || !std::isfinite(phase[i]))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq: magnitudes must be finite and >= 0, phases finite");
+        if (mode == BFHIP_EQ_MINIMUM && !(mag[i] > 0.0))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq: minimum phase needs every magnitude > 0");
+        b->freq[i] = freq[i]; b->mag[i] = mag[i]; b->phase[i] = phase[i];
+    }
+    b->n = n_bands;
+    return BFHIP_OK;
+}
+
+}  // namespace
+
+// finalize's step: everything the asynchronous rewrite and the renders touch, so that they allocate nothing
+// on the audio path
+int nupc_host::upd_finalize(bfhip_nupc *n, int prio_least) {
+    NupcUpdate &u = n->upd;
+    if (u.reserve) {
+        const size_t bytes = (size_t)n->taps() * n->rs;
+        NCHK(bfhip_internal_pin_alloc((void **)&u.h_taps, bytes, hipHostMallocDefault));
+        memset(u.h_taps, 0, bytes);
+        NCHK(bfhip_internal_dev_alloc((void **)&u.d_taps, bytes));
+        NCHK(hipMemset(u.d_taps, 0, bytes));
+        NCHK(bfhip_internal_pin_alloc((void **)&u.h_bad, n->seg.size() * sizeof(int), hipHostMallocDefault));
+        memset(u.h_bad, 0, n->seg.size() * sizeof(int));
+        NCHK(hipStreamCreateWithPriority(&u.stream, hipStreamNonBlocking, prio_least));
+        NCHK(hipEventCreateWithFlags(&u.ev_load, hipEventDisableTiming));
+        NCHK(hipEventCreateWithFlags(&u.ev_main, hipEventDisableTiming));
+        for (auto &s : n->seg) {
+            if (s.delay_steps > 0) NCHK(hipEventCreateWithFlags(&s.ev_upd, hipEventDisableTiming));
+            ECHK(bfhip_internal_engine_reserve_update(s.eng));
+        }
+        u.bad.resize(n->sets.coeff.size());
+        for (size_t f = 0; f < n->sets.coeff.size(); f++) u.bad[f].assign(n->sets.coeff[f].size(), 0);
+    }
+    if (n->eq.reserve) {
+        NCHK(eq_render_alloc(n->eq.lin, n->rs, n->eq.reserve));
+        if (n->eq.min.reserved) NCHK(eq_minphase_alloc(n->eq.min, n->eq.lin));
+        NCHK(hipEventCreateWithFlags(&n->eq.ev, hipEventDisableTiming));
+    }
+    return BFHIP_OK;
+}
+
+// destroy's step (the streams have been waited for)
+void nupc_host::upd_release(bfhip_nupc *n) {
+    NupcUpdate &u = n->upd;
+    if (u.h_taps) (void)hipHostFree(u.h_taps);
+    if (u.h_bad) (void)hipHostFree(u.h_bad);
+    if (u.d_taps) (void)hipFree(u.d_taps);
+    eq_render_free(n->eq.lin);
+    eq_minphase_free(n->eq.min);
+    if (n->eq.ev) (void)hipEventDestroy(n->eq.ev);
+    if (u.ev_load) (void)hipEventDestroy(u.ev_load);
+    if (u.ev_main) (void)hipEventDestroy(u.ev_main);
+    if (u.stream) (void)hipStreamDestroy(u.stream);
+}
+
+// has every piece of the rewrite in flight completed?  hipEventQuery only: never blocks.  On
+// completion the segment engines' non-finite flags (pinned, written behind each preparation)
+// become the rewrite's result.
+int nupc_host::upd_poll(bfhip_nupc *n) {
+    NupcUpdate &u = n->upd;
+    if (!u.inflight) return BFHIP_OK;
+    NCHK(hipSetDevice(n->device));
+    for (size_t k = 0; k < n->seg.size() + 2; k++) {
+        const hipEvent_t ev = k == 0 ? u.ev_load : k == 1 ? u.ev_main : n->seg[k - 2].ev_upd;
+        if (!ev) continue;                                        // a main-stream segment: ev_main covers it
+        const hipError_t e = hipEventQuery(ev);
+        if (e == hipErrorNotReady) { (void)hipGetLastError(); return BFHIP_OK; }
+        if (e != hipSuccess) return nfail(BFHIP_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
+    }
+    int bad = 0;
+    for (size_t k = 0; k < n->seg.size(); k++) bad |= ((volatile int *)u.h_bad)[k];
+    u.result = bad ? BFHIP_EINVAL : u.failed ? BFHIP_EHIP : BFHIP_OK;
+    u.bad[u.filter][u.set] = bad || u.failed ? 1 : 0;
+    u.inflight = false;
+    return BFHIP_OK;
+}
+
+extern "C" {
+
+// rewrite every partition of an idle set in every segment engine
+int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!set_ok(n, filter, coeff) || !taps || n_taps < 1 || n_taps > n->taps())
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff: bad argument");
+    if (n->sets.sched.set_in_use(filter, coeff))
+        return nfail(BFHIP_ESTATE, "nupc_update_coeff: the set is live or part of a queued / in-flight switch");
+    OWNER(n);
+    if (n->upd.reserve && n->finalized) {
+        { const int r = upd_poll(n); if (r < 0) return r; }
+        if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_update_coeff: an asynchronous rewrite is in flight (bfhip_nupc_update_busy)");
+    }
+    if (past_set(n, filter, coeff, taps, false, n_taps))
+        return nfail(BFHIP_EINVAL, "nupc_update_coeff: set 0 of this filter is shorter than these taps (add_filter's length)");
+    NCHK(hipSetDevice(n->device));
+    const unsigned char *t = (const unsigned char *)taps;
+    for (Seg &s : n->seg) {
+        std::vector<unsigned char> part((size_t)s.L * n->rs);
+        for (int p = 0; p < s.n_blocks[filter][coeff]; p++) {
+            const long first = s.off + (long)p * s.L;
+            const long take = std::max(0L, std::min((long)s.L, n_taps - first));
+            std::fill(part.begin(), part.end(), 0);
+            if (take > 0) memcpy(part.data(), t + (size_t)first * n->rs, (size_t)take * n->rs);
+            ECHK(bfhip_engine_update_coeff_block(s.eng, n->sets.coeff[filter][coeff], p, part.data()));
+        }
+    }
+    if (n->upd.reserve && n->finalized) n->upd.bad[filter][coeff] = 0;
+    return BFHIP_OK;
+}
+
+// ---- asynchronous set rewrite ----------------------------------------------------------------
+
+int bfhip_nupc_reserve_update(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_update after finalize");
+    n->upd.reserve = true;
+    return BFHIP_OK;
+}
+
+void *bfhip_nupc_update_buffer(bfhip_nupc *n) { return n && n->finalized ? n->upd.h_taps : nullptr; }
+
+int bfhip_nupc_update_coeff_async(bfhip_nupc *n, int filter, int coeff, const void *taps, long n_taps) {
+    return upd_start(n, filter, coeff, taps, false, n_taps, nullptr);
+}
+
+int bfhip_nupc_update_coeff_dev_async(bfhip_nupc *n, int filter, int coeff, const void *taps_dev, long n_taps,
+                                      void *ready_event) {
+    return upd_start(n, filter, coeff, taps_dev, true, n_taps, ready_event);
+}
+
+int bfhip_nupc_update_busy(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd.reserve) return 0;
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    return n->upd.inflight ? 1 : 0;
+}
+
+int bfhip_nupc_update_result(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd.reserve) return nfail(BFHIP_ESTATE, "nupc_update_result: no reservation (bfhip_nupc_reserve_update)");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_update_result: the rewrite is still in flight (bfhip_nupc_update_busy)");
+    if (n->upd.result == BFHIP_EHIP) return nfail(BFHIP_EHIP, "nupc_update_result: the rewrite could not be enqueued completely");
+    if (n->upd.result != BFHIP_OK) return nfail(n->upd.result, "NaN or Inf value among coefficients.");
+    return BFHIP_OK;
+}
+
+// blocks: not for the audio thread
+int bfhip_nupc_update_wait(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd.reserve) return nfail(BFHIP_ESTATE, "nupc_update_wait: no reservation (bfhip_nupc_reserve_update)");
+    OWNER(n);
+    if (n->upd.inflight) {
+        NCHK(hipSetDevice(n->device));
+        NCHK(hipEventSynchronize(n->upd.ev_load));
+        NCHK(hipEventSynchronize(n->upd.ev_main));
+        for (auto &s : n->seg) if (s.ev_upd) NCHK(hipEventSynchronize(s.ev_upd));
+    }
+    return bfhip_nupc_update_result(n);
+}
+
+// ---- equaliser curves rendered on the device -------------------------------------------------
+
+int bfhip_nupc_reserve_eq(bfhip_nupc *n, long max_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq after finalize");
+    if (!n->upd.reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq: needs bfhip_nupc_reserve_update first");
+    if (max_taps < 8 || (max_taps & (max_taps - 1)) || max_taps > std::min(n->taps(), 1L << (kEqMaxLog2H + 1)))
+        return nfail(BFHIP_EINVAL, "nupc_reserve_eq: max_taps must be a power of two, 8 .. min(taps, 1048576)");
+    n->eq.reserve = max_taps;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_reserve_eq_minimum(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_minimum after finalize");
+    if (!n->eq.reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_minimum: needs bfhip_nupc_reserve_eq first");
+    n->eq.min.reserved = true;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq_mode_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
+                                    const double mag[], const double phase[], int mode) {
+    EqBands b;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.lin.taps, true, taps, nullptr, &b, mode);
+}
+
+int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
+                               const double mag[], const double phase[]) {
+    return bfhip_nupc_render_eq_mode_async(n, filter, coeff, taps, n_bands, freq, mag, phase, BFHIP_EQ_LINEAR);
+}
+
+int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                              const double phase[], int mode, void *taps_out) {
+    EqBands b;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
+    if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq: null buffer");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq: a rewrite is in flight (bfhip_nupc_update_busy)");
+    NCHK(hipSetDevice(n->device));
+    NCHK(eq_launch(n, b, taps, mode));
+    NCHK(hipMemcpyAsync(taps_out, n->eq.lin.taps, (size_t)taps * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
+    NCHK(hipStreamSynchronize(n->upd.stream));
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
+                         const double phase[], void *taps_out) {
+    return bfhip_nupc_render_eq_mode(n, taps, n_bands, freq, mag, phase, BFHIP_EQ_LINEAR, taps_out);
+}
+
+}  // extern "C"
