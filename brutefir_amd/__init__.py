@@ -239,6 +239,10 @@ def lib():
     L.bfhip_nupc_reserve_eq_minimum.argtypes = [vp]
     L.bfhip_nupc_render_eq_mode_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp, ci]
     L.bfhip_nupc_render_eq_mode.argtypes = [vp, C.c_long, ci, dp, dp, dp, ci, vp]
+    L.bfhip_nupc_reserve_eq_base.argtypes = [vp, ci]
+    L.bfhip_nupc_set_eq_base.argtypes = [vp, ci, vp, C.c_long]
+    L.bfhip_nupc_render_eq_base_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp, ci]
+    L.bfhip_nupc_render_eq_base.argtypes = [vp, ci, C.c_long, ci, dp, dp, dp, ci, vp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -811,6 +815,32 @@ class Nupc:
         assert len(freq) == len(mag) == len(phase)
         out = np.zeros(max(int(taps), 0), self.dt)
         self._chk(lib().bfhip_nupc_render_eq_mode(self.h, taps, len(freq), _darr(list(freq)), _darr(list(mag)),
+                                                  _darr(list(phase)), self._eq_mode(mode), _ptr(out)))
+        return out
+
+    # the render convolved onto a base impulse response (include/bfhip_nupc.h)
+    def reserve_eq_base(self, filt):
+        """before finalize, after reserve_eq: the filter gets a base of `taps` reals on the device, which
+        holds add_filter's taps at finalize"""
+        self._chk(lib().bfhip_nupc_reserve_eq_base(self.h, filt))
+
+    def set_eq_base(self, filt, taps):
+        """replace the filter's base (at most `taps` reals, zero-padded); blocks, not for the audio thread"""
+        taps = np.ascontiguousarray(taps, self.dt)
+        self._chk(lib().bfhip_nupc_set_eq_base(self.h, filt, _ptr(taps), len(taps)))
+
+    def render_eq_base_async(self, filt, coeff, eq_taps, freq, mag, phase, mode="linear"):
+        """render the curve into eq_taps reals (a power of two, at most 8192), convolve them onto the
+        filter's base, truncated at `taps`, and rewrite an idle set with the result; returns at once"""
+        assert len(freq) == len(mag) == len(phase)
+        self._chk(lib().bfhip_nupc_render_eq_base_async(self.h, filt, coeff, eq_taps, len(freq), _darr(list(freq)),
+                                                        _darr(list(mag)), _darr(list(phase)), self._eq_mode(mode)))
+
+    def render_eq_base(self, filt, eq_taps, freq, mag, phase, mode="linear"):
+        """the same computation alone, synchronous: a numpy array of `taps` reals"""
+        assert len(freq) == len(mag) == len(phase)
+        out = np.zeros(self.taps, self.dt)
+        self._chk(lib().bfhip_nupc_render_eq_base(self.h, filt, eq_taps, len(freq), _darr(list(freq)), _darr(list(mag)),
                                                   _darr(list(phase)), self._eq_mode(mode), _ptr(out)))
         return out
 

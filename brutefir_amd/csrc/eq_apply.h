@@ -1,0 +1,223 @@
+// eq_apply.h -- the rendered equaliser taps of eq_render.h / eq_minphase.h convolved onto a base
+// impulse response on the device (bfhip_nupc_render_eq_base*, include/bfhip_nupc.h): the idle set
+// receives base (*) eq instead of eq.  An extension: the reference cascades two filters instead.
+//
+// e[0 .. R) are the rendered taps, b[0 .. T) the base, and the result is the convolution truncated at T:
+//     y[t] = sum_{j = 0}^{min(t, R - 1)} e[j] b[t - j],   0 <= t < T
+// by FFT overlap-save with blocks of B reals, R <= B <= 8192, both powers of two.  Window j of
+// ceil(T / B) is the 2B reals b[(j - 1) B, (j + 1) B), zeros in front of tap 0 and behind T; its circular
+// convolution with e, zero-padded to 2B, is exact in its last B values, which are y[j B, (j + 1) B).
+//
+// Both real transforms are the packed complex ones K1 and K3 use (kernels.h: untangle / tangle) with
+// H = B points in LDS:
+//     eq_apply_spectrum_kernel   one workgroup, once per render: e -> E[0 .. H], scaled by 1 / (2B) (a
+//                                power of two: exact); E[0] and E[H] are real and share slot 0
+//     eq_apply_kernel            one workgroup per window: load -> lds_fft -> untangle, times E, tangle
+//                                -> lds_fft inverse -> the last B reals to y
+// No atomics and no scratch: y is a pure function of e, b, B and T.  LDS is the padded array alone,
+// 139 280 bytes at float64 and B = 8192.
+#pragma once
+#include <algorithm>
+
+#include "eq_render.h"
+
+namespace bfhip {
+
+constexpr int kEqApplyMaxLog2B = 13;                  // what one workgroup transforms in LDS at float64
+constexpr int kEqApplyLog2B = 11;                     // the block length where R leaves the choice open
+
+// B for R taps onto T: max(R, 2048), but no longer than the power of two that holds T in one window.
+// A short curve then does not mean hundreds of thousands of 8-point windows, a long schedule has
+// hundreds of workgroups to spread over the CUs, and a short schedule is one window.
+inline int eq_apply_log2b(long R, long T) { return std::max(eq_log2(R), std::min(kEqApplyLog2B, eq_log2(T))); }
+
+template <typename T, int LOG2H>
+__global__ __launch_bounds__(fft_threads<T>(LOG2H)) void
+eq_apply_spectrum_kernel(const c2<T> *__restrict__ e, int pairs /* R / 2 <= H / 2 */, const c2<T> *__restrict__ tw,
+                         c2<T> *__restrict__ E) {
+    constexpr int H = 1 << LOG2H, NT = fft_threads<T>(LOG2H);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsArr<T> s{reinterpret_cast<c2<T> *>(smem)};
+    const int tid = threadIdx.x;
+    TwRegs<T, LOG2H, NT> twr;
+    twr.prefetch(tw);
+    for (int n = tid; n < H; n += NT) s[n] = n < pairs ? e[n] : mk<T>((T)0, (T)0);
+    __syncthreads();
+    lds_fft<T, LOG2H, NT, false>(s, twr);
+    const T sc = (T)1 / (T)(2 * H);
+    for (int k = tid; k <= H / 2; k += NT) {
+        if (k == 0) {
+            const c2<T> z = s[0];
+            E[0] = mk<T>((z.x + z.y) * sc, (z.x - z.y) * sc);
+            continue;
+        }
+        c2<T> xk, xlk;
+        untangle(s[k], conj(s[H - k]), tw[k], xk, xlk);
+        E[k] = mk<T>(xk.x * sc, xk.y * sc);
+        if (k != H - k) E[H - k] = mk<T>(xlk.x * sc, xlk.y * sc);
+    }
+}
+
+// B reals b[from, from + B) as packed pairs into s[n0, n0 + B / 2): zeros outside [0, T), 16-byte loads
+// where the range is whole (from is a multiple of B >= 8 reals, so it is 16-byte aligned)
+template <typename T, int B, int NT>
+__device__ __forceinline__ void eq_apply_load(LdsArr<T> s, int n0, const T *__restrict__ b, long from, long Tn, int tid) {
+    if (from < 0 || from >= Tn) {
+        for (int n = tid; n < B / 2; n += NT) s[n0 + n] = mk<T>((T)0, (T)0);
+    } else if (from + B <= Tn) {
+        if constexpr (sizeof(T) == 8) {
+            const c2<T> *p = reinterpret_cast<const c2<T> *>(b + from);
+            for (int n = tid; n < B / 2; n += NT) s[n0 + n] = p[n];
+        } else {
+            const float4 *p = reinterpret_cast<const float4 *>(b + from);
+            for (int m = tid; m < B / 4; m += NT) {
+                const float4 v = p[m];
+                s[n0 + 2 * m] = mk<T>(v.x, v.y);
+                s[n0 + 2 * m + 1] = mk<T>(v.z, v.w);
+            }
+        }
+    } else {
+        for (int n = tid; n < B / 2; n += NT) {
+            const long i = from + 2 * n;
+            s[n0 + n] = mk<T>(i < Tn ? b[i] : (T)0, i + 1 < Tn ? b[i + 1] : (T)0);
+        }
+    }
+}
+
+template <typename T, int LOG2H>
+__global__ __launch_bounds__(fft_threads<T>(LOG2H)) void
+eq_apply_kernel(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw, T *__restrict__ y, long Tn) {
+    constexpr int H = 1 << LOG2H, B = H, NT = fft_threads<T>(LOG2H);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsArr<T> s{reinterpret_cast<c2<T> *>(smem)};
+    const int tid = threadIdx.x;
+    const long at = (long)blockIdx.x * B;                 // y[at, at + B) is this window's
+    TwRegs<T, LOG2H, NT> twr;
+    twr.prefetch(tw);
+    eq_apply_load<T, B, NT>(s, 0, b, at - B, Tn, tid);
+    eq_apply_load<T, B, NT>(s, H / 2, b, at, Tn, tid);
+    __syncthreads();
+    lds_fft<T, LOG2H, NT, false>(s, twr);
+    for (int k = tid; k <= H / 2; k += NT) {
+        if (k == 0) {                                     // X[0] and X[H] are real, and so are E's
+            const c2<T> z = s[0], e0 = E[0];
+            const T y0 = (z.x + z.y) * e0.x, yh = (z.x - z.y) * e0.y;
+            s[0] = mk<T>(y0 + yh, y0 - yh);
+            continue;
+        }
+        c2<T> xk, xlk, zk, zlk;
+        untangle(s[k], conj(s[H - k]), tw[k], xk, xlk);
+        const c2<T> pk = cmul(xk, E[k]);
+        const c2<T> pl = k == H - k ? pk : cmul(xlk, E[H - k]);
+        tangle(pk, conj(pl), tw[k], zk, zlk);
+        s[k] = zk;
+        if (k != H - k) s[H - k] = zlk;
+    }
+    __syncthreads();
+    lds_fft<T, LOG2H, NT, true>(s, twr);
+    // s[n] = (window[2n], window[2n + 1]): the last B reals are pairs H/2 .. H - 1
+    if (at + B <= Tn) {
+        if constexpr (sizeof(T) == 8) {
+            c2<T> *p = reinterpret_cast<c2<T> *>(y + at);
+            for (int n = tid; n < B / 2; n += NT) p[n] = s[H / 2 + n];
+        } else {
+            float4 *p = reinterpret_cast<float4 *>(y + at);
+            for (int m = tid; m < B / 4; m += NT) {
+                const c2<T> u = s[H / 2 + 2 * m], v = s[H / 2 + 2 * m + 1];
+                p[m] = make_float4(u.x, u.y, v.x, v.y);
+            }
+        }
+    } else {
+        for (int n = tid; n < B / 2; n += NT) {
+            const long i = at + 2 * n;
+            const c2<T> v = s[H / 2 + n];
+            if (i < Tn) y[i] = v.x;
+            if (i + 1 < Tn) y[i + 1] = v.y;
+        }
+    }
+}
+
+// ---- host
+
+// what bfhip_nupc_reserve_eq_base adds to an EqRender: a base per reserved filter, the result, the
+// curve's spectrum and the twiddle tables of the block lengths the render's own lengths do not cover
+struct EqApply {
+    bool reserved = false;
+    long T = 0;
+    std::vector<void *> base;                  // [filter]: T reals, nullptr without a reservation
+    void *y = nullptr;                         // T reals: the device source of the rewrite
+    void *spec = nullptr;                      // B_max complex values
+    const void *tw[kEqApplyMaxLog2B + 1] = {}; // [log2 B]: the render's table, or one of `own`
+    void *own[kEqApplyMaxLog2B + 1] = {};
+};
+
+inline hipError_t eq_apply_alloc(EqApply &a, const EqRender &e, long T, const std::vector<char> &want) {
+    a.T = T;
+    hipError_t err;
+    const size_t bytes = (size_t)T * e.rs;
+    a.base.assign(want.size(), nullptr);
+    for (size_t f = 0; f < want.size(); f++) {
+        if (!want[f]) continue;
+        if ((err = bfhip_internal_dev_alloc(&a.base[f], bytes)) != hipSuccess) return err;
+        if ((err = hipMemset(a.base[f], 0, bytes)) != hipSuccess) return err;
+    }
+    if ((err = bfhip_internal_dev_alloc(&a.y, bytes)) != hipSuccess) return err;
+    if ((err = hipMemset(a.y, 0, bytes)) != hipSuccess) return err;
+    const int lo = eq_apply_log2b(8, T), hi = eq_apply_log2b(std::min(e.max_taps, 1L << kEqApplyMaxLog2B), T);
+    if ((err = bfhip_internal_dev_alloc(&a.spec, ((size_t)2 << hi) * e.rs)) != hipSuccess) return err;
+    for (int l = lo; l <= hi; l++) {
+        if (e.tw[l]) { a.tw[l] = e.tw[l]; continue; }
+        const std::vector<unsigned char> t = make_twiddle_table(l, e.rs, e.rs == 4 ? fft_threads<float>(l) : fft_threads<double>(l));
+        if ((err = bfhip_internal_dev_alloc(&a.own[l], t.size())) != hipSuccess) return err;
+        if ((err = hipMemcpy(a.own[l], t.data(), t.size(), hipMemcpyHostToDevice)) != hipSuccess) return err;
+        a.tw[l] = a.own[l];
+    }
+    return hipSuccess;
+}
+
+inline void eq_apply_free(EqApply &a) {
+    for (void *&p : a.base) if (p) { (void)hipFree(p); p = nullptr; }
+    for (void *&p : a.own) if (p) { (void)hipFree(p); p = nullptr; }
+    void **p[] = {&a.y, &a.spec};
+    for (void **q : p) if (*q) { (void)hipFree(*q); *q = nullptr; }
+}
+
+template <typename T, int LOG2H>
+inline hipError_t eq_apply_launch_lds(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+    auto spec = eq_apply_spectrum_kernel<T, LOG2H>;
+    auto kern = eq_apply_kernel<T, LOG2H>;
+    const size_t lds = lds_fft_bytes(LOG2H, sizeof(c2<T>));
+    hipError_t err;
+    if ((err = hipFuncSetAttribute(reinterpret_cast<const void *>(spec), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
+    if ((err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
+    const dim3 nt(fft_threads<T>(LOG2H));
+    const c2<T> *tw = (const c2<T> *)a.tw[LOG2H];
+    hipLaunchKernelGGL(spec, dim3(1), nt, lds, st, (const c2<T> *)e.taps, (int)(R / 2), tw, (c2<T> *)a.spec);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    const long B = 1L << LOG2H;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.T + B - 1) / B)), nt, lds, st, (const T *)base, (const c2<T> *)a.spec, tw,
+                       (T *)a.y, a.T);
+    return hipGetLastError();
+}
+
+// enqueue y = base (*) e.taps[0 .. R), truncated at T, into a.y (R: a power of two, 8 .. 8192, rendered
+// into e.taps on the same stream before)
+template <typename T>
+inline hipError_t eq_apply_launch(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+    switch (eq_apply_log2b(R, a.T)) {
+    case 3: return eq_apply_launch_lds<T, 3>(a, e, base, R, st);
+    case 4: return eq_apply_launch_lds<T, 4>(a, e, base, R, st);
+    case 5: return eq_apply_launch_lds<T, 5>(a, e, base, R, st);
+    case 6: return eq_apply_launch_lds<T, 6>(a, e, base, R, st);
+    case 7: return eq_apply_launch_lds<T, 7>(a, e, base, R, st);
+    case 8: return eq_apply_launch_lds<T, 8>(a, e, base, R, st);
+    case 9: return eq_apply_launch_lds<T, 9>(a, e, base, R, st);
+    case 10: return eq_apply_launch_lds<T, 10>(a, e, base, R, st);
+    case 11: return eq_apply_launch_lds<T, 11>(a, e, base, R, st);
+    case 12: return eq_apply_launch_lds<T, 12>(a, e, base, R, st);
+    case 13: return eq_apply_launch_lds<T, 13>(a, e, base, R, st);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace bfhip

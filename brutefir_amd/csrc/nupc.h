@@ -13,6 +13,7 @@
 
 #include "../../include/bfhip_nupc.h"
 #include "alloc.h"
+#include "eq_apply.h"
 #include "eq_minphase.h"
 #include "eq_render.h"
 #include "kernels.h"
@@ -136,6 +137,10 @@ struct NupcEq {
     long reserve = 0;                      // max_taps asked for before finalize, 0 = none
     EqRender lin;
     EqMinphase min;                        // bfhip_nupc_reserve_eq_minimum (eq_minphase.h)
+    // render onto a base (bfhip_nupc_reserve_eq_base, eq_apply.h): one more producer step behind the render
+    EqApply app;
+    std::vector<char> base_want;           // [filter]: reserved before finalize
+    std::vector<std::vector<unsigned char>> taps0;   // [filter]: add_filter's taps until finalize, the initial base
     hipEvent_t ev = nullptr;               // the render into lin.taps is done
 };
 

@@ -236,6 +236,9 @@ int bfhip_nupc_add_filter(bfhip_nupc *n, int in_ch, int out_ch, const void *taps
     n->sets.coeff.push_back({set0});
     n->sets.out_scale.push_back(out_scale);
     n->sets.sched.add_filter();
+    // kept until finalize: the base of a filter that bfhip_nupc_reserve_eq_base names later
+    const size_t keep = (size_t)std::min(n_taps, n->taps()) * n->rs;
+    n->eq.taps0.emplace_back((const unsigned char *)taps, (const unsigned char *)taps + keep);
     return BFHIP_OK;
 }
 

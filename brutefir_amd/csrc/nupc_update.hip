@@ -2,8 +2,8 @@
 // equaliser renders (include/bfhip_nupc.h; state in nupc.h).  None of this is on the audio path and none of
 // it launches a kernel of nupc_kernels.h: a rewrite uploads the taps and has every segment engine prepare
 // its slice on the engine's own stream, in order with the segment's blocks; a render (eq_render.h,
-// eq_minphase.h) is a producer in front of a rewrite, on the loader stream.  Which sets may be rewritten is
-// the switch schedule's answer (Switcher::set_in_use).
+// eq_minphase.h, and eq_apply.h where it goes onto a base) is a producer in front of a rewrite, on the loader
+// stream.  Which sets may be rewritten is the switch schedule's answer (Switcher::set_in_use).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -30,12 +30,27 @@ bool past_set(const bfhip_nupc *n, int filter, int coeff, const void *taps, bool
     return false;
 }
 
-hipError_t eq_launch(const bfhip_nupc *n, const EqBands &b, long taps, int mode) {
-    if (mode == BFHIP_EQ_MINIMUM)
-        return n->rs == 4 ? eq_minphase_launch<float>(n->eq.lin, n->eq.min, b, taps, n->upd.stream)
-                          : eq_minphase_launch<double>(n->eq.lin, n->eq.min, b, taps, n->upd.stream);
-    return n->rs == 4 ? eq_render_launch<float>(n->eq.lin, b, taps, n->upd.stream)
-                      : eq_render_launch<double>(n->eq.lin, b, taps, n->upd.stream);
+// a render on the loader stream: the curve in `mode` into eq.lin.taps[0 .. taps), and with base >= 0 that
+// filter's base convolved with them into eq.app.y (eq_apply.h)
+struct EqJob {
+    EqBands b;
+    long taps = 0;
+    int mode = BFHIP_EQ_LINEAR;
+    int base = -1;
+};
+
+hipError_t eq_launch(const bfhip_nupc *n, const EqJob &j) {
+    const hipStream_t st = n->upd.stream;
+    hipError_t err;
+    if (j.mode == BFHIP_EQ_MINIMUM)
+        err = n->rs == 4 ? eq_minphase_launch<float>(n->eq.lin, n->eq.min, j.b, j.taps, st)
+                         : eq_minphase_launch<double>(n->eq.lin, n->eq.min, j.b, j.taps, st);
+    else
+        err = n->rs == 4 ? eq_render_launch<float>(n->eq.lin, j.b, j.taps, st)
+                         : eq_render_launch<double>(n->eq.lin, j.b, j.taps, st);
+    if (err != hipSuccess || j.base < 0) return err;
+    return n->rs == 4 ? eq_apply_launch<float>(n->eq.app, n->eq.lin, n->eq.app.base[j.base], j.taps, st)
+                      : eq_apply_launch<double>(n->eq.app, n->eq.lin, n->eq.app.base[j.base], j.taps, st);
 }
 
 // enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
@@ -87,10 +102,10 @@ int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_
 }
 
 // the checks of an asynchronous rewrite, then upd_enqueue.  Host source: `taps` is the pinned staging
-// buffer or is copied into it.  eq: the taps are rendered from this curve (in mode eq_mode) into eq.lin.taps
-// on the loader stream first, and eq.ev is the ready event (the caller passes taps = eq.lin.taps, on_device).
+// buffer or is copied into it.  eq: the taps are produced by this render on the loader stream first, and
+// eq.ev is the ready event (the caller passes taps = eq.lin.taps or eq.app.y, on_device).
 int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event,
-              const EqBands *eq = nullptr, int eq_mode = BFHIP_EQ_LINEAR) {
+              const EqJob *eq = nullptr) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (!set_ok(n, filter, coeff) || !taps || n_taps < 1 || n_taps > n->taps())
         return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: bad argument");
@@ -107,8 +122,8 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
     if (!on_device && taps != (const void *)u.h_taps) memcpy(u.h_taps, taps, (size_t)n_taps * n->rs);
     NCHK(hipSetDevice(n->device));
     if (eq) {
-        // a failure here has touched eq.lin.taps only: the set is as it was
-        NCHK(eq_launch(n, *eq, n_taps, eq_mode));
+        // a failure here has touched eq.lin.taps and eq.app.y only: the set is as it was
+        NCHK(eq_launch(n, *eq));
         NCHK(hipEventRecord(n->eq.ev, u.stream));
         ready_event = n->eq.ev;
     }
@@ -124,7 +139,8 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
 
 // state and curve checks shared by the render calls; fills the kernel-argument copy of the bands
 int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
-             const double phase[], int mode, EqBands *b) {
+             const double phase[], int mode, EqJob *j, int base = -1) {
+    EqBands *b = &j->b;
     if (!n) return nfail(BFHIP_EINVAL, "null");
     if (!n->finalized || !n->eq.reserve)
         return nfail(BFHIP_ESTATE, "nupc_render_eq: needs bfhip_nupc_reserve_eq before finalize, and finalize");
@@ -132,6 +148,13 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
         return nfail(BFHIP_EINVAL, "nupc_render_eq: mode must be BFHIP_EQ_LINEAR or BFHIP_EQ_MINIMUM");
     if (mode == BFHIP_EQ_MINIMUM && !n->eq.min.reserved)
         return nfail(BFHIP_ESTATE, "nupc_render_eq: minimum phase needs bfhip_nupc_reserve_eq_minimum before finalize");
+    if (base >= 0) {
+        if (base >= (int)n->eq.app.base.size() || !n->eq.app.base[base])
+            return nfail(base >= (int)n->sets.coeff.size() ? BFHIP_EINVAL : BFHIP_ESTATE,
+                         "nupc_render_eq_base: needs bfhip_nupc_reserve_eq_base for this filter before finalize");
+        if (taps < 8 || (taps & (taps - 1)) || taps > std::min(n->eq.reserve, 1L << kEqApplyMaxLog2B))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. min(max_taps, 8192)");
+    }
     if (taps < 8 || (taps & (taps - 1)) || taps > n->eq.reserve)
         return nfail(BFHIP_EINVAL, "nupc_render_eq: taps must be a power of two, 8 .. max_taps");
     if (!freq || !mag || !phase || n_bands < 2 || n_bands > kEqMaxBands)
@@ -147,6 +170,7 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
         b->freq[i] = freq[i]; b->mag[i] = mag[i]; b->phase[i] = phase[i];
     }
     b->n = n_bands;
+    j->taps = taps; j->mode = mode; j->base = base;
     return BFHIP_OK;
 }
 
@@ -179,6 +203,14 @@ int nupc_host::upd_finalize(bfhip_nupc *n, int prio_least) {
         if (n->eq.min.reserved) NCHK(eq_minphase_alloc(n->eq.min, n->eq.lin));
         NCHK(hipEventCreateWithFlags(&n->eq.ev, hipEventDisableTiming));
     }
+    // behind everything else, so that a convolver without this reservation allocates what it did, in order
+    if (n->eq.app.reserved) {
+        n->eq.base_want.resize(n->sets.coeff.size(), 0);
+        NCHK(eq_apply_alloc(n->eq.app, n->eq.lin, n->taps(), n->eq.base_want));
+        for (size_t f = 0; f < n->eq.base_want.size(); f++)
+            if (n->eq.base_want[f]) NCHK(hipMemcpy(n->eq.app.base[f], n->eq.taps0[f].data(), n->eq.taps0[f].size(), hipMemcpyHostToDevice));
+    }
+    std::vector<std::vector<unsigned char>>().swap(n->eq.taps0);
     return BFHIP_OK;
 }
 
@@ -190,6 +222,7 @@ void nupc_host::upd_release(bfhip_nupc *n) {
     if (u.d_taps) (void)hipFree(u.d_taps);
     eq_render_free(n->eq.lin);
     eq_minphase_free(n->eq.min);
+    eq_apply_free(n->eq.app);
     if (n->eq.ev) (void)hipEventDestroy(n->eq.ev);
     if (u.ev_load) (void)hipEventDestroy(u.ev_load);
     if (u.ev_main) (void)hipEventDestroy(u.ev_main);
@@ -325,9 +358,9 @@ int bfhip_nupc_reserve_eq_minimum(bfhip_nupc *n) {
 
 int bfhip_nupc_render_eq_mode_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
                                     const double mag[], const double phase[], int mode) {
-    EqBands b;
-    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
-    return upd_start(n, filter, coeff, n->eq.lin.taps, true, taps, nullptr, &b, mode);
+    EqJob j;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &j); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.lin.taps, true, taps, nullptr, &j);
 }
 
 int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_bands, const double freq[],
@@ -337,14 +370,14 @@ int bfhip_nupc_render_eq_async(bfhip_nupc *n, int filter, int coeff, long taps, 
 
 int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
                               const double phase[], int mode, void *taps_out) {
-    EqBands b;
-    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &b); if (r < 0) return r; }
+    EqJob j;
+    { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &j); if (r < 0) return r; }
     if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq: null buffer");
     OWNER(n);
     { const int r = upd_poll(n); if (r < 0) return r; }
     if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq: a rewrite is in flight (bfhip_nupc_update_busy)");
     NCHK(hipSetDevice(n->device));
-    NCHK(eq_launch(n, b, taps, mode));
+    NCHK(eq_launch(n, j));
     NCHK(hipMemcpyAsync(taps_out, n->eq.lin.taps, (size_t)taps * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
     NCHK(hipStreamSynchronize(n->upd.stream));
     return BFHIP_OK;
@@ -353,6 +386,66 @@ int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const doubl
 int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
                          const double phase[], void *taps_out) {
     return bfhip_nupc_render_eq_mode(n, taps, n_bands, freq, mag, phase, BFHIP_EQ_LINEAR, taps_out);
+}
+
+// ---- render onto a base impulse response (eq_apply.h) ----------------------------------------
+
+int bfhip_nupc_reserve_eq_base(bfhip_nupc *n, int filter) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_base after finalize");
+    if (!n->eq.reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_base: needs bfhip_nupc_reserve_eq first");
+    if (filter < 0 || filter >= (int)n->sets.coeff.size()) return nfail(BFHIP_EINVAL, "nupc_reserve_eq_base: no such filter");
+    n->eq.base_want.resize(n->sets.coeff.size(), 0);
+    n->eq.base_want[filter] = 1;
+    n->eq.app.reserved = true;
+    return BFHIP_OK;
+}
+
+// blocks: not for the audio thread
+int bfhip_nupc_set_eq_base(bfhip_nupc *n, int filter, const void *taps, long n_taps) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_eq_base before finalize");
+    if (filter < 0 || filter >= (int)n->sets.coeff.size() || !taps || n_taps < 1 || n_taps > n->taps())
+        return nfail(BFHIP_EINVAL, "nupc_set_eq_base: bad argument");
+    if (filter >= (int)n->eq.app.base.size() || !n->eq.app.base[filter])
+        return nfail(BFHIP_ESTATE, "nupc_set_eq_base: needs bfhip_nupc_reserve_eq_base for this filter before finalize");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_set_eq_base: a rewrite is in flight (bfhip_nupc_update_busy)");
+    for (long i = 0; i < n_taps; i++)
+        if (!std::isfinite(n->rs == 4 ? (double)((const float *)taps)[i] : ((const double *)taps)[i]))
+            return nfail(BFHIP_EINVAL, "NaN or Inf value among coefficients.");
+    NCHK(hipSetDevice(n->device));
+    uint8_t *b = (uint8_t *)n->eq.app.base[filter];
+    const size_t bytes = (size_t)n_taps * n->rs, all = (size_t)n->taps() * n->rs;
+    NCHK(hipMemcpyAsync(b, taps, bytes, hipMemcpyHostToDevice, n->upd.stream));
+    if (all > bytes) NCHK(hipMemsetAsync(b + bytes, 0, all - bytes, n->upd.stream));
+    NCHK(hipStreamSynchronize(n->upd.stream));
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq_base_async(bfhip_nupc *n, int filter, int coeff, long eq_taps, int n_bands, const double freq[],
+                                    const double mag[], const double phase[], int mode) {
+    if (n && filter < 0) return nfail(BFHIP_EINVAL, "nupc_render_eq_base: no such filter");
+    EqJob j;
+    { const int r = eq_check(n, eq_taps, n_bands, freq, mag, phase, mode, &j, filter); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.app.y, true, n->taps(), nullptr, &j);
+}
+
+int bfhip_nupc_render_eq_base(bfhip_nupc *n, int filter, long eq_taps, int n_bands, const double freq[], const double mag[],
+                              const double phase[], int mode, void *taps_out) {
+    if (n && filter < 0) return nfail(BFHIP_EINVAL, "nupc_render_eq_base: no such filter");
+    EqJob j;
+    { const int r = eq_check(n, eq_taps, n_bands, freq, mag, phase, mode, &j, filter); if (r < 0) return r; }
+    if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq_base: null buffer");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq_base: a rewrite is in flight (bfhip_nupc_update_busy)");
+    NCHK(hipSetDevice(n->device));
+    NCHK(eq_launch(n, j));
+    NCHK(hipMemcpyAsync(taps_out, n->eq.app.y, (size_t)n->taps() * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
+    NCHK(hipStreamSynchronize(n->upd.stream));
+    return BFHIP_OK;
 }
 
 }  // extern "C"

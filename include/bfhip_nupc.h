@@ -319,6 +319,59 @@ int bfhip_nupc_render_eq_mode_async(bfhip_nupc *n, int filter, int coeff, long t
                                     const double freq[], const double mag[], const double phase[], int mode);
 int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const double freq[],
                               const double mag[], const double phase[], int mode, void *taps_out);
+/* ---- render onto a base impulse response (an extension: the reference cascades an equaliser
+ * filter into the main one with to_filters / from_filters; this convolver has no cascades) --------
+ * The renders above REPLACE a set with the curve's taps.  With a base the idle set receives
+ * base (*) eq: a room-correction response keeps its correction under a tone control, with no host
+ * convolution and no upload.
+ *
+ * Base.  A filter with a reservation owns a base of T = bfhip_nupc_taps() reals on the device.  At
+ * finalize it holds bfhip_nupc_add_filter's taps, zero-padded (the scales are not part of it: the
+ * filter applies them as always); bfhip_nupc_set_eq_base replaces it.  The base belongs to the
+ * filter, not to a set.
+ *
+ * Result.  e[0 .. R), R = eq_taps, are the taps bfhip_nupc_render_eq_mode returns for the same
+ * curve and mode, in the convolver's real type, b is the base, and
+ *     y[t] = sum_{j = 0}^{min(t, R - 1)} e[j] b[t - j],   0 <= t < T
+ * The convolution is TRUNCATED at T: a base with at least R trailing zeros loses nothing, a longer
+ * one loses the tail that would reach past the schedule.  BFHIP_EQ_LINEAR adds R/2 frames of delay,
+ * as the plain render does.  y is computed in the convolver's real type by FFT overlap-save
+ * (eq_apply.h; block length in DESIGN.md section 4) and is a pure function of curve, mode, R and
+ * base: the same arguments give the same bytes.  The synchronous call returns exactly the array the
+ * asynchronous call writes into the set: a set written by bfhip_nupc_render_eq_base_async has the
+ * bits of bfhip_nupc_update_coeff_async with the synchronous call's array.
+ *
+ * eq_taps: a power of two, 8 <= eq_taps <= min(max_taps, 8192).  8192 is what one workgroup
+ * transforms in LDS at float64; longer curves (through the big FFT) are a later step.
+ * Everything is allocated at finalize and only under a reservation: T reals per reserved filter, one
+ * result of T reals, one spectrum, and the twiddle tables the renders do not already have.  A
+ * convolver that never calls bfhip_nupc_reserve_eq_base allocates, launches and computes exactly as
+ * before.
+ */
+/* before finalize, after bfhip_nupc_reserve_eq (BFHIP_ESTATE otherwise / after finalize); filter in
+   range (BFHIP_EINVAL) */
+int bfhip_nupc_reserve_eq_base(bfhip_nupc *n, int filter);
+/* after finalize; synchronous, for set-up and offline use, NOT for the audio thread.  taps: realsize
+   wide, 1 <= n_taps <= T, shorter input is zero-padded (BFHIP_EINVAL otherwise).  A non-finite tap:
+   BFHIP_EINVAL with the reference's "NaN or Inf value among coefficients.", and the base stays as it
+   was.  BFHIP_ESTATE before finalize, without the filter's reservation, and while
+   bfhip_nupc_update_busy is 1. */
+int bfhip_nupc_set_eq_base(bfhip_nupc *n, int filter, const void *taps, long n_taps);
+/* render the curve, convolve it onto the filter's base and rewrite set `coeff` of `filter` with the T
+   reals.  Curve and mode rules are those of bfhip_nupc_render_eq_mode_async (BFHIP_EQ_MINIMUM needs
+   bfhip_nupc_reserve_eq_minimum).  y spans the whole schedule, so the set-length rule of
+   bfhip_nupc_update_coeff_dev_async applies with n_taps = T: coeff == 0 is accepted only where set 0
+   covers every partition (BFHIP_EINVAL otherwise); the usual flow alternates between two sets made
+   with bfhip_nupc_add_coeff.  State rules, busy / result / wait calls, "one rewrite in flight" and
+   "no host wait, no allocation, no blocking copy, bands copied at the call" are those of
+   bfhip_nupc_render_eq_mode_async; a failed argument or state check changes nothing.  BFHIP_ESTATE
+   without the filter's reservation. */
+int bfhip_nupc_render_eq_base_async(bfhip_nupc *n, int filter, int coeff, long eq_taps, int n_bands,
+                                    const double freq[], const double mag[], const double phase[], int mode);
+/* the same computation alone, synchronous: bfhip_nupc_taps() reals (realsize wide) into host memory,
+   for tests and offline use.  BFHIP_ESTATE while a rewrite is in flight. */
+int bfhip_nupc_render_eq_base(bfhip_nupc *n, int filter, long eq_taps, int n_bands, const double freq[],
+                              const double mag[], const double phase[], int mode, void *taps_out);
 /* per-output gain applied at the emit step, in force from the first frame of the next block call's
    output (a step, or the start of a ramp: bfhip_nupc_set_gain_ramp below); 0.0 mutes; default 1.0
    (multiplied into the 1/scale factor in float64: exact) */

@@ -9,7 +9,8 @@ bfhip_nupc_block call (host buffers in and out) against the period at 48 kHz, ne
 uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
-                                  [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum]]
+                                  [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
+                                   | --eq-base [--eq-mode minimum] [--eq-taps R]]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -27,7 +28,11 @@ the idle set of each filter (bfhip_nupc_render_eq_async), then switched to; it a
 of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wait) of 8, of 16 384 and of
 1 048 576 taps, made before the timed loop: an upper bound of the render's device time.  --eq-mode minimum
 renders every curve with minimum phase (BFHIP_EQ_MINIMUM: no taps / 2 frames of delay; three transforms
-instead of one).  --gain-ramp sets an
+instead of one).  --eq-taps sets the render length (default 1 048 576).  --eq-base is --eq with every curve
+rendered ONTO the filter's base impulse response (bfhip_nupc_render_eq_base_async: --eq-taps taps, default and
+at most 8192, convolved with the filter's own 1 048 576 taps on the device, all partitions rewritten); its
+synchronous renders are bfhip_nupc_render_eq_base at 8 and at --eq-taps taps (1 048 576 reals to the host
+each).  --eq --eq-taps 8192 is the plain render to hold it against.  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
@@ -61,6 +66,8 @@ def main():
     ap.add_argument("--rewrite-sync", action="store_true")
     ap.add_argument("--eq", action="store_true")
     ap.add_argument("--eq-mode", choices=["linear", "minimum"], default="linear")
+    ap.add_argument("--eq-base", action="store_true")
+    ap.add_argument("--eq-taps", type=int)
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
@@ -94,7 +101,10 @@ def main():
         for io in (bf.IN, bf.OUT):
             for c in range(2):
                 nu.set_subdelay(io, c, 37 - 62 * c)
-    assert a.rewrite + a.rewrite_sync + a.eq <= 1 and (a.eq or a.eq_mode == "linear")
+    assert a.rewrite + a.rewrite_sync + a.eq + a.eq_base <= 1
+    a.eq = a.eq or a.eq_base
+    assert a.eq or (a.eq_mode == "linear" and a.eq_taps is None)
+    eq_taps = a.eq_taps or (8192 if a.eq_base else 1048576)
     rewriting = a.rewrite or a.rewrite_sync or a.eq
     if a.rewrite or a.eq:
         nu.reserve_update()
@@ -109,6 +119,8 @@ def main():
             nu.add_filter(i, o, h)
             if rewriting:
                 nu.add_coeff(2 * o + i, h[:nu.taps] * 0.5)
+            if a.eq_base:
+                nu.reserve_eq_base(2 * o + i)
     nu.finalize()
     # two impulse responses to render alternately into the idle set (a render costs what it costs
     # the caller: here one numpy copy into the staging buffer, or nothing for the synchronous call)
@@ -123,10 +135,14 @@ def main():
         # a synchronous render of 8 taps is the call, the wait and a copy of 64 bytes; one of 1 048 576
         # taps adds the long render and 8 MB of copy to pageable memory
         c = curve()
-        for n_taps in (8, 16384, 1048576):
+        sync_taps = (8, eq_taps) if a.eq_base else (8, 16384, 1048576)
+        for n_taps in sync_taps:
             for _ in range(5):
                 t0 = time.perf_counter()
-                nu.render_eq(n_taps, *c, mode=a.eq_mode)
+                if a.eq_base:
+                    nu.render_eq_base(0, n_taps, *c, mode=a.eq_mode)
+                else:
+                    nu.render_eq(n_taps, *c, mode=a.eq_mode)
                 render_ms.append((n_taps, (time.perf_counter() - t0) * 1e3))
     live_set, todo, round_no, due = 0, [], 0, False
     call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
@@ -179,7 +195,10 @@ def main():
                 if a.eq:
                     c = curve()
                     t0 = time.perf_counter()
-                    nu.render_eq_async(f, 1 - live_set, 1048576, *c, mode=a.eq_mode)
+                    if a.eq_base:
+                        nu.render_eq_base_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
+                    else:
+                        nu.render_eq_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
                     call_ms.append((time.perf_counter() - t0) * 1e3)
                     started_at = s
                 elif a.rewrite:
@@ -220,7 +239,7 @@ def main():
         if len(v) == 0:
             return None
         return {"n": int(len(v)), "median": round(float(np.median(v)), 4), "p99": round(float(np.percentile(v, 99)), 4),
-                "max": round(float(v.max()), 4)}
+                "p99.9": round(float(np.percentile(v, 99.9)), 4), "max": round(float(v.max()), 4)}
     # the periods in which every segment has a block to launch (the schedule's worst case), as
     # opposed to the rare host-side hiccups that land anywhere
     ratio = seg_len[-1] // L0
@@ -234,12 +253,12 @@ def main():
         "gain_ramp": {"ramp_frames": ramp_periods * L0, "outputs": [0, 1], "new_target_every_periods": 300,
                       "ramps": n_ramps, "step_ms_ramp_in_progress": dist(ts[rp]),
                       "step_ms_no_ramp": dist(ts[~rp])} if a.gain_ramp else None,
-        "rewrite": {"mode": ("eq" if a.eq_mode == "linear" else "eq-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
-                    "taps_per_set": int(nu.taps), "rounds": round_no,
+        "rewrite": {"mode": ("eq-base" if a.eq_base else "eq") + ("" if a.eq_mode == "linear" else "-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+                    "taps_per_set": int(nu.taps), "eq_taps": eq_taps if a.eq else None, "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
                     "periods_to_idle": dist(busy_periods),
                     "render_eq_sync_ms": {str(k): dist([v for n_taps, v in render_ms if n_taps == k][1:])
-                                          for k in (8, 16384, 1048576)} if a.eq else None,
+                                          for k in sync_taps} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),

@@ -3,11 +3,14 @@
 own report.
 
     python3 tools/nupc_resources.py [--parent OTHER_TREE] > profiles/nupc_refactor_resources.json
+    python3 tools/nupc_resources.py --eq-base > profiles/nupc_eq_base_resources.json
 
 Compiles brutefir_amd/csrc/nupc.hip, the unit that launches (and so instantiates) the nupc kernels, for
 gfx950 with -Rpass-analysis=kernel-resource-usage (device side only; no GPU needed) and reads the remarks of
 every kernel whose name starts with `nupc_`.  With --parent the same is done for another checkout and the two
-are put side by side; "same" says whether every figure of every kernel is equal."""
+are put side by side; "same" says whether every figure of every kernel is equal.  With --eq-base the unit is
+brutefir_amd/csrc/nupc_update.hip and the kernels are those of eq_apply.h (the render onto a base), whose names
+start with `eq_apply_`."""
 import json
 import os
 import re
@@ -21,9 +24,9 @@ COLUMNS = ["VGPRs", "AGPRs", "TotalSGPRs", "LDS Size [bytes/block]", "ScratchSiz
            "Occupancy [waves/SIMD]"]
 
 
-def kernels(tree):
+def kernels(tree, unit="nupc.hip", prefix="nupc_"):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = os.path.join(tree, "brutefir_amd", "csrc", "nupc.hip")
+    src = os.path.join(tree, "brutefir_amd", "csrc", unit)
     err = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc"] + FLAGS + [src, "-o", os.devnull],
                          capture_output=True, text=True, check=True).stderr
     raw, cur = {}, None
@@ -40,16 +43,17 @@ def kernels(tree):
     out = {}
     for n, d in zip(names, plain):
         d = re.sub(r"^void |\(anonymous namespace\)::|\w+::", "", d).split("(")[0]      # without namespaces and parameters
-        if d.startswith("nupc_"):
+        if d.startswith(prefix):
             out[d] = raw[n]
     return out
 
 
 def main(argv):
-    new = kernels(ROOT)
-    res = {"flags": "hipcc " + " ".join(FLAGS) + " brutefir_amd/csrc/nupc.hip", "columns": COLUMNS}
+    unit, prefix = ("nupc_update.hip", "eq_apply_") if "--eq-base" in argv else ("nupc.hip", "nupc_")
+    new = kernels(ROOT, unit, prefix)
+    res = {"flags": "hipcc " + " ".join(FLAGS) + " brutefir_amd/csrc/" + unit, "columns": COLUMNS}
     if "--parent" in argv:
-        par = kernels(argv[argv.index("--parent") + 1])
+        par = kernels(argv[argv.index("--parent") + 1], unit, prefix)
         res["kernels"] = [{"kernel": k, "parent": par.get(k), "new": new.get(k)} for k in sorted(set(par) | set(new))]
         res["same"] = par == new
     else:
