@@ -243,6 +243,7 @@ def lib():
     L.bfhip_nupc_set_eq_base.argtypes = [vp, ci, vp, C.c_long]
     L.bfhip_nupc_render_eq_base_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp, ci]
     L.bfhip_nupc_render_eq_base.argtypes = [vp, ci, C.c_long, ci, dp, dp, dp, ci, vp]
+    L.bfhip_nupc_reserve_eq_base_long.argtypes = [vp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -824,14 +825,19 @@ class Nupc:
         holds add_filter's taps at finalize"""
         self._chk(lib().bfhip_nupc_reserve_eq_base(self.h, filt))
 
+    def reserve_eq_base_long(self):
+        """before finalize, after reserve_eq: render_eq_base* then take eq_taps up to reserve_eq's max_taps
+        instead of min(max_taps, 8192); finalize allocates the big-FFT scratch of the long windows"""
+        self._chk(lib().bfhip_nupc_reserve_eq_base_long(self.h))
+
     def set_eq_base(self, filt, taps):
         """replace the filter's base (at most `taps` reals, zero-padded); blocks, not for the audio thread"""
         taps = np.ascontiguousarray(taps, self.dt)
         self._chk(lib().bfhip_nupc_set_eq_base(self.h, filt, _ptr(taps), len(taps)))
 
     def render_eq_base_async(self, filt, coeff, eq_taps, freq, mag, phase, mode="linear"):
-        """render the curve into eq_taps reals (a power of two, at most 8192), convolve them onto the
-        filter's base, truncated at `taps`, and rewrite an idle set with the result; returns at once"""
+        """render the curve into eq_taps reals (a power of two, at most 8192, or at most reserve_eq's
+        max_taps with reserve_eq_base_long), convolve them onto the filter's base, truncated at `taps`, and rewrite an idle set with the result; returns at once"""
         assert len(freq) == len(mag) == len(phase)
         self._chk(lib().bfhip_nupc_render_eq_base_async(self.h, filt, coeff, eq_taps, len(freq), _darr(list(freq)),
                                                         _darr(list(mag)), _darr(list(phase)), self._eq_mode(mode)))

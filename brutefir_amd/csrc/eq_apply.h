@@ -4,7 +4,8 @@
 //
 // e[0 .. R) are the rendered taps, b[0 .. T) the base, and the result is the convolution truncated at T:
 //     y[t] = sum_{j = 0}^{min(t, R - 1)} e[j] b[t - j],   0 <= t < T
-// by FFT overlap-save with blocks of B reals, R <= B <= 8192, both powers of two.  Window j of
+// by FFT overlap-save with blocks of B reals, R <= B <= 8192, both powers of two (B = R beyond 8192,
+// through bigfft.h: the second half of this file).  Window j of
 // ceil(T / B) is the 2B reals b[(j - 1) B, (j + 1) B), zeros in front of tap 0 and behind T; its circular
 // convolution with e, zero-padded to 2B, is exact in its last B values, which are y[j B, (j + 1) B).
 //
@@ -137,19 +138,95 @@ eq_apply_kernel(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T
     }
 }
 
+// ---- R > 8192 (bfhip_nupc_reserve_eq_base_long): B = R, and a window's H = B points do not fit a
+// workgroup's LDS.  The same overlap-save with the transforms of bigfft.h over global scratch, all n_win =
+// ceil(T / B) windows as one batch, and the curve as transform n_win of the forward batch:
+//     eq_apply_gather_kernel     z[w][n] = (b[(w - 1) B + 2n], b[(w - 1) B + 2n + 1]), zeros outside [0, T);
+//                                z[n_win][n] = (e[2n], e[2n + 1]), zeros from R / 2 on
+//     big_fft_run forward        n_win + 1 transforms of H points
+//     big_untangle               transform n_win -> E[0 .. H], scaled by 1 / (2B), E[0] and E[H] in slot 0
+//     eq_apply_product_kernel    (w, k <= H / 2): eq_apply_kernel's untangle, times E, tangle
+//     big_fft_run inverse        n_win transforms
+//     eq_apply_store_kernel      the last B reals of window w to y[w B, (w + 1) B), clipped at T
+// No atomics here either.  The three buffers that big_fft_run alternates between hold (n_win + 1) B complex
+// values each: T + max_taps where B divides T, below T + 2 max_taps otherwise.
+
+template <typename T>
+__global__ __launch_bounds__(256) void
+eq_apply_gather_kernel(const T *__restrict__ b, const c2<T> *__restrict__ e, int pairs /* R / 2 */, c2<T> *__restrict__ z,
+                       int log2b, int n_win, long Tn) {
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;  // < B: the grid is B / 256 wide
+    const int w = blockIdx.y;
+    c2<T> v;
+    if (w == n_win) {
+        v = n < pairs ? e[n] : mk<T>((T)0, (T)0);
+    } else {
+        const long i = ((long)(w - 1) << log2b) + 2 * n;   // even: in front of tap 0 both of a pair lie, or neither
+        if (i >= 0 && i + 1 < Tn) v = *reinterpret_cast<const c2<T> *>(b + i);
+        else v = mk<T>(i >= 0 && i < Tn ? b[i] : (T)0, (T)0);
+    }
+    z[((size_t)w << log2b) + n] = v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void
+eq_apply_product_kernel(const c2<T> *__restrict__ x, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw,
+                        c2<T> *__restrict__ z, int H) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k > H / 2) return;
+    const c2<T> *s = x + (size_t)blockIdx.y * H;
+    c2<T> *d = z + (size_t)blockIdx.y * H;
+    if (k == 0) {                                         // X[0] and X[H] are real, and so are E's
+        const c2<T> z0 = s[0], e0 = E[0];
+        const T y0 = (z0.x + z0.y) * e0.x, yh = (z0.x - z0.y) * e0.y;
+        d[0] = mk<T>(y0 + yh, y0 - yh);
+        return;
+    }
+    c2<T> xk, xlk, zk, zlk;
+    untangle(s[k], conj(s[H - k]), tw[k], xk, xlk);
+    const c2<T> pk = cmul(xk, E[k]);
+    const c2<T> pl = k == H - k ? pk : cmul(xlk, E[H - k]);
+    tangle(pk, conj(pl), tw[k], zk, zlk);
+    d[k] = zk;
+    if (k != H - k) d[H - k] = zlk;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void
+eq_apply_store_kernel(const c2<T> *__restrict__ z, T *__restrict__ y, int log2b, long Tn) {
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;  // < B / 2: the grid is B / 512 wide
+    const long B = 1L << log2b, at = (long)blockIdx.y << log2b;
+    // z[w][n] = (window[2n], window[2n + 1]): the last B reals are pairs B/2 .. B - 1
+    const c2<T> v = z[(size_t)at + B / 2 + n];
+    const long i = at + 2 * n;
+    if (i + 1 < Tn) *reinterpret_cast<c2<T> *>(y + i) = v;
+    else if (i < Tn) y[i] = v.x;
+}
+
 // ---- host
 
 // what bfhip_nupc_reserve_eq_base adds to an EqRender: a base per reserved filter, the result, the
-// curve's spectrum and the twiddle tables of the block lengths the render's own lengths do not cover
+// curve's spectrum and the twiddle tables of the block lengths the render's own lengths do not cover;
+// and what bfhip_nupc_reserve_eq_base_long adds to that where max_taps > 8192
 struct EqApply {
     bool reserved = false;
+    bool reserved_long = false;                // bfhip_nupc_reserve_eq_base_long
     long T = 0;
     std::vector<void *> base;                  // [filter]: T reals, nullptr without a reservation
     void *y = nullptr;                         // T reals: the device source of the rewrite
-    void *spec = nullptr;                      // B_max complex values
-    const void *tw[kEqApplyMaxLog2B + 1] = {}; // [log2 B]: the render's table, or one of `own`
-    void *own[kEqApplyMaxLog2B + 1] = {};
+    void *spec = nullptr;                      // B_max complex values, B_max <= 8192
+    const void *tw[kEqMaxLog2H + 2] = {};      // [log2 B]: the render's table, or one of `own`
+    void *own[kEqMaxLog2H + 2] = {};
+    void *big[3] = {};                         // R > 8192: (n_win + 1) B complex values each, the largest over B
+    void *big_spec = nullptr;                  // max_taps complex values
 };
+
+// R > 8192: the complex values each of the three buffers holds, the largest over the lengths B
+inline size_t eq_apply_big_elems(long T, long max_taps) {
+    size_t most = 0;
+    for (long B = 2L << kEqApplyMaxLog2B; B <= max_taps; B *= 2) most = std::max(most, (size_t)((T + B - 1) / B + 1) * (size_t)B);
+    return most;
+}
 
 inline hipError_t eq_apply_alloc(EqApply &a, const EqRender &e, long T, const std::vector<char> &want) {
     a.T = T;
@@ -172,13 +249,24 @@ inline hipError_t eq_apply_alloc(EqApply &a, const EqRender &e, long T, const st
         if ((err = hipMemcpy(a.own[l], t.data(), t.size(), hipMemcpyHostToDevice)) != hipSuccess) return err;
         a.tw[l] = a.own[l];
     }
-    return hipSuccess;
+    if (!a.reserved_long || e.max_taps <= (1L << kEqApplyMaxLog2B)) return hipSuccess;
+    // the tables of H = 16384 .. max_taps points: the render's own stop at max_taps / 2
+    for (int l = kEqApplyMaxLog2B + 1; l <= eq_log2(e.max_taps); l++) {
+        if (l <= kEqMaxLog2H && e.tw[l]) { a.tw[l] = e.tw[l]; continue; }   // e.tw stops at kEqMaxLog2H
+        const std::vector<unsigned char> t = make_twiddle_table(l, e.rs, 0);
+        if ((err = bfhip_internal_dev_alloc(&a.own[l], t.size())) != hipSuccess) return err;
+        if ((err = hipMemcpy(a.own[l], t.data(), t.size(), hipMemcpyHostToDevice)) != hipSuccess) return err;
+        a.tw[l] = a.own[l];
+    }
+    for (void *&p : a.big)
+        if ((err = bfhip_internal_dev_alloc(&p, eq_apply_big_elems(T, e.max_taps) * 2 * e.rs)) != hipSuccess) return err;
+    return bfhip_internal_dev_alloc(&a.big_spec, (size_t)e.max_taps * 2 * e.rs);
 }
 
 inline void eq_apply_free(EqApply &a) {
     for (void *&p : a.base) if (p) { (void)hipFree(p); p = nullptr; }
     for (void *&p : a.own) if (p) { (void)hipFree(p); p = nullptr; }
-    void **p[] = {&a.y, &a.spec};
+    void **p[] = {&a.y, &a.spec, &a.big[0], &a.big[1], &a.big[2], &a.big_spec};
     for (void **q : p) if (*q) { (void)hipFree(*q); *q = nullptr; }
 }
 
@@ -200,10 +288,36 @@ inline hipError_t eq_apply_launch_lds(const EqApply &a, const EqRender &e, const
     return hipGetLastError();
 }
 
-// enqueue y = base (*) e.taps[0 .. R), truncated at T, into a.y (R: a power of two, 8 .. 8192, rendered
-// into e.taps on the same stream before)
+// R > 8192: the windows through bigfft.h (needs what eq_apply_alloc adds under reserved_long)
+template <typename T>
+inline hipError_t eq_apply_launch_big(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+    const int l = eq_apply_log2b(R, a.T);
+    const long B = 1L << l;
+    const int H = (int)B, n_win = (int)((a.T + B - 1) / B);
+    if (!a.big[0] || !a.tw[l] || (size_t)(n_win + 1) * (size_t)B > eq_apply_big_elems(a.T, e.max_taps)) return hipErrorInvalidValue;
+    c2<T> *z0 = (c2<T> *)a.big[0], *z1 = (c2<T> *)a.big[1], *z2 = (c2<T> *)a.big[2], *E = (c2<T> *)a.big_spec;
+    const c2<T> *tw13 = (const c2<T> *)e.tw[BIG_LOG2M], *twL = (const c2<T> *)a.tw[l];
+    hipError_t err;
+    hipLaunchKernelGGL(eq_apply_gather_kernel<T>, dim3((unsigned)(B / 256), (unsigned)(n_win + 1)), dim3(256), 0, st,
+                       (const T *)base, (const c2<T> *)e.taps, (int)(R / 2), z0, l, n_win, a.T);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = big_fft_run<T, false>(z0, z1, z2, l, n_win + 1, tw13, twL, st)) != hipSuccess) return err;
+    hipLaunchKernelGGL(big_untangle<T>, dim3((unsigned)(H / 2 / 256 + 1), 1), dim3(256), 0, st, z2 + (size_t)n_win * B, E, (size_t)0,
+                       twL, H, (T)1 / (T)(2 * B));
+    hipLaunchKernelGGL(eq_apply_product_kernel<T>, dim3((unsigned)(H / 2 / 256 + 1), (unsigned)n_win), dim3(256), 0, st,
+                       (const c2<T> *)z2, (const c2<T> *)E, twL, z0, H);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    if ((err = big_fft_run<T, true>(z0, z1, z2, l, n_win, tw13, twL, st)) != hipSuccess) return err;
+    hipLaunchKernelGGL(eq_apply_store_kernel<T>, dim3((unsigned)(B / 512), (unsigned)n_win), dim3(256), 0, st, (const c2<T> *)z2,
+                       (T *)a.y, l, a.T);
+    return hipGetLastError();
+}
+
+// enqueue y = base (*) e.taps[0 .. R), truncated at T, into a.y (R: a power of two, 8 .. max_taps, rendered
+// into e.taps on the same stream before; above 8192 under reserved_long only)
 template <typename T>
 inline hipError_t eq_apply_launch(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+    if (R > (1L << kEqApplyMaxLog2B)) return eq_apply_launch_big<T>(a, e, base, R, st);
     switch (eq_apply_log2b(R, a.T)) {
     case 3: return eq_apply_launch_lds<T, 3>(a, e, base, R, st);
     case 4: return eq_apply_launch_lds<T, 4>(a, e, base, R, st);

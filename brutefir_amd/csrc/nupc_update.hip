@@ -152,7 +152,10 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
         if (base >= (int)n->eq.app.base.size() || !n->eq.app.base[base])
             return nfail(base >= (int)n->sets.coeff.size() ? BFHIP_EINVAL : BFHIP_ESTATE,
                          "nupc_render_eq_base: needs bfhip_nupc_reserve_eq_base for this filter before finalize");
-        if (taps < 8 || (taps & (taps - 1)) || taps > std::min(n->eq.reserve, 1L << kEqApplyMaxLog2B))
+        const bool pow2 = taps >= 8 && !(taps & (taps - 1));
+        if (n->eq.app.reserved_long && (!pow2 || taps > n->eq.reserve))
+            return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. max_taps = " + std::to_string(n->eq.reserve));
+        if (!n->eq.app.reserved_long && (!pow2 || taps > std::min(n->eq.reserve, 1L << kEqApplyMaxLog2B)))
             return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. min(max_taps, 8192)");
     }
     if (taps < 8 || (taps & (taps - 1)) || taps > n->eq.reserve)
@@ -398,6 +401,14 @@ int bfhip_nupc_reserve_eq_base(bfhip_nupc *n, int filter) {
     n->eq.base_want.resize(n->sets.coeff.size(), 0);
     n->eq.base_want[filter] = 1;
     n->eq.app.reserved = true;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_reserve_eq_base_long(bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_base_long after finalize");
+    if (!n->eq.reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_base_long: needs bfhip_nupc_reserve_eq first");
+    n->eq.app.reserved_long = true;
     return BFHIP_OK;
 }
 

@@ -341,8 +341,10 @@ int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const doubl
  * asynchronous call writes into the set: a set written by bfhip_nupc_render_eq_base_async has the
  * bits of bfhip_nupc_update_coeff_async with the synchronous call's array.
  *
- * eq_taps: a power of two, 8 <= eq_taps <= min(max_taps, 8192).  8192 is what one workgroup
- * transforms in LDS at float64; longer curves (through the big FFT) are a later step.
+ * eq_taps: a power of two, 8 <= eq_taps <= min(max_taps, 8192), and 8 <= eq_taps <= max_taps with
+ * bfhip_nupc_reserve_eq_base_long.  8192 is what one workgroup transforms in LDS at float64; a
+ * longer curve (at 48 kHz 8192 taps are 5.9 Hz per bin, too coarse for room modes) is one block of
+ * the overlap-save per eq_taps, transformed through the big FFT over global scratch.
  * Everything is allocated at finalize and only under a reservation: T reals per reserved filter, one
  * result of T reals, one spectrum, and the twiddle tables the renders do not already have.  A
  * convolver that never calls bfhip_nupc_reserve_eq_base allocates, launches and computes exactly as
@@ -351,6 +353,18 @@ int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const doubl
 /* before finalize, after bfhip_nupc_reserve_eq (BFHIP_ESTATE otherwise / after finalize); filter in
    range (BFHIP_EINVAL) */
 int bfhip_nupc_reserve_eq_base(bfhip_nupc *n, int filter);
+/* before finalize, after bfhip_nupc_reserve_eq (BFHIP_ESTATE otherwise / after finalize).  Lifts the
+   eq_taps limit of bfhip_nupc_render_eq_base* from min(max_taps, 8192) to max_taps; every other rule
+   of the two calls holds unchanged, and an eq_taps above the limit in force is BFHIP_EINVAL with that
+   limit in the message.  Independent of the order of the bfhip_nupc_reserve_eq_base calls.  For
+   eq_taps <= 8192 it changes no byte and no launch.  Allocates (at finalize) only when
+   max_taps > 8192 and some filter has a base reservation: three buffers of (ceil(T / B) + 1) B
+   complex values, the largest over the lengths B = 16384 .. max_taps (T + max_taps where max_taps
+   divides T), one spectrum of max_taps complex values and the twiddle table of max_taps points
+   (2 max_taps complex values).  T = 1 048 576 at float64: 150 994 944 bytes for
+   max_taps = 1 048 576, 56 623 104 bytes for max_taps = 65536.  A convolver that never calls this
+   allocates, launches and answers exactly as before. */
+int bfhip_nupc_reserve_eq_base_long(bfhip_nupc *n);
 /* after finalize; synchronous, for set-up and offline use, NOT for the audio thread.  taps: realsize
    wide, 1 <= n_taps <= T, shorter input is zero-padded (BFHIP_EINVAL otherwise).  A non-finite tap:
    BFHIP_EINVAL with the reference's "NaN or Inf value among coefficients.", and the base stays as it

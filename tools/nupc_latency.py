@@ -29,10 +29,10 @@ of synchronous renders (bfhip_nupc_render_eq: call, render, copy to the host, wa
 1 048 576 taps, made before the timed loop: an upper bound of the render's device time.  --eq-mode minimum
 renders every curve with minimum phase (BFHIP_EQ_MINIMUM: no taps / 2 frames of delay; three transforms
 instead of one).  --eq-taps sets the render length (default 1 048 576).  --eq-base is --eq with every curve
-rendered ONTO the filter's base impulse response (bfhip_nupc_render_eq_base_async: --eq-taps taps, default and
-at most 8192, convolved with the filter's own 1 048 576 taps on the device, all partitions rewritten); its
+rendered ONTO the filter's base impulse response (bfhip_nupc_render_eq_base_async: --eq-taps taps, default
+8192, above 8192 with bfhip_nupc_reserve_eq_base_long and through the big FFT, convolved with the filter's own 1 048 576 taps on the device, all partitions rewritten); its
 synchronous renders are bfhip_nupc_render_eq_base at 8 and at --eq-taps taps (1 048 576 reals to the host
-each).  --eq --eq-taps 8192 is the plain render to hold it against.  --gain-ramp sets an
+each).  --eq with the same --eq-taps is the plain render to hold it against.  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
@@ -112,6 +112,8 @@ def main():
         nu.reserve_eq(1048576)
         if a.eq_mode == "minimum":
             nu.reserve_eq_minimum()
+        if a.eq_base and eq_taps > 8192:
+            nu.reserve_eq_base_long()
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
