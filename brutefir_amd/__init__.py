@@ -244,6 +244,9 @@ def lib():
     L.bfhip_nupc_render_eq_base_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, dp, dp, ci]
     L.bfhip_nupc_render_eq_base.argtypes = [vp, ci, C.c_long, ci, dp, dp, dp, ci, vp]
     L.bfhip_nupc_reserve_eq_base_long.argtypes = [vp]
+    L.bfhip_nupc_reserve_eq_group.argtypes = [vp, ci]
+    L.bfhip_nupc_render_eq_group_async.argtypes = [vp, ci, ip, ip, ip, C.c_long, ci, dp, dp, dp, ci]
+    L.bfhip_nupc_update_result_member.argtypes = [vp, ci]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -785,6 +788,10 @@ class Nupc:
         """result of the last completed rewrite (raises on a non-finite tap, and while busy)"""
         return self._chk(lib().bfhip_nupc_update_result(self.h))
 
+    def update_result_member(self, member):
+        """result of member `member` of the last completed group (a single rewrite: member 0)"""
+        return self._chk(lib().bfhip_nupc_update_result_member(self.h, member))
+
     def update_wait(self):
         """blocks until the rewrite is done; not for the audio thread"""
         return self._chk(lib().bfhip_nupc_update_wait(self.h))
@@ -841,6 +848,22 @@ class Nupc:
         assert len(freq) == len(mag) == len(phase)
         self._chk(lib().bfhip_nupc_render_eq_base_async(self.h, filt, coeff, eq_taps, len(freq), _darr(list(freq)),
                                                         _darr(list(mag)), _darr(list(phase)), self._eq_mode(mode)))
+
+    # one render across a group of filters (include/bfhip_nupc.h)
+    def reserve_eq_group(self, max_members):
+        """before finalize, after reserve_eq: render_eq_group_async then takes up to max_members (2 .. 16) sets"""
+        self._chk(lib().bfhip_nupc_reserve_eq_group(self.h, max_members))
+
+    def render_eq_group_async(self, filters, coeffs, onto_base, eq_taps, freq, mag, phase, mode="linear"):
+        """one curve into the idle sets (filters[i], coeffs[i]) at once: onto the filter's base where
+        onto_base[i] is true (None: nowhere), the curve's taps alone otherwise; returns at once.  Every set
+        gets the bytes of render_eq_base_async / render_eq_async; update_busy / update_wait cover the group"""
+        assert len(freq) == len(mag) == len(phase) and len(filters) == len(coeffs)
+        assert onto_base is None or len(onto_base) == len(filters)
+        iarr = lambda v: (C.c_int * max(len(v), 1))(*[int(x) for x in v])
+        self._chk(lib().bfhip_nupc_render_eq_group_async(self.h, len(filters), iarr(filters), iarr(coeffs),
+                                                         None if onto_base is None else iarr(onto_base), eq_taps, len(freq),
+                                                         _darr(list(freq)), _darr(list(mag)), _darr(list(phase)), self._eq_mode(mode)))
 
     def render_eq_base(self, filt, eq_taps, freq, mag, phase, mode="linear"):
         """the same computation alone, synchronous: a numpy array of `taps` reals"""

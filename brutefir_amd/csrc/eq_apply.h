@@ -15,6 +15,8 @@
 //                                power of two: exact); E[0] and E[H] are real and share slot 0
 //     eq_apply_kernel            one workgroup per window: load -> lds_fft -> untangle, times E, tangle
 //                                -> lds_fft inverse -> the last B reals to y
+//     eq_apply_group_kernel      the same window for up to 16 bases under one E, grid (windows, members):
+//                                bfhip_nupc_render_eq_group_async
 // No atomics and no scratch: y is a pure function of e, b, B and T.  LDS is the padded array alone,
 // 139 280 bytes at float64 and B = 8192.
 #pragma once
@@ -85,9 +87,11 @@ __device__ __forceinline__ void eq_apply_load(LdsArr<T> s, int n0, const T *__re
     }
 }
 
+// one window of one base: y[at, at + B), at = blockIdx.x * B.  The body of both window kernels below, so
+// that a member of a group gets the single render's arithmetic operation for operation
 template <typename T, int LOG2H>
-__global__ __launch_bounds__(fft_threads<T>(LOG2H)) void
-eq_apply_kernel(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw, T *__restrict__ y, long Tn) {
+__device__ __forceinline__ void
+eq_apply_window(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw, T *__restrict__ y, long Tn) {
     constexpr int H = 1 << LOG2H, B = H, NT = fft_threads<T>(LOG2H);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LdsArr<T> s{reinterpret_cast<c2<T> *>(smem)};
@@ -136,6 +140,28 @@ eq_apply_kernel(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T
             if (i + 1 < Tn) y[i + 1] = v.y;
         }
     }
+}
+
+template <typename T, int LOG2H>
+__global__ __launch_bounds__(fft_threads<T>(LOG2H)) void
+eq_apply_kernel(const T *__restrict__ b, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw, T *__restrict__ y, long Tn) {
+    eq_apply_window<T, LOG2H>(b, E, tw, y, Tn);
+}
+
+// ---- a group of bases under one curve (bfhip_nupc_render_eq_group_async): grid (ceil(T / B), members),
+// member blockIdx.y takes its base and its result from the by-value table (256 bytes of kernel arguments:
+// no upload), E is the one spectrum of the call.  LDS is the padded array alone here too.
+constexpr int kEqGroupMax = 16;                       // BFHIP_NUPC_GROUP_MAX
+struct EqApplyGroup {
+    const void *b[kEqGroupMax];
+    void *y[kEqGroupMax];
+};
+
+template <typename T, int LOG2H>
+__global__ __launch_bounds__(fft_threads<T>(LOG2H)) void
+eq_apply_group_kernel(const EqApplyGroup g, const c2<T> *__restrict__ E, const c2<T> *__restrict__ tw, long Tn) {
+    const int m = blockIdx.y;                             // < members <= kEqGroupMax: the grid's height
+    eq_apply_window<T, LOG2H>(static_cast<const T *>(g.b[m]), E, tw, static_cast<T *>(g.y[m]), Tn);
 }
 
 // ---- R > 8192 (bfhip_nupc_reserve_eq_base_long): B = R, and a window's H = B points do not fit a
@@ -214,6 +240,7 @@ struct EqApply {
     long T = 0;
     std::vector<void *> base;                  // [filter]: T reals, nullptr without a reservation
     void *y = nullptr;                         // T reals: the device source of the rewrite
+    void *ys[kEqGroupMax] = {};                // [slot]: ys[0] = y; 1 .. max_members - 1 under bfhip_nupc_reserve_eq_group
     void *spec = nullptr;                      // B_max complex values, B_max <= 8192
     const void *tw[kEqMaxLog2H + 2] = {};      // [log2 B]: the render's table, or one of `own`
     void *own[kEqMaxLog2H + 2] = {};
@@ -240,6 +267,7 @@ inline hipError_t eq_apply_alloc(EqApply &a, const EqRender &e, long T, const st
     }
     if ((err = bfhip_internal_dev_alloc(&a.y, bytes)) != hipSuccess) return err;
     if ((err = hipMemset(a.y, 0, bytes)) != hipSuccess) return err;
+    a.ys[0] = a.y;
     const int lo = eq_apply_log2b(8, T), hi = eq_apply_log2b(std::min(e.max_taps, 1L << kEqApplyMaxLog2B), T);
     if ((err = bfhip_internal_dev_alloc(&a.spec, ((size_t)2 << hi) * e.rs)) != hipSuccess) return err;
     for (int l = lo; l <= hi; l++) {
@@ -263,34 +291,58 @@ inline hipError_t eq_apply_alloc(EqApply &a, const EqRender &e, long T, const st
     return bfhip_internal_dev_alloc(&a.big_spec, (size_t)e.max_taps * 2 * e.rs);
 }
 
+// what bfhip_nupc_reserve_eq_group adds: one more result of T reals per member beyond the first
+inline hipError_t eq_apply_group_alloc(EqApply &a, const EqRender &e, int max_members) {
+    hipError_t err;
+    const size_t bytes = (size_t)a.T * e.rs;
+    for (int m = 1; m < max_members; m++) {
+        if ((err = bfhip_internal_dev_alloc(&a.ys[m], bytes)) != hipSuccess) return err;
+        if ((err = hipMemset(a.ys[m], 0, bytes)) != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 inline void eq_apply_free(EqApply &a) {
+    for (int m = 1; m < kEqGroupMax; m++) if (a.ys[m]) { (void)hipFree(a.ys[m]); a.ys[m] = nullptr; }
+    a.ys[0] = nullptr;
     for (void *&p : a.base) if (p) { (void)hipFree(p); p = nullptr; }
     for (void *&p : a.own) if (p) { (void)hipFree(p); p = nullptr; }
     void **p[] = {&a.y, &a.spec, &a.big[0], &a.big[1], &a.big[2], &a.big_spec};
     for (void **q : p) if (*q) { (void)hipFree(*q); *q = nullptr; }
 }
 
+// n members: base[i] (*) e.taps[0 .. R) into y[i].  One member is the single render's two launches; more
+// are the spectrum once and one batched launch
 template <typename T, int LOG2H>
-inline hipError_t eq_apply_launch_lds(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+inline hipError_t eq_apply_launch_lds(const EqApply &a, const EqRender &e, int n, const void *const base[], void *const y[], long R,
+                                      hipStream_t st) {
     auto spec = eq_apply_spectrum_kernel<T, LOG2H>;
     auto kern = eq_apply_kernel<T, LOG2H>;
+    auto group = eq_apply_group_kernel<T, LOG2H>;
     const size_t lds = lds_fft_bytes(LOG2H, sizeof(c2<T>));
     hipError_t err;
     if ((err = hipFuncSetAttribute(reinterpret_cast<const void *>(spec), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
-    if ((err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
+    if (n == 1 && (err = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
+    if (n > 1 && (err = hipFuncSetAttribute(reinterpret_cast<const void *>(group), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return err;
     const dim3 nt(fft_threads<T>(LOG2H));
     const c2<T> *tw = (const c2<T> *)a.tw[LOG2H];
     hipLaunchKernelGGL(spec, dim3(1), nt, lds, st, (const c2<T> *)e.taps, (int)(R / 2), tw, (c2<T> *)a.spec);
     if ((err = hipGetLastError()) != hipSuccess) return err;
     const long B = 1L << LOG2H;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.T + B - 1) / B)), nt, lds, st, (const T *)base, (const c2<T> *)a.spec, tw,
-                       (T *)a.y, a.T);
+    const unsigned n_win = (unsigned)((a.T + B - 1) / B);
+    if (n == 1) {
+        hipLaunchKernelGGL(kern, dim3(n_win), nt, lds, st, (const T *)base[0], (const c2<T> *)a.spec, tw, (T *)y[0], a.T);
+        return hipGetLastError();
+    }
+    EqApplyGroup g = {};
+    for (int i = 0; i < n; i++) { g.b[i] = base[i]; g.y[i] = y[i]; }
+    hipLaunchKernelGGL(group, dim3(n_win, (unsigned)n), nt, lds, st, g, (const c2<T> *)a.spec, tw, a.T);
     return hipGetLastError();
 }
 
 // R > 8192: the windows through bigfft.h (needs what eq_apply_alloc adds under reserved_long)
 template <typename T>
-inline hipError_t eq_apply_launch_big(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
+inline hipError_t eq_apply_launch_big(const EqApply &a, const EqRender &e, const void *base, void *y, long R, hipStream_t st) {
     const int l = eq_apply_log2b(R, a.T);
     const long B = 1L << l;
     const int H = (int)B, n_win = (int)((a.T + B - 1) / B);
@@ -309,27 +361,37 @@ inline hipError_t eq_apply_launch_big(const EqApply &a, const EqRender &e, const
     if ((err = hipGetLastError()) != hipSuccess) return err;
     if ((err = big_fft_run<T, true>(z0, z1, z2, l, n_win, tw13, twL, st)) != hipSuccess) return err;
     hipLaunchKernelGGL(eq_apply_store_kernel<T>, dim3((unsigned)(B / 512), (unsigned)n_win), dim3(256), 0, st, (const c2<T> *)z2,
-                       (T *)a.y, l, a.T);
+                       (T *)y, l, a.T);
     return hipGetLastError();
 }
 
-// enqueue y = base (*) e.taps[0 .. R), truncated at T, into a.y (R: a power of two, 8 .. max_taps, rendered
-// into e.taps on the same stream before; above 8192 under reserved_long only)
+// enqueue y[i] = base[i] (*) e.taps[0 .. R), truncated at T, for n members (R: a power of two, 8 .. max_taps,
+// rendered into e.taps on the same stream before; above 8192 under reserved_long only, and there the members
+// go through the three big buffers one after another, each with the single render's launches: the curve is
+// member n_win of every member's forward batch again)
 template <typename T>
-inline hipError_t eq_apply_launch(const EqApply &a, const EqRender &e, const void *base, long R, hipStream_t st) {
-    if (R > (1L << kEqApplyMaxLog2B)) return eq_apply_launch_big<T>(a, e, base, R, st);
+inline hipError_t eq_apply_launch(const EqApply &a, const EqRender &e, int n, const void *const base[], void *const y[], long R,
+                                  hipStream_t st) {
+    if (n < 1 || n > kEqGroupMax) return hipErrorInvalidValue;
+    if (R > (1L << kEqApplyMaxLog2B)) {
+        for (int i = 0; i < n; i++) {
+            const hipError_t err = eq_apply_launch_big<T>(a, e, base[i], y[i], R, st);
+            if (err != hipSuccess) return err;
+        }
+        return hipSuccess;
+    }
     switch (eq_apply_log2b(R, a.T)) {
-    case 3: return eq_apply_launch_lds<T, 3>(a, e, base, R, st);
-    case 4: return eq_apply_launch_lds<T, 4>(a, e, base, R, st);
-    case 5: return eq_apply_launch_lds<T, 5>(a, e, base, R, st);
-    case 6: return eq_apply_launch_lds<T, 6>(a, e, base, R, st);
-    case 7: return eq_apply_launch_lds<T, 7>(a, e, base, R, st);
-    case 8: return eq_apply_launch_lds<T, 8>(a, e, base, R, st);
-    case 9: return eq_apply_launch_lds<T, 9>(a, e, base, R, st);
-    case 10: return eq_apply_launch_lds<T, 10>(a, e, base, R, st);
-    case 11: return eq_apply_launch_lds<T, 11>(a, e, base, R, st);
-    case 12: return eq_apply_launch_lds<T, 12>(a, e, base, R, st);
-    case 13: return eq_apply_launch_lds<T, 13>(a, e, base, R, st);
+    case 3: return eq_apply_launch_lds<T, 3>(a, e, n, base, y, R, st);
+    case 4: return eq_apply_launch_lds<T, 4>(a, e, n, base, y, R, st);
+    case 5: return eq_apply_launch_lds<T, 5>(a, e, n, base, y, R, st);
+    case 6: return eq_apply_launch_lds<T, 6>(a, e, n, base, y, R, st);
+    case 7: return eq_apply_launch_lds<T, 7>(a, e, n, base, y, R, st);
+    case 8: return eq_apply_launch_lds<T, 8>(a, e, n, base, y, R, st);
+    case 9: return eq_apply_launch_lds<T, 9>(a, e, n, base, y, R, st);
+    case 10: return eq_apply_launch_lds<T, 10>(a, e, n, base, y, R, st);
+    case 11: return eq_apply_launch_lds<T, 11>(a, e, n, base, y, R, st);
+    case 12: return eq_apply_launch_lds<T, 12>(a, e, n, base, y, R, st);
+    case 13: return eq_apply_launch_lds<T, 13>(a, e, n, base, y, R, st);
     default: return hipErrorInvalidValue;
     }
 }

@@ -115,20 +115,35 @@ struct NupcSubdelay {
 };
 
 // asynchronous set rewrite (bfhip_nupc_reserve_update / _update_coeff_async): everything is
-// allocated at finalize; one rewrite in flight at a time
+// allocated at finalize; one rewrite in flight at a time.  A rewrite is a group of members, each a set of
+// a filter of its own (bfhip_nupc_render_eq_group_async); every single call is a group of one.
+struct UpdMember {
+    int filter = -1, set = -1;
+    const uint8_t *src = nullptr;          // the member's taps: host (member 0 of a single call only) or device
+    long n_taps = 0;
+    int result = BFHIP_OK;                 // of the last completed rewrite
+};
+
 struct NupcUpdate {
     bool reserve = false;                  // asked for before finalize
     uint8_t *h_taps = nullptr;             // pinned staging: taps() reals (bfhip_nupc_update_buffer)
-    uint8_t *d_taps = nullptr;             // device staging: the segment engines prepare out of their slices
+    uint8_t *d_taps = nullptr;             // device staging of member 0: the segment engines prepare out of their slices
     hipStream_t stream = nullptr;          // loader: low priority, uploads the background segments' slices
     hipEvent_t ev_load = nullptr;          // the loader's upload is done
     hipEvent_t ev_main = nullptr;          // the main-stream segments' share is done
-    int *h_bad = nullptr;                  // pinned, one word per segment: the engine's non-finite flag
+    int *h_bad = nullptr;                  // pinned, one word per segment: the engine's non-finite flag for member 0
+    int *h_bad_group = nullptr;            // pinned, [member - 1][segment]: the same for the members behind it
     bool inflight = false;
-    bool failed = false;                   // enqueuing it failed part-way: the set's contents are unknown
-    int filter = -1, set = -1;             // the set being rewritten / rewritten last
-    int result = BFHIP_OK;                 // result of the last completed rewrite
+    bool failed = false;                   // enqueuing it failed part-way: the sets' contents are unknown
+    int n_members = 0;                     // of the rewrite in flight / completed last
+    UpdMember mem[kEqGroupMax];
+    int result = BFHIP_OK;                 // result of the last completed rewrite: BFHIP_OK iff every member's is
     std::vector<std::vector<char>> bad;    // [filter][set]: the last rewrite ended non-finite
+
+    bool rewrites(int filter, int set) const {
+        for (int m = 0; m < n_members; m++) if (mem[m].filter == filter && mem[m].set == set) return true;
+        return false;
+    }
 };
 
 // equaliser render (bfhip_nupc_reserve_eq / _render_eq_async, eq_render.h): a producer in front of
@@ -142,6 +157,7 @@ struct NupcEq {
     std::vector<char> base_want;           // [filter]: reserved before finalize
     std::vector<std::vector<unsigned char>> taps0;   // [filter]: add_filter's taps until finalize, the initial base
     hipEvent_t ev = nullptr;               // the render into lin.taps is done
+    int group = 0;                         // bfhip_nupc_reserve_eq_group's max_members, 0 = none
 };
 
 }  // namespace nupc_host

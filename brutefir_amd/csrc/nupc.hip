@@ -729,7 +729,7 @@ int bfhip_nupc_set_coeff(bfhip_nupc *n, int filter, int coeff) {
     if (n->sets.sched.busy()) return nfail(BFHIP_ESTATE, "nupc_set_coeff: the previous switch is still in flight (bfhip_nupc_switch_busy)");
     if (n->upd.reserve) {
         STEP(upd_poll(n));
-        if (n->upd.inflight && filter == n->upd.filter && coeff == n->upd.set)
+        if (n->upd.inflight && n->upd.rewrites(filter, coeff))
             return nfail(BFHIP_ESTATE, "nupc_set_coeff: a rewrite of this set is in flight (bfhip_nupc_update_busy)");
         if (n->upd.bad[filter][coeff])
             return nfail(BFHIP_ESTATE, "nupc_set_coeff: the last rewrite of this set found a NaN or Inf value among its coefficients");

@@ -30,13 +30,14 @@ bool past_set(const bfhip_nupc *n, int filter, int coeff, const void *taps, bool
     return false;
 }
 
-// a render on the loader stream: the curve in `mode` into eq.lin.taps[0 .. taps), and with base >= 0 that
-// filter's base convolved with them into eq.app.y (eq_apply.h)
+// a render on the loader stream: the curve in `mode` into eq.lin.taps[0 .. taps), and with n_base > 0 the
+// bases of those filters convolved with them into eq.app.ys[0 .. n_base) (eq_apply.h)
 struct EqJob {
     EqBands b;
     long taps = 0;
     int mode = BFHIP_EQ_LINEAR;
-    int base = -1;
+    int n_base = 0;
+    int base[kEqGroupMax] = {};
 };
 
 hipError_t eq_launch(const bfhip_nupc *n, const EqJob &j) {
@@ -48,18 +49,27 @@ hipError_t eq_launch(const bfhip_nupc *n, const EqJob &j) {
     else
         err = n->rs == 4 ? eq_render_launch<float>(n->eq.lin, j.b, j.taps, st)
                          : eq_render_launch<double>(n->eq.lin, j.b, j.taps, st);
-    if (err != hipSuccess || j.base < 0) return err;
-    return n->rs == 4 ? eq_apply_launch<float>(n->eq.app, n->eq.lin, n->eq.app.base[j.base], j.taps, st)
-                      : eq_apply_launch<double>(n->eq.app, n->eq.lin, n->eq.app.base[j.base], j.taps, st);
+    if (err != hipSuccess || j.n_base == 0) return err;
+    const void *base[kEqGroupMax];
+    for (int i = 0; i < j.n_base; i++) base[i] = n->eq.app.base[j.base[i]];
+    return n->rs == 4 ? eq_apply_launch<float>(n->eq.app, n->eq.lin, j.n_base, base, n->eq.app.ys, j.taps, st)
+                      : eq_apply_launch<double>(n->eq.app, n->eq.lin, j.n_base, base, n->eq.app.ys, j.taps, st);
 }
 
-// enqueue the upload and every segment engine's preparation of set (filter, coeff); no host wait,
-// no allocation.  Host source: the pinned staging buffer.  Device source: the loader (and the main
-// stream, for its own slices) waits on ready_event.
-int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event) {
+// the pinned word that segment k's engine writes its non-finite flag of member m to
+int *bad_word(const NupcUpdate &u, int m, size_t k, size_t n_seg) {
+    return m == 0 ? u.h_bad + k : u.h_bad_group + (size_t)(m - 1) * n_seg + k;
+}
+
+// enqueue the upload and every segment engine's preparation of the members of u.mem; no host wait, no
+// allocation.  Member 0 goes through the staging buffers as every single rewrite does: a host source out of
+// the pinned one, a device source behind ready_event, which the loader (and the main stream, for its own
+// slices) waits on.  The members behind it are device arrays of the convolver's own that nothing writes
+// while the group is in flight (eq.lin.taps, eq.app.ys): the engines prepare straight out of them.
+int upd_enqueue(bfhip_nupc *n, bool on_device, void *ready_event) {
     NupcUpdate &u = n->upd;
     const size_t rs = (size_t)n->rs;
-    const uint8_t *src = on_device ? (const uint8_t *)taps : u.h_taps;
+    const uint8_t *src = u.mem[0].src;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     bool main_waits = false;
     if (on_device && ready_event) NCHK(hipStreamWaitEvent(u.stream, (hipEvent_t)ready_event, 0));
@@ -74,36 +84,67 @@ int upd_enqueue(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_
         run_from = run_to = -1;
         return e;
     };
-    for (const Seg &s : n->seg) {
-        const long from = s.off, to = std::min(s.off + (long)s.L * s.N, n_taps);
-        if (to <= from) continue;
-        if (s.delay_steps > 0) {
-            if (run_to != from) { NCHK(flush()); run_from = from; }
-            run_to = to;
-            continue;
+    for (int m = 0; m < u.n_members; m++) {
+        for (const Seg &s : n->seg) {
+            const long from = s.off, to = std::min(s.off + (long)s.L * s.N, u.mem[m].n_taps);
+            if (to <= from) continue;
+            if (s.delay_steps > 0) {
+                if (m > 0) continue;
+                if (run_to != from) { NCHK(flush()); run_from = from; }
+                run_to = to;
+                continue;
+            }
+            // the main stream waits only where one of its own segments reads a member's taps
+            if (on_device && ready_event && !main_waits) { NCHK(hipStreamWaitEvent(n->stream, (hipEvent_t)ready_event, 0)); main_waits = true; }
+            if (m == 0) NCHK(hipMemcpyAsync(u.d_taps + (size_t)from * rs, src + (size_t)from * rs, (size_t)(to - from) * rs, kind, n->stream));
         }
-        if (on_device && ready_event && !main_waits) { NCHK(hipStreamWaitEvent(n->stream, (hipEvent_t)ready_event, 0)); main_waits = true; }
-        NCHK(hipMemcpyAsync(u.d_taps + (size_t)from * rs, src + (size_t)from * rs, (size_t)(to - from) * rs, kind, n->stream));
+        if (m == 0) NCHK(flush());
     }
-    NCHK(flush());
     NCHK(hipEventRecord(u.ev_load, u.stream));
-    // preparation: one launch per segment engine on the engine's own stream, in order with its blocks
+    // preparation: one launch per segment engine and member on the engine's own stream, in order with its blocks
     for (size_t k = 0; k < n->seg.size(); k++) {
         Seg &s = n->seg[k];
         const long cap = (long)s.L * s.N;
-        const long left = std::max(0L, std::min(n_taps - s.off, cap));
         if (s.delay_steps > 0) NCHK(hipStreamWaitEvent(s.stream, u.ev_load, 0));
-        ECHK(bfhip_internal_engine_update_coeff_dev_async(s.eng, n->sets.coeff[filter][coeff], u.d_taps + (size_t)s.off * rs,
-                                                          (int)left, s.n_blocks[filter][coeff], u.h_bad + k));
+        for (int m = 0; m < u.n_members; m++) {
+            const UpdMember &mb = u.mem[m];
+            const long left = std::max(0L, std::min(mb.n_taps - s.off, cap));
+            const uint8_t *from = m == 0 ? u.d_taps + (size_t)s.off * rs : left > 0 ? mb.src + (size_t)s.off * rs : mb.src;
+            ECHK(bfhip_internal_engine_update_coeff_dev_async(s.eng, n->sets.coeff[mb.filter][mb.set], from, (int)left,
+                                                              s.n_blocks[mb.filter][mb.set], bad_word(u, m, k, n->seg.size())));
+        }
         if (s.delay_steps > 0) NCHK(hipEventRecord(s.ev_upd, s.stream));
     }
     NCHK(hipEventRecord(u.ev_main, n->stream));
     return BFHIP_OK;
 }
 
-// the checks of an asynchronous rewrite, then upd_enqueue.  Host source: `taps` is the pinned staging
-// buffer or is copied into it.  eq: the taps are produced by this render on the loader stream first, and
-// eq.ev is the ready event (the caller passes taps = eq.lin.taps or eq.app.y, on_device).
+// every check has passed: the rewrite of n_members sets begins.  eq: the taps are produced by this render on
+// the loader stream first, and eq.ev is the ready event (the members' sources are eq.lin.taps / eq.app.ys).
+int upd_go(bfhip_nupc *n, int n_members, const UpdMember mem[], bool on_device, void *ready_event, const EqJob *eq) {
+    NupcUpdate &u = n->upd;
+    NCHK(hipSetDevice(n->device));
+    if (eq) {
+        // a failure here has touched eq.lin.taps and eq.app.ys only: the sets are as they were
+        NCHK(eq_launch(n, *eq));
+        NCHK(hipEventRecord(n->eq.ev, u.stream));
+        ready_event = n->eq.ev;
+    }
+    // from here on work may be enqueued: a failure leaves the sets' contents unknown
+    u.inflight = true;
+    u.n_members = n_members;
+    for (int m = 0; m < n_members; m++) {
+        u.mem[m] = mem[m];
+        u.bad[mem[m].filter][mem[m].set] = 1;
+    }
+    u.failed = false;
+    const int r = upd_enqueue(n, on_device, ready_event);
+    if (r < 0) u.failed = true;
+    return r;
+}
+
+// the checks of a single asynchronous rewrite, then upd_go with a group of one.  Host source: `taps` is the
+// pinned staging buffer or is copied into it.  eq: the caller passes taps = eq.lin.taps or eq.app.y, on_device.
 int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_device, long n_taps, void *ready_event,
               const EqJob *eq = nullptr) {
     if (!n) return nfail(BFHIP_EINVAL, "null");
@@ -120,21 +161,23 @@ int upd_start(bfhip_nupc *n, int filter, int coeff, const void *taps, bool on_de
     if (past_set(n, filter, coeff, taps, on_device, n_taps))
         return nfail(BFHIP_EINVAL, "nupc_update_coeff_async: set 0 of this filter is shorter than these taps (add_filter's length)");
     if (!on_device && taps != (const void *)u.h_taps) memcpy(u.h_taps, taps, (size_t)n_taps * n->rs);
-    NCHK(hipSetDevice(n->device));
-    if (eq) {
-        // a failure here has touched eq.lin.taps and eq.app.y only: the set is as it was
-        NCHK(eq_launch(n, *eq));
-        NCHK(hipEventRecord(n->eq.ev, u.stream));
-        ready_event = n->eq.ev;
-    }
-    // from here on work may be enqueued: a failure leaves the set's contents unknown
-    u.inflight = true;
-    u.filter = filter; u.set = coeff;
-    u.bad[filter][coeff] = 1;
-    u.failed = false;
-    const int r = upd_enqueue(n, filter, coeff, taps, on_device, n_taps, ready_event);
-    if (r < 0) u.failed = true;
-    return r;
+    UpdMember one;
+    one.filter = filter; one.set = coeff; one.n_taps = n_taps;
+    one.src = on_device ? (const uint8_t *)taps : u.h_taps;
+    return upd_go(n, 1, &one, on_device, ready_event, eq);
+}
+
+// a render onto a base: the filter's reservation and the limit on eq_taps in force
+int eq_base_check(const bfhip_nupc *n, int base, long taps) {
+    if (base >= (int)n->eq.app.base.size() || !n->eq.app.base[base])
+        return nfail(base >= (int)n->sets.coeff.size() ? BFHIP_EINVAL : BFHIP_ESTATE,
+                     "nupc_render_eq_base: needs bfhip_nupc_reserve_eq_base for this filter before finalize");
+    const bool pow2 = taps >= 8 && !(taps & (taps - 1));
+    if (n->eq.app.reserved_long && (!pow2 || taps > n->eq.reserve))
+        return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. max_taps = " + std::to_string(n->eq.reserve));
+    if (!n->eq.app.reserved_long && (!pow2 || taps > std::min(n->eq.reserve, 1L << kEqApplyMaxLog2B)))
+        return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. min(max_taps, 8192)");
+    return BFHIP_OK;
 }
 
 // state and curve checks shared by the render calls; fills the kernel-argument copy of the bands
@@ -148,16 +191,7 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
         return nfail(BFHIP_EINVAL, "nupc_render_eq: mode must be BFHIP_EQ_LINEAR or BFHIP_EQ_MINIMUM");
     if (mode == BFHIP_EQ_MINIMUM && !n->eq.min.reserved)
         return nfail(BFHIP_ESTATE, "nupc_render_eq: minimum phase needs bfhip_nupc_reserve_eq_minimum before finalize");
-    if (base >= 0) {
-        if (base >= (int)n->eq.app.base.size() || !n->eq.app.base[base])
-            return nfail(base >= (int)n->sets.coeff.size() ? BFHIP_EINVAL : BFHIP_ESTATE,
-                         "nupc_render_eq_base: needs bfhip_nupc_reserve_eq_base for this filter before finalize");
-        const bool pow2 = taps >= 8 && !(taps & (taps - 1));
-        if (n->eq.app.reserved_long && (!pow2 || taps > n->eq.reserve))
-            return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. max_taps = " + std::to_string(n->eq.reserve));
-        if (!n->eq.app.reserved_long && (!pow2 || taps > std::min(n->eq.reserve, 1L << kEqApplyMaxLog2B)))
-            return nfail(BFHIP_EINVAL, "nupc_render_eq_base: eq_taps must be a power of two, 8 .. min(max_taps, 8192)");
-    }
+    if (base >= 0) { const int r = eq_base_check(n, base, taps); if (r < 0) return r; }
     if (taps < 8 || (taps & (taps - 1)) || taps > n->eq.reserve)
         return nfail(BFHIP_EINVAL, "nupc_render_eq: taps must be a power of two, 8 .. max_taps");
     if (!freq || !mag || !phase || n_bands < 2 || n_bands > kEqMaxBands)
@@ -173,7 +207,9 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
         b->freq[i] = freq[i]; b->mag[i] = mag[i]; b->phase[i] = phase[i];
     }
     b->n = n_bands;
-    j->taps = taps; j->mode = mode; j->base = base;
+    j->taps = taps; j->mode = mode;
+    j->n_base = base >= 0 ? 1 : 0;
+    j->base[0] = base;
     return BFHIP_OK;
 }
 
@@ -214,6 +250,15 @@ int nupc_host::upd_finalize(bfhip_nupc *n, int prio_least) {
             if (n->eq.base_want[f]) NCHK(hipMemcpy(n->eq.app.base[f], n->eq.taps0[f].data(), n->eq.taps0[f].size(), hipMemcpyHostToDevice));
     }
     std::vector<std::vector<unsigned char>>().swap(n->eq.taps0);
+    // and the group render's behind those: a result per member beyond the first, and their non-finite words
+    if (n->eq.group) {
+        const size_t words = (size_t)(n->eq.group - 1) * n->seg.size();
+        hipError_t err = n->eq.app.reserved ? eq_apply_group_alloc(n->eq.app, n->eq.lin, n->eq.group) : hipSuccess;
+        if (err == hipSuccess) err = bfhip_internal_pin_alloc((void **)&u.h_bad_group, words * sizeof(int), hipHostMallocDefault);
+        if (err == hipErrorOutOfMemory) return nfail(BFHIP_ENOMEM, "nupc_finalize: out of memory for bfhip_nupc_reserve_eq_group's results");
+        NCHK(err);
+        memset(u.h_bad_group, 0, words * sizeof(int));
+    }
     return BFHIP_OK;
 }
 
@@ -222,6 +267,7 @@ void nupc_host::upd_release(bfhip_nupc *n) {
     NupcUpdate &u = n->upd;
     if (u.h_taps) (void)hipHostFree(u.h_taps);
     if (u.h_bad) (void)hipHostFree(u.h_bad);
+    if (u.h_bad_group) (void)hipHostFree(u.h_bad_group);
     if (u.d_taps) (void)hipFree(u.d_taps);
     eq_render_free(n->eq.lin);
     eq_minphase_free(n->eq.min);
@@ -232,9 +278,9 @@ void nupc_host::upd_release(bfhip_nupc *n) {
     if (u.stream) (void)hipStreamDestroy(u.stream);
 }
 
-// has every piece of the rewrite in flight completed?  hipEventQuery only: never blocks.  On
-// completion the segment engines' non-finite flags (pinned, written behind each preparation)
-// become the rewrite's result.
+// has every piece of every member of the rewrite in flight completed?  hipEventQuery only: never blocks.
+// On completion the segment engines' non-finite flags (pinned, written behind each preparation)
+// become the members' results, and the rewrite's.
 int nupc_host::upd_poll(bfhip_nupc *n) {
     NupcUpdate &u = n->upd;
     if (!u.inflight) return BFHIP_OK;
@@ -246,10 +292,15 @@ int nupc_host::upd_poll(bfhip_nupc *n) {
         if (e == hipErrorNotReady) { (void)hipGetLastError(); return BFHIP_OK; }
         if (e != hipSuccess) return nfail(BFHIP_EHIP, std::string("hipEventQuery: ") + hipGetErrorString(e));
     }
-    int bad = 0;
-    for (size_t k = 0; k < n->seg.size(); k++) bad |= ((volatile int *)u.h_bad)[k];
-    u.result = bad ? BFHIP_EINVAL : u.failed ? BFHIP_EHIP : BFHIP_OK;
-    u.bad[u.filter][u.set] = bad || u.failed ? 1 : 0;
+    int any = 0;
+    for (int m = 0; m < u.n_members; m++) {
+        int bad = 0;
+        for (size_t k = 0; k < n->seg.size(); k++) bad |= *(volatile int *)bad_word(u, m, k, n->seg.size());
+        u.mem[m].result = bad ? BFHIP_EINVAL : u.failed ? BFHIP_EHIP : BFHIP_OK;
+        u.bad[u.mem[m].filter][u.mem[m].set] = bad || u.failed ? 1 : 0;
+        any |= bad;
+    }
+    u.result = any ? BFHIP_EINVAL : u.failed ? BFHIP_EHIP : BFHIP_OK;
     u.inflight = false;
     return BFHIP_OK;
 }
@@ -322,6 +373,20 @@ int bfhip_nupc_update_result(bfhip_nupc *n) {
     if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_update_result: the rewrite is still in flight (bfhip_nupc_update_busy)");
     if (n->upd.result == BFHIP_EHIP) return nfail(BFHIP_EHIP, "nupc_update_result: the rewrite could not be enqueued completely");
     if (n->upd.result != BFHIP_OK) return nfail(n->upd.result, "NaN or Inf value among coefficients.");
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_update_result_member(bfhip_nupc *n, int member) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->upd.reserve) return nfail(BFHIP_ESTATE, "nupc_update_result_member: no reservation (bfhip_nupc_reserve_update)");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_update_result_member: the rewrite is still in flight (bfhip_nupc_update_busy)");
+    if (member < 0 || member >= n->upd.n_members)
+        return nfail(BFHIP_EINVAL, "nupc_update_result_member: the last rewrite had " + std::to_string(n->upd.n_members) + " members");
+    const int r = n->upd.mem[member].result;
+    if (r == BFHIP_EHIP) return nfail(BFHIP_EHIP, "nupc_update_result_member: the rewrite could not be enqueued completely");
+    if (r != BFHIP_OK) return nfail(r, "NaN or Inf value among coefficients.");
     return BFHIP_OK;
 }
 
@@ -457,6 +522,60 @@ int bfhip_nupc_render_eq_base(bfhip_nupc *n, int filter, long eq_taps, int n_ban
     NCHK(hipMemcpyAsync(taps_out, n->eq.app.y, (size_t)n->taps() * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
     NCHK(hipStreamSynchronize(n->upd.stream));
     return BFHIP_OK;
+}
+
+// ---- one render across a group of filters ----------------------------------------------------
+
+int bfhip_nupc_reserve_eq_group(bfhip_nupc *n, int max_members) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_group after finalize");
+    if (!n->eq.reserve) return nfail(BFHIP_ESTATE, "nupc_reserve_eq_group: needs bfhip_nupc_reserve_eq first");
+    if (max_members < 2 || max_members > BFHIP_NUPC_GROUP_MAX)
+        return nfail(BFHIP_EINVAL, "nupc_reserve_eq_group: 2 .. 16 members");
+    n->eq.group = max_members;
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_eq_group_async(bfhip_nupc *n, int n_members, const int filter[], const int coeff[],
+                                     const int onto_base[], long eq_taps, int n_bands, const double freq[],
+                                     const double mag[], const double phase[], int mode) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->eq.group)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq_group: needs bfhip_nupc_reserve_eq_group before finalize, and finalize");
+    if (n_members < 1 || n_members > n->eq.group || !filter || !coeff)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq_group: 1 .. max_members = " + std::to_string(n->eq.group) + " members, filter[] and coeff[]");
+    EqJob j;
+    { const int r = eq_check(n, eq_taps, n_bands, freq, mag, phase, mode, &j); if (r < 0) return r; }
+    // every member is checked before anything is enqueued; the message names the member
+    auto member = [&](int i, int code, const std::string &msg) {
+        return nfail(code, "nupc_render_eq_group: member " + std::to_string(i) + ": " + msg);
+    };
+    for (int i = 0; i < n_members; i++) {
+        if (!set_ok(n, filter[i], coeff[i])) return member(i, BFHIP_EINVAL, "no such filter or set");
+        if (onto_base && onto_base[i]) {
+            const int r = eq_base_check(n, filter[i], eq_taps);
+            if (r < 0) return member(i, r, bfhip_nupc_last_error());
+        }
+        if (n->sets.sched.set_in_use(filter[i], coeff[i]))
+            return member(i, BFHIP_ESTATE, "the set is live or part of a queued / in-flight switch");
+        for (int k = 0; k < i; k++)
+            if (filter[k] == filter[i] && coeff[k] == coeff[i]) return member(i, BFHIP_EINVAL, "the same set as member " + std::to_string(k));
+    }
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq_group: a rewrite is in flight (bfhip_nupc_update_busy)");
+    UpdMember mem[kEqGroupMax];
+    j.n_base = 0;
+    for (int i = 0; i < n_members; i++) {
+        const bool base = onto_base && onto_base[i];
+        mem[i].filter = filter[i]; mem[i].set = coeff[i];
+        mem[i].n_taps = base ? n->taps() : eq_taps;
+        mem[i].src = (const uint8_t *)(base ? n->eq.app.ys[j.n_base] : n->eq.lin.taps);
+        if (base) j.base[j.n_base++] = filter[i];
+        if (past_set(n, filter[i], coeff[i], mem[i].src, true, mem[i].n_taps))
+            return member(i, BFHIP_EINVAL, "set 0 of this filter is shorter than these taps (add_filter's length)");
+    }
+    return upd_go(n, n_members, mem, true, nullptr, &j);
 }
 
 }  // extern "C"

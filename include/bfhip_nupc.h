@@ -215,7 +215,8 @@ int bfhip_nupc_update_coeff(bfhip_nupc *n, int filter, int coeff, const void *ta
  * FFT scratch above 8192).  Per partition it is the arithmetic of bfhip_nupc_update_coeff: the
  * prepared set, and the output after a switch onto it, have the same bits.
  * Exactness: a rewrite of an idle set changes no output byte until a switch onto the set; the
- * state rules are those of bfhip_nupc_update_coeff.  One rewrite is in flight at a time.
+ * state rules are those of bfhip_nupc_update_coeff.  One rewrite is in flight at a time (a rewrite is
+ * one set, or the sets of one bfhip_nupc_render_eq_group_async call).
  * A convolver that never calls reserve_update allocates nothing more, makes the same launches
  * and changes no byte.
  * Cost: DESIGN.md section 4 and profiles/nupc_rewrite_latency.jsonl.
@@ -386,6 +387,70 @@ int bfhip_nupc_render_eq_base_async(bfhip_nupc *n, int filter, int coeff, long e
    for tests and offline use.  BFHIP_ESTATE while a rewrite is in flight. */
 int bfhip_nupc_render_eq_base(bfhip_nupc *n, int filter, long eq_taps, int n_bands, const double freq[],
                               const double mag[], const double phase[], int mode, void *taps_out);
+/* ---- one render across a group of filters (an extension) ------------------------------------------
+ * A tone control turns every filter of a crossbar under ONE curve, each filter on its own base.  With
+ * the calls above that is one rewrite after another, each a round trip the host has to poll for, and
+ * the curve rendered once per filter.  A group render names up to BFHIP_NUPC_GROUP_MAX idle sets of
+ * different filters in one call: the curve is rendered once, its spectrum is computed once, every
+ * member's convolution onto its base runs in one batched launch (eq_apply.h; beyond 8192 taps the
+ * members go through the big FFT's buffers one after another, the curve transformed with each), all
+ * members' preparations are enqueued together, and there is one completion to poll.  The
+ * bfhip_nupc_set_coeff group then switches the members as one preset.
+ *
+ * Bytes.  After completion every member's set holds exactly the bytes the corresponding single call
+ * writes into it -- bfhip_nupc_render_eq_base_async for a member rendered onto its base,
+ * bfhip_nupc_render_eq_mode_async for a plain one, with the same curve, mode and eq_taps, and the same
+ * base -- so the output after a switch onto the set is byte-identical to the output after the single
+ * call.  A group of one IS the single call: the same launches.
+ *
+ * Argument and state rules.  Every member is checked before anything is enqueued: any failing check
+ * answers its code, NOTHING changes for any member, and the message names the member.  Each member
+ * obeys its single call's rules: eq_taps within the limit in force for a member onto a base (8192, or
+ * max_taps with bfhip_nupc_reserve_eq_base_long) and within max_taps for a plain one; the curve rules
+ * unchanged; BFHIP_EQ_MINIMUM needs its reservation; coeff == 0 only where set 0 covers every partition
+ * (onto a base) or the eq_taps (plain); the set idle: neither live, queued, nor part of an in-flight
+ * switch (BFHIP_ESTATE).  Beyond those: 1 <= n_members <= max_members, filter and coeff non-NULL, the
+ * (filter, coeff) pairs pairwise distinct (BFHIP_EINVAL), no rewrite in flight and the reservation
+ * made (BFHIP_ESTATE).
+ *
+ * Busy, result and wait.  bfhip_nupc_update_busy is 1 until every piece of every member is complete;
+ * bfhip_nupc_update_wait waits for the group.  bfhip_nupc_update_result is BFHIP_OK iff every member is;
+ * if a member ended non-finite it is BFHIP_EINVAL with the reference's message, and
+ * bfhip_nupc_update_result_member says which.  bfhip_nupc_set_coeff onto a member's set answers
+ * BFHIP_ESTATE while the group is in flight, and afterwards only for the members that ended
+ * non-finite: the others can be switched to.  While a group is in flight every rewrite, render and
+ * bfhip_nupc_set_eq_base call answers what it answers during a single rewrite.
+ *
+ * Audio path.  The call makes no host wait, no allocation and no blocking copy, and no later block
+ * call makes one on its behalf; bands are copied at the call; the members' base and result pointers
+ * travel as kernel arguments (16 pointer pairs, 256 bytes): there is no upload.  The main stream waits
+ * for the render only where one of its own zero-slack segments reads a member's taps, as in a single
+ * render; it then waits for the whole group's render.
+ *
+ * Allocation.  At finalize, behind every other allocation: one result of T reals per member beyond the
+ * first (only where some filter has a base reservation), and (max_members - 1) * n_segments pinned
+ * words for the per-member non-finite flags.  T = 1 048 576 at float64 and a group of four:
+ * 3 * 8 388 608 = 25 165 824 bytes of device memory, and 12 pinned bytes per segment.  The members
+ * behind the first are prepared straight out of their results (and the plain ones out of the one
+ * rendered array: no copy per member), so the device staging buffer stays one.  A convolver that never
+ * calls bfhip_nupc_reserve_eq_group allocates, launches and computes exactly as before; one that
+ * reserves but never renders a group changes no output byte, and its single calls keep their bytes.
+ */
+#define BFHIP_NUPC_GROUP_MAX 16
+/* before finalize, after bfhip_nupc_reserve_eq (BFHIP_ESTATE otherwise / after finalize);
+   2 <= max_members <= BFHIP_NUPC_GROUP_MAX (BFHIP_EINVAL).  Everything a group needs is allocated at
+   finalize, behind every allocation made without it. */
+int bfhip_nupc_reserve_eq_group(bfhip_nupc *n, int max_members);
+/* one curve into n_members idle sets at once.  Member i is set coeff[i] of filter filter[i];
+   onto_base[i] != 0: the set receives base_i (*) eq as bfhip_nupc_render_eq_base_async writes it
+   (needs that filter's bfhip_nupc_reserve_eq_base), == 0: the curve's taps as
+   bfhip_nupc_render_eq_mode_async writes them.  onto_base == NULL: all zero. */
+int bfhip_nupc_render_eq_group_async(bfhip_nupc *n, int n_members, const int filter[], const int coeff[],
+                                     const int onto_base[], long eq_taps, int n_bands, const double freq[],
+                                     const double mag[], const double phase[], int mode);
+/* result of member i of the last completed group (a single rewrite is a group of one, member 0):
+   BFHIP_OK, BFHIP_EINVAL (non-finite), BFHIP_ESTATE while busy, BFHIP_EINVAL for i out of range */
+int bfhip_nupc_update_result_member(bfhip_nupc *n, int member);
 /* per-output gain applied at the emit step, in force from the first frame of the next block call's
    output (a step, or the start of a ramp: bfhip_nupc_set_gain_ramp below); 0.0 mutes; default 1.0
    (multiplied into the 1/scale factor in float64: exact) */

@@ -10,7 +10,7 @@ uniform engine's block time and I/O delay for the same filters.
 
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
-                                   | --eq-base [--eq-mode minimum] [--eq-taps R]]
+                                   | --eq-base [--eq-mode minimum] [--eq-taps R] | --eq-group [--eq-mode minimum] [--eq-taps R]]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -32,7 +32,10 @@ instead of one).  --eq-taps sets the render length (default 1 048 576).  --eq-ba
 rendered ONTO the filter's base impulse response (bfhip_nupc_render_eq_base_async: --eq-taps taps, default
 8192, above 8192 with bfhip_nupc_reserve_eq_base_long and through the big FFT, convolved with the filter's own 1 048 576 taps on the device, all partitions rewritten); its
 synchronous renders are bfhip_nupc_render_eq_base at 8 and at --eq-taps taps (1 048 576 reals to the host
-each).  --eq with the same --eq-taps is the plain render to hold it against.  --gain-ramp sets an
+each).  --eq with the same --eq-taps is the plain render to hold it against.  --eq-group is the --eq-base
+round with all four filters in ONE call (bfhip_nupc_render_eq_group_async: one curve per round, every filter
+onto its own base); it reports what --eq-base reports.  Both report knob_to_switch: periods and frames from the
+first render call of a round to the block call that commits the switch.  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--eq", action="store_true")
     ap.add_argument("--eq-mode", choices=["linear", "minimum"], default="linear")
     ap.add_argument("--eq-base", action="store_true")
+    ap.add_argument("--eq-group", action="store_true")
     ap.add_argument("--eq-taps", type=int)
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
@@ -101,7 +105,8 @@ def main():
         for io in (bf.IN, bf.OUT):
             for c in range(2):
                 nu.set_subdelay(io, c, 37 - 62 * c)
-    assert a.rewrite + a.rewrite_sync + a.eq + a.eq_base <= 1
+    assert a.rewrite + a.rewrite_sync + a.eq + a.eq_base + a.eq_group <= 1
+    a.eq_base = a.eq_base or a.eq_group
     a.eq = a.eq or a.eq_base
     assert a.eq or (a.eq_mode == "linear" and a.eq_taps is None)
     eq_taps = a.eq_taps or (8192 if a.eq_base else 1048576)
@@ -114,6 +119,8 @@ def main():
             nu.reserve_eq_minimum()
         if a.eq_base and eq_taps > 8192:
             nu.reserve_eq_base_long()
+        if a.eq_group:
+            nu.reserve_eq_group(4)
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -148,6 +155,7 @@ def main():
                 render_ms.append((n_taps, (time.perf_counter() - t0) * 1e3))
     live_set, todo, round_no, due = 0, [], 0, False
     call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
+    knob_at, knob_periods = None, []   # the period of a round's first render call -> periods to the committing block call
     in_flight = []                     # per period: a rewrite was in flight (or made) during it
     dump = []
     x = rng.standard_normal((8, L0, 2)) * 0.1
@@ -191,13 +199,22 @@ def main():
                     for f in range(4):
                         nu.set_coeff(f, 1 - live_set)
                     live_set = 1 - live_set
+                    if knob_at is not None:                    # this period's block call commits the switch
+                        knob_periods.append(s - knob_at)
+                        knob_at = None
             if todo and started_at is None:
                 f = todo.pop(0)
+                if a.eq_group:
+                    f, todo = [f] + todo, []
+                if a.eq_base and knob_at is None:
+                    knob_at = s
                 src = renders[round_no & 1]
                 if a.eq:
                     c = curve()
                     t0 = time.perf_counter()
-                    if a.eq_base:
+                    if a.eq_group:
+                        nu.render_eq_group_async(f, [1 - live_set] * 4, [1] * 4, eq_taps, *c, mode=a.eq_mode)
+                    elif a.eq_base:
                         nu.render_eq_base_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
                     else:
                         nu.render_eq_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
@@ -255,10 +272,12 @@ def main():
         "gain_ramp": {"ramp_frames": ramp_periods * L0, "outputs": [0, 1], "new_target_every_periods": 300,
                       "ramps": n_ramps, "step_ms_ramp_in_progress": dist(ts[rp]),
                       "step_ms_no_ramp": dist(ts[~rp])} if a.gain_ramp else None,
-        "rewrite": {"mode": ("eq-base" if a.eq_base else "eq") + ("" if a.eq_mode == "linear" else "-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+        "rewrite": {"mode": ("eq-group" if a.eq_group else "eq-base" if a.eq_base else "eq") + ("" if a.eq_mode == "linear" else "-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
                     "taps_per_set": int(nu.taps), "eq_taps": eq_taps if a.eq else None, "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
                     "periods_to_idle": dist(busy_periods),
+                    "knob_to_switch_periods": dist(knob_periods) if a.eq_base else None,
+                    "knob_to_switch_frames": dist(np.array(knob_periods) * L0) if a.eq_base else None,
                     "render_eq_sync_ms": {str(k): dist([v for n_taps, v in render_ms if n_taps == k][1:])
                                           for k in sync_taps} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
