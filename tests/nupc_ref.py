@@ -120,10 +120,12 @@ def new_overflows(fmts, start=None):
     return [bo.Overflow(0, 0, 0.0, 1.0 if f.isfloat else float((1 << (8 * f.sbytes - 1)) - 1)) for f in fmts]
 
 
-def encode(y, fmts, L0, gain=None, dither=(), rate=44100, max_size=0, overflow=None, safety_limit=0.0):
+def encode(y, fmts, L0, gain=None, dither=(), rate=44100, max_size=0, overflow=None, safety_limit=0.0, resets=()):
     """y: [frames][n_out] float64 reals; gain: per-channel factors, or [frames][n_out]; dither:
-    ascending output channels with HP-TPDF dither (slot = rank).  Returns (raw stream, overflow
-    structs, status bits per period).  Periods of L0 frames, as the library quantises them."""
+    ascending output channels with HP-TPDF dither (slot = rank); resets: periods in front of which
+    the overflow structs go back to their initial value (the dither walk goes on).  Returns (raw
+    stream, overflow structs, status bits per period).  Periods of L0 frames, as the library
+    quantises them."""
     n, n_out = y.shape
     assert n % L0 == 0
     g = np.ones(n_out) if gain is None else np.asarray(gain, np.float64)
@@ -137,6 +139,8 @@ def encode(y, fmts, L0, gain=None, dither=(), rate=44100, max_size=0, overflow=N
     status = []
     for b in range(n // L0):
         st_all = 0
+        if b in resets:
+            of = new_overflows(fmts)
         for c, f in enumerate(fmts):
             d = list(dither).index(c) if c in dither else -1
             seg = np.ascontiguousarray(v[b * L0:(b + 1) * L0, c])

@@ -5,12 +5,11 @@ update_delay then mute on output); with a period of L0 frames the nupc must prod
 The model is the oracle's integer delay (bfo_delay_new / bfo_delay_update, pinned to delay.c by
 tests/test_oracle_delay.py), applied per raw channel with fragment L0: the delayed, muted nupc
 equals a plain nupc fed the model's input, with the model applied to its output, byte for byte."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import bforacle as bo
+from nupc_chain_ref import Model
 
 pytestmark = pytest.mark.gpu
 SMALL = ([64, 128, 256, 512], [2, 2, 2, 6])               # offsets 0, 128, 384, 896; 3968 taps
@@ -18,54 +17,6 @@ C4 = ([64, 128, 256, 512, 1024, 2048], [2, 2, 2, 2, 2, 4])  # configs[4]-shaped,
 L0 = 64
 IN, OUT = 0, 1
 EINVAL, ESTATE = -1, -5
-
-
-def _olib():
-    L = bo.lib()
-    L.bfo_delay_new.restype = C.c_void_p
-    L.bfo_delay_new.argtypes = [C.c_int] * 4
-    L.bfo_delay_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.bfo_delay_free.argtypes = [C.c_void_p]
-    return L
-
-
-class Line:
-    """the oracle's delay line of one raw channel (fragment L0) and the channel's mute, with the
-    order dai.c uses on the side"""
-
-    def __init__(self, io, init, maxd, nbytes):
-        self.io, self.ss, self.maxd = io, nbytes, maxd
-        self.d = _olib().bfo_delay_new(L0, init, maxd, nbytes)
-        self.req, self.muted = init, False
-        self.cur = 0 if maxd == 0 else init          # curdelay (tests keep init <= a positive maxd)
-
-    def __del__(self):
-        _olib().bfo_delay_free(self.d)
-
-    def run(self, frames, ch):
-        """frames: [L0][frame bytes] uint8, modified in place"""
-        s = np.ascontiguousarray(frames[:, ch * self.ss:(ch + 1) * self.ss])
-        if self.io == IN and self.muted:
-            s[:] = 0
-        _olib().bfo_delay_update(self.d, s.ctypes.data, int(self.req))
-        if self.req != self.cur and self.req <= self.maxd:
-            self.cur = self.req
-        if self.io == OUT and self.muted:
-            s[:] = 0
-        frames[:, ch * self.ss:(ch + 1) * self.ss] = s
-
-
-class Model:
-    def __init__(self, io, fmt, spec):
-        """spec: per channel (initial delay, maxdelay)"""
-        self.nbytes = bo.SAMPLE_FORMATS[fmt][0]
-        self.lines = [Line(io, d, m, self.nbytes) for d, m in spec]
-
-    def run(self, raw):
-        fr = np.ascontiguousarray(raw).view(np.uint8).reshape(L0, -1).copy()
-        for ch, ln in enumerate(self.lines):
-            ln.run(fr, ch)
-        return fr.ravel()
 
 
 def _raw(rng, fmt, frames, n_ch, amp=0.3):
@@ -131,7 +82,7 @@ def test_input_delay_and_mute_equal_the_model_on_the_input(hip, rs, infmt, sched
     _configure(a, IN, spec)
     a.finalize()
     b.finalize()
-    m = Model(IN, infmt, spec)
+    m = Model(IN, infmt, spec, L0)
     x = _raw(np.random.default_rng(rs * 100 + len(infmt)), infmt, periods * L0, n_ch)
     for p in range(periods):
         if p == 10:
@@ -168,7 +119,7 @@ def test_output_delay_and_mute_equal_the_model_on_the_output(hip, rs, outfmt, di
     _configure(a, OUT, spec)
     a.finalize()
     b.finalize()
-    m = Model(OUT, outfmt, spec)
+    m = Model(OUT, outfmt, spec, L0)
     oa, ob = _ovf(outfmt, n_ch, hip), _ovf(outfmt, n_ch, hip)
     x = _raw(np.random.default_rng(17 + rs), infmt, 60 * L0, n_ch)
     clipped = 0
@@ -224,7 +175,7 @@ def _random_run(hip, rs, infmt, outfmt, seed, periods, sched=SMALL):
     assert L.bfhip_nupc_set_delay(a.h, OUT, 0, -5) == EINVAL
     assert L.bfhip_nupc_set_delay(a.h, OUT, n_ch, 5) == EINVAL
     assert L.bfhip_nupc_set_mute(a.h, 2, 0, 1) == EINVAL
-    mi, mo = Model(IN, infmt, spec_in), Model(OUT, outfmt, spec_out)
+    mi, mo = Model(IN, infmt, spec_in, L0), Model(OUT, outfmt, spec_out, L0)
     rng = np.random.default_rng(seed)
     x = _raw(rng, infmt, periods * L0, n_ch)
     choices = [0, 1, L0 - 1, L0, L0 + 1, 2 * L0 - 3, 2 * L0, 2 * L0 + 17, 3 * L0 + 10, 5 * L0, 5 * L0 + 1, 9 * L0]

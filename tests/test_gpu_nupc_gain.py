@@ -13,6 +13,7 @@ import pytest
 import bforacle as bo
 import cases
 import nupc_ref as nr
+from nupc_chain_ref import GainRamp
 
 pytestmark = pytest.mark.gpu
 TOL = {4: 1e-5, 8: 1e-12}
@@ -107,8 +108,8 @@ class Rig:
         [(block, t_sw, F, assignment)] and the per-frame output gain self.g"""
         nu = self.nu
         self.asg, self.req, self.F, self.switches = list(self.asg0), {}, L0, []
-        self.g = np.ones((self.n, 2)) * np.array(self.g0)
-        self.tgt, self.R, self.pend = list(self.g0), 0, {}
+        self.gr = GainRamp(self.n, L0, self.g0)
+        self.g = self.gr.g
         got, t_last = [], nu.switch_frame()
         if dev:
             import torch
@@ -153,26 +154,17 @@ class Rig:
             self.nu.set_filter_gain(f, g)
             self.req[f] = (self.req.get(f, (None, None))[0], g)
 
-    # ---- output gain: the header's ramp definition
+    # ---- output gain: the header's ramp definition (nupc_chain_ref.GainRamp)
     def ramp(self, R):
         self.nu.set_gain_ramp(R)
-        self.R = R
+        self.gr.set_ramp(R)
 
     def gain(self, ch, g):
         self.nu.set_output_gain(ch, g)
-        if g != self.pend.get(ch, (self.tgt[ch],))[0]:
-            self.pend[ch] = (g, self.R)
+        self.gr.request(ch, g)
 
     def _commit_gain(self, b):
-        t0 = b * L0
-        for ch, (g, R) in self.pend.items():
-            if g == self.tgt[ch]:
-                continue
-            a = self.g[t0 - 1, ch] if t0 else self.g0[ch]
-            j = np.arange(self.n - t0)
-            self.g[t0:, ch] = g if R == 0 else np.where(j >= R - 1, g, a + (g - a) * ((j + 1) / float(max(R, 1))))
-            self.tgt[ch] = g
-        self.pend = {}
+        self.gr.commit(b)
 
     def frames(self, raw):
         return nr.decode(raw, self.fmts, self.n)

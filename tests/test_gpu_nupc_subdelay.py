@@ -20,6 +20,7 @@ import pytest
 import bforacle as bo
 import cases
 import nupc_ref as nr
+from nupc_chain_ref import fir as _fir
 
 pytestmark = pytest.mark.gpu
 SMALL = ([64, 128, 256, 512], [2, 2, 2, 6])     # a zero-slack segment, background segments, L0 = 64
@@ -73,34 +74,6 @@ def _ovf(outfmt, n_ch, hip):
     return (hip.Overflow * n_ch)(*[hip.Overflow(0, 0, 0.0, mx) for _ in range(n_ch)])
 
 
-_TAPS = {}
-
-
-def _taps(hip, half, v, rs):
-    """the device's taps for value v, as float64 (computed once per key)"""
-    key = (half, v, rs)
-    if key not in _TAPS:
-        out = np.zeros(2 * half + 1, np.float32 if rs == 4 else np.float64)
-        assert hip.lib().bfhip_selftest_subdelay_filter(half, v, rs, out.ctypes.data) == 2 * half + 1
-        _TAPS[key] = out.astype(np.float64)
-    return _TAPS[key]
-
-
-def _fir(hip, x, vals, half, rs, L0):
-    """the stream x (float64 [frames]) through the per-period filters: period p uses the taps of
-    vals[p] from its first frame on, on the unfiltered history; x[t < 0] = 0.  vals None: the
-    channel has no filter and is delayed by `half` whole frames."""
-    n = len(x)
-    pad = np.concatenate([np.zeros(2 * half), x])
-    if vals is None:
-        return pad[half:half + n].copy()
-    y = np.zeros(n)
-    for p in range(n // L0):
-        seg = pad[p * L0:(p + 1) * L0 + 2 * half]
-        y[p * L0:(p + 1) * L0] = np.convolve(seg, _taps(hip, half, vals[p], rs), mode="valid")
-    return y
-
-
 def _run(nu, x, L0, periods, events=None, ovf=None):
     """periods block calls; events: {period: callable} run before that period's call"""
     out, sts = [], []
@@ -145,14 +118,14 @@ def _model(hip, x_raw, infmt, outfmt, n_ch, rs, L0, periods, half, filters, vin,
     if in_mute is not None:
         xr = np.where(in_mute, 0.0, xr)
     if any(v is not None for v in vin):
-        xr = np.stack([_fir(hip, xr[:, c], vin[c], half, rs, L0) for c in range(n_ch)], axis=1)
+        xr = np.stack([_fir(xr[:, c], vin[c], half, rs, L0) for c in range(n_ch)], axis=1)
     y = nr.convolve(xr, filters, n_ch)
     if blend:
         y = nr.crossfade(y, nr.convolve(xr, blend[0], n_ch), blend[1], blend[2])
     if gain is not None:
         y = y * gain
     if any(v is not None for v in vout):
-        y = np.stack([_fir(hip, y[:, c], vout[c], half, rs, L0) for c in range(n_ch)], axis=1)
+        y = np.stack([_fir(y[:, c], vout[c], half, rs, L0) for c in range(n_ch)], axis=1)
     raw, of, _ = nr.encode(y, _fmts(outfmt, n_ch), L0, dither=tuple(dither), rate=300)
     return raw
 
@@ -427,7 +400,7 @@ def test_filters_on_the_outputs_only_leave_the_input_path_alone(hip, rs):
     assert not any(sa) and not any(sb)
     fm = _fmts(fmt, n_ch)
     plain = nr.decode(yb, fm, periods * L0)
-    want = np.stack([_fir(hip, plain[:, c], [v] * periods, half, rs, L0) for c, v in enumerate((37, -25))], axis=1)
+    want = np.stack([_fir(plain[:, c], [v] * periods, half, rs, L0) for c, v in enumerate((37, -25))], axis=1)
     got = nr.decode(ya, fm, periods * L0)
     for c in range(n_ch):
         err = cases.rel_rms(got[:, c], want[:, c])

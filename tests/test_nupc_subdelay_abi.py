@@ -73,7 +73,7 @@ def test_enable_subdelay_argument_checks():
 
 
 @pytest.mark.parametrize("rs", [4, 8])
-@pytest.mark.parametrize("half", [7, 15, 31])
+@pytest.mark.parametrize("half", [7, 15, 31, 128, 255, 511])
 def test_value_zero_is_the_unit_pulse(half, rs):
     import brutefir_amd as bf
     want = np.zeros(2 * half + 1)
@@ -82,13 +82,16 @@ def test_value_zero_is_the_unit_pulse(half, rs):
 
 
 @pytest.mark.parametrize("rs,bar", [(4, 1e-5), (8, 1e-12)])
-@pytest.mark.parametrize("half", [7, 15, 31])
+@pytest.mark.parametrize("half", [7, 15, 31, 128, 255, 511])
 def test_taps_are_the_oracles_impulse_response(half, rs, bar):
     """a unit pulse through the oracle's engine (dirac filter, `subdelay: v` on the input, the way
     tests/test_oracle_engine.py drives it) is the filter the reference applies; relative RMS at the
-    project's parity bars (the oracle goes through its FFT overlap-save: not a bit comparison)"""
+    project's parity bars (the oracle goes through its FFT overlap-save: not a bit comparison).
+    The half-lengths above 31 are the ones whose filter block size (512, 1024) takes the device's
+    FIR through more than one history sample per thread; the oracle engine runs them at the smallest
+    block length that admits them, L >= 2 * half + 1."""
     import brutefir_amd as bf
-    L = 64
+    L = max(64, 1 << (2 * half + 1).bit_length())
     x = np.zeros((L, 1))
     x[0, 0] = 1.0
     for v in (-99, -75, -50, -25, -1, 1, 12, 37, 50, 63, 99):
