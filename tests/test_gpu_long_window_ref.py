@@ -24,163 +24,9 @@ import brutefir_amd as bf
 import cases
 import xbar_ref as xr
 
+from long_rig import L, TOL_BLOCK, TOL_RUN, Rig, _ir, blocks_for, both, drive, hold  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-L = 8192
-TOL_BLOCK, TOL_RUN = 2e-5, 1e-5
-
-
-def _ir(seed, taps, n_in):
-    return cases.make_ir(np.random.default_rng(seed), taps, n_in)
-
-
-class Rig:
-    """one crossbar configuration: sets (o, i) and extra sets ("x", k), filter f = o * I + i"""
-
-    def __init__(self, N, I, O, seed=1000, delays=None, lengths=None, gain=1.0, n_extra=0, crossfade=False,
-                 infmt="S24_4LE", outfmt="FLOAT_LE"):
-        self.N, self.I, self.O = N, I, O
-        self.infmt, self.outfmt, self.crossfade = infmt, outfmt, crossfade
-        self.delays = delays or {}
-        self.sets = {}
-        for o in range(O):
-            for i in range(I):
-                n = (lengths or {}).get((o, i), L * N)
-                self.sets[(o, i)] = _ir(seed + o * I + i, n, I) * gain
-        for k in range(n_extra):
-            self.sets[("x", k)] = _ir(seed + 7919 + k, L * N, I) * gain
-        self.model = [xr.Filter(i, o, self.sets[(o, i)], self.delay(o, i)) for o in range(O) for i in range(I)]
-        self.uses = [(o, i) for o in range(O) for i in range(I)]
-
-    def delay(self, o, i):
-        d = self.delays
-        return d.get((o, i), d.get(i, 0)) if isinstance(d, dict) else 0
-
-    def engine(self, monkeypatch, long, env=None, setup=None, sets_hook=None):
-        monkeypatch.setenv("BFHIP_LONG_WINDOW", "1" if long else "0")
-        for k in ("BFHIP_OVERLAP", "BFHIP_DEFER", "BFHIP_LONG_CHUNKS", "BFHIP_TEST_WRAP_PERIODS"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in (env or {}).items():
-            monkeypatch.setenv(k, v)
-        e = bf.Engine(L, self.N, 4, self.I, self.O)
-        if setup:
-            setup(e)
-        else:
-            e.set_interleaved(0, self.infmt)
-        e.set_interleaved(1, self.outfmt)
-        e.cid = {}
-        for key, h in self.sets.items():
-            e.cid[key] = e.add_coeff(h)
-        if sets_hook:
-            sets_hook(e)
-        for o in range(self.O):
-            for i in range(self.I):
-                e.add_filter(in_ch=[i], out_ch=[o], coeff=e.cid[(o, i)], delayblocks=self.delay(o, i),
-                             crossfade=self.crossfade)
-        e.finalize()
-        return e
-
-    # ---- control calls, applied to an engine and (once) to the model
-    def act(self, e, a):
-        if a[0] == "coeff":
-            e.set_coeff(a[1], e.cid[a[2]])
-        elif a[0] == "rewrite":
-            e.update_coeff_block(e.cid[a[1]], a[2], a[3])
-        elif a[0] == "delay":
-            e.set_delayblocks(a[1], a[2])
-
-    def model_act(self, t, a):
-        if a[0] == "coeff":
-            self.uses[a[1]] = a[2]
-            self.model[a[1]].change(t, fade=self.crossfade, taps=self.sets[a[2]])
-        elif a[0] == "rewrite":
-            h = self.sets[a[1]].copy()
-            h[a[2] * L:(a[2] + 1) * L] = a[3]
-            self.sets[a[1]] = h
-            for f, key in enumerate(self.uses):
-                if key == a[1]:
-                    self.model[f].change(t, taps=h)
-        elif a[0] == "delay":
-            self.model[a[1]].change(t, delay=a[2])
-
-    def expect(self, blocks, actions=None, x=None):
-        for t in sorted(actions or {}):
-            for a in actions[t]:
-                self.model_act(t, a)
-        if x is None:
-            x = xr.decode(np.concatenate(blocks), self.infmt, self.I)
-        return xr.output(x, self.model, L, self.N, self.O, len(blocks))
-
-
-def drive(rig, e, blocks, actions=None, rt=None):
-    """-> (outputs [frames][O] in the output format's units, status per block, window_blocks per block)"""
-    outs, sts, wins = [], [], []
-    if rt is not None:
-        e.rt_begin(rt)
-    pending = 0
-    for k, b in enumerate(blocks):
-        for a in (actions or {}).get(k, ()):
-            rig.act(e, a)
-        if rt is not None and rt & bf.RT_OVERLAP:
-            e.rt_submit(b)
-            pending += 1
-            if pending == 2:
-                st, raw = e.rt_wait()
-                pending -= 1
-                sts.append(st)
-                outs.append(raw)
-        elif rt is not None:
-            st, raw = e.rt_block(b)
-            sts.append(st)
-            outs.append(raw)
-        else:
-            st, raw = e.block(b)
-            sts.append(st)
-            outs.append(raw)
-        wins.append(e.window_blocks)
-    while pending:
-        st, raw = e.rt_wait()
-        pending -= 1
-        sts.append(st)
-        outs.append(raw)
-    if rt is not None:
-        e.rt_end()
-    e.sync()
-    y = xr.decode(np.concatenate(outs), rig.outfmt, rig.O)
-    return y, sts, wins
-
-
-def hold(got, want, label=""):
-    assert cases.rel_rms(got, want) <= TOL_RUN, label
-    for k in range(len(want) // L):
-        s = slice(k * L, (k + 1) * L)
-        err = cases.rel_rms(got[s], want[s])
-        assert err <= TOL_BLOCK, (label, k, err)
-
-
-def both(monkeypatch, rig, blocks, actions=None, env=None, win=None, rt=None):
-    """run the long and the standard engine, hold both to the model; win(k) -> the plan expected at
-    block k on the long engine (4 or 2), default 4 everywhere"""
-    got = {}
-    for long in (True, False):
-        e = rig.engine(monkeypatch, long, env)
-        y, sts, wins = drive(rig, e, blocks, actions, rt)
-        assert sts == [0] * len(blocks), (long, sts)
-        if long:
-            want_w = [win(k) if win else 4 for k in range(len(blocks))]
-            assert wins == want_w, wins
-        else:
-            assert set(wins) == {2}
-        got[long] = (y, e)
-    want = rig.expect(blocks, actions)
-    for long in (True, False):
-        hold(got[long][0], want, "long" if long else "standard")
-    for long in (True, False):
-        got[long][1].close()
-    return got[True][0], got[False][0], want
-
-
-def blocks_for(rig, n, seed=7, amplitude=0.1):
-    return cases.raw_blocks(seed, n, L, rig.I, rig.infmt, amplitude=amplitude)
 
 
 # ------------------------------------------------------------------ a. shapes
