@@ -18,6 +18,11 @@ IN, OUT = 0, 1
 EQ_LINEAR, EQ_MINIMUM = 0, 1                       # include/bfhip_nupc.h: BFHIP_EQ_*
 SWITCH_ALIGNED, SWITCH_STAGGERED = 0, 1            # include/bfhip_nupc.h: BFHIP_NUPC_SWITCH_*
 EQ_MODES = {"linear": EQ_LINEAR, "minimum": EQ_MINIMUM}
+BIQUAD_MAX = 32                                    # BFHIP_BIQUAD_MAX
+BIQUAD_OWN, BIQUAD_LINEAR = 0, 1                   # BFHIP_BIQUAD_OWN / _LINEAR: a namespace apart from EQ_*
+BIQUAD_PHASES = {"own": BIQUAD_OWN, "linear": BIQUAD_LINEAR}
+(BIQUAD_PEAK, BIQUAD_LOW_SHELF, BIQUAD_HIGH_SHELF, BIQUAD_LOW_PASS, BIQUAD_HIGH_PASS, BIQUAD_NOTCH,
+ BIQUAD_ALL_PASS) = range(7)                       # bfhip_biquad_design's types
 RT_SPIN, RT_NO_GRAPH, RT_COPY_ENGINE, RT_OVERLAP = 1, 2, 4, 8      # bfhip_engine_rt_begin flags
 COEFF_WATCH, COEFF_LAZY = 1, 2                                       # bfhip_engine_add_coeff_processed_blocks flags
 ST_NONFINITE, ST_SAFETY = 1, 2
@@ -247,6 +252,12 @@ def lib():
     L.bfhip_nupc_reserve_eq_group.argtypes = [vp, ci]
     L.bfhip_nupc_render_eq_group_async.argtypes = [vp, ci, ip, ip, ip, C.c_long, ci, dp, dp, dp, ci]
     L.bfhip_nupc_update_result_member.argtypes = [vp, ci]
+    L.bfhip_nupc_render_biquads.argtypes = [vp, C.c_long, ci, dp, ci, vp]
+    L.bfhip_nupc_render_biquads_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, ci]
+    L.bfhip_nupc_render_biquads_base.argtypes = [vp, ci, C.c_long, ci, dp, ci, vp]
+    L.bfhip_nupc_render_biquads_base_async.argtypes = [vp, ci, ci, C.c_long, ci, dp, ci]
+    L.bfhip_nupc_render_biquads_group_async.argtypes = [vp, ci, ip, ip, ip, C.c_long, ci, dp, ci]
+    L.bfhip_biquad_design.argtypes = [ci, cd, cd, cd, dp]
     L.bfhip_nupc_enable_dither.argtypes = [vp, ip, ci, ci, ci]
     L.bfhip_nupc_set_maxdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_set_delay.argtypes = [vp, ci, ci, ci]
@@ -873,6 +884,47 @@ class Nupc:
                                                   _darr(list(phase)), self._eq_mode(mode), _ptr(out)))
         return out
 
+    # parametric equaliser sections rendered on the device (include/bfhip_nupc.h): each call is its band
+    # counterpart with the curve given as an (n, 5) array of b0, b1, b2, a1, a2 and a phase "own" / "linear"
+    @staticmethod
+    def _sections(sections, phase):
+        s = np.ascontiguousarray(sections, np.float64)
+        assert s.ndim == 2 and s.shape[1] == 5, "sections: an (n, 5) array of b0, b1, b2, a1, a2"
+        return len(s), s.ctypes.data_as(C.POINTER(C.c_double)), BIQUAD_PHASES[phase] if isinstance(phase, str) else int(phase), s
+
+    def render_biquads(self, taps, sections, phase="own"):
+        """the cascade's response rendered into `taps` reals, synchronous: a numpy array.  phase: "own" (the
+        sections' own phase, time-aliased at `taps`, no delay) or "linear" (magnitude alone, taps/2 frames of delay)"""
+        n, p, ph, _keep = self._sections(sections, phase)
+        out = np.zeros(max(int(taps), 0), self.dt)
+        self._chk(lib().bfhip_nupc_render_biquads(self.h, taps, n, p, ph, _ptr(out)))
+        return out
+
+    def render_biquads_async(self, filt, coeff, taps, sections, phase="own"):
+        """render the cascade into `taps` reals on the device and rewrite an idle set with them; returns at once"""
+        n, p, ph, _keep = self._sections(sections, phase)
+        self._chk(lib().bfhip_nupc_render_biquads_async(self.h, filt, coeff, taps, n, p, ph))
+
+    def render_biquads_base(self, filt, eq_taps, sections, phase="own"):
+        """the cascade rendered into eq_taps reals and convolved onto the filter's base, synchronous: `taps` reals"""
+        n, p, ph, _keep = self._sections(sections, phase)
+        out = np.zeros(self.taps, self.dt)
+        self._chk(lib().bfhip_nupc_render_biquads_base(self.h, filt, eq_taps, n, p, ph, _ptr(out)))
+        return out
+
+    def render_biquads_base_async(self, filt, coeff, eq_taps, sections, phase="own"):
+        """render_eq_base_async with the curve given as sections; returns at once"""
+        n, p, ph, _keep = self._sections(sections, phase)
+        self._chk(lib().bfhip_nupc_render_biquads_base_async(self.h, filt, coeff, eq_taps, n, p, ph))
+
+    def render_biquads_group_async(self, filters, coeffs, onto_base, eq_taps, sections, phase="own"):
+        """render_eq_group_async with the curve given as sections; returns at once"""
+        assert len(filters) == len(coeffs) and (onto_base is None or len(onto_base) == len(filters))
+        n, p, ph, _keep = self._sections(sections, phase)
+        iarr = lambda v: (C.c_int * max(len(v), 1))(*[int(x) for x in v])
+        self._chk(lib().bfhip_nupc_render_biquads_group_async(self.h, len(filters), iarr(filters), iarr(coeffs),
+                                                              None if onto_base is None else iarr(onto_base), eq_taps, n, p, ph))
+
     def set_output_gain(self, ch, gain):
         self._chk(lib().bfhip_nupc_set_output_gain(self.h, ch, gain))
 
@@ -943,3 +995,13 @@ class Nupc:
 
 def device_count():
     return lib().bfhip_device_count()
+
+
+def biquad_design(type, f0, gain_db, q):
+    """one audio-EQ-cookbook section (bfhip_biquad_design: host only, needs no device): five float64
+    b0, b1, b2, a1, a2; f0 normalised, 0 < f0 < 0.5"""
+    coef = np.zeros(5, np.float64)
+    r = lib().bfhip_biquad_design(type, f0, gain_db, q, coef.ctypes.data_as(C.POINTER(C.c_double)))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return coef

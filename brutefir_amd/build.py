@@ -29,7 +29,7 @@ UNITS = {
     "channels.hip": DEVICE + ["engine.h", "channels.h", "alloc.h", "dither_init.h", "subdelay_filter.h"],
     "convolver_abi.hip": DEVICE + ["conv_shared.h"],
     "nupc.hip": NUPC + ["nupc_kernels.h", "dither_init.h", "subdelay_filter.h"],
-    "nupc_update.hip": NUPC + ["coeff_async.h"],
+    "nupc_update.hip": NUPC + ["coeff_async.h", "eq_biquad.h", "biquad_host.h"],
     "host_ops.cpp": ["host_fft.h", "conv_shared.h"] + PUBLIC,
 }
 

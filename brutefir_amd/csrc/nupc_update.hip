@@ -2,13 +2,14 @@
 // equaliser renders (include/bfhip_nupc.h; state in nupc.h).  None of this is on the audio path and none of
 // it launches a kernel of nupc_kernels.h: a rewrite uploads the taps and has every segment engine prepare
 // its slice on the engine's own stream, in order with the segment's blocks; a render (eq_render.h,
-// eq_minphase.h, and eq_apply.h where it goes onto a base) is a producer in front of a rewrite, on the loader
+// eq_minphase.h, eq_biquad.h, and eq_apply.h where it goes onto a base) is a producer in front of a rewrite, on the loader
 // stream.  Which sets may be rewritten is the switch schedule's answer (Switcher::set_in_use).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "coeff_async.h"
+#include "eq_biquad.h"
 #include "nupc.h"
 
 namespace {
@@ -30,12 +31,16 @@ bool past_set(const bfhip_nupc *n, int filter, int coeff, const void *taps, bool
     return false;
 }
 
-// a render on the loader stream: the curve in `mode` into eq.lin.taps[0 .. taps), and with n_base > 0 the
-// bases of those filters convolved with them into eq.app.ys[0 .. n_base) (eq_apply.h)
+// a render on the loader stream: the curve -- bands in `mode`, or sections in `phase` (eq_biquad.h) -- into
+// eq.lin.taps[0 .. taps), and with n_base > 0 the bases of those filters convolved with them into
+// eq.app.ys[0 .. n_base) (eq_apply.h)
 struct EqJob {
+    bool sections = false;
     EqBands b;
+    EqBiquads q;
     long taps = 0;
     int mode = BFHIP_EQ_LINEAR;
+    int phase = BFHIP_BIQUAD_OWN;
     int n_base = 0;
     int base[kEqGroupMax] = {};
 };
@@ -43,7 +48,10 @@ struct EqJob {
 hipError_t eq_launch(const bfhip_nupc *n, const EqJob &j) {
     const hipStream_t st = n->upd.stream;
     hipError_t err;
-    if (j.mode == BFHIP_EQ_MINIMUM)
+    if (j.sections)
+        err = n->rs == 4 ? eq_biquad_launch<float>(n->eq.lin, j.q, j.phase, j.taps, st)
+                         : eq_biquad_launch<double>(n->eq.lin, j.q, j.phase, j.taps, st);
+    else if (j.mode == BFHIP_EQ_MINIMUM)
         err = n->rs == 4 ? eq_minphase_launch<float>(n->eq.lin, n->eq.min, j.b, j.taps, st)
                          : eq_minphase_launch<double>(n->eq.lin, n->eq.min, j.b, j.taps, st);
     else
@@ -210,6 +218,85 @@ int eq_check(const bfhip_nupc *n, long taps, int n_bands, const double freq[], c
     j->taps = taps; j->mode = mode;
     j->n_base = base >= 0 ? 1 : 0;
     j->base[0] = base;
+    return BFHIP_OK;
+}
+
+// the same for a cascade of sections (biquad_host.h has the section rules); fills the kernel-argument copy
+int bq_check(const bfhip_nupc *n, long taps, int n_sections, const double coef[], int phase_mode, EqJob *j, int base = -1) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->eq.reserve)
+        return nfail(BFHIP_ESTATE, "nupc_render_biquads: needs bfhip_nupc_reserve_eq before finalize, and finalize");
+    if (phase_mode != BFHIP_BIQUAD_OWN && phase_mode != BFHIP_BIQUAD_LINEAR)
+        return nfail(BFHIP_EINVAL, "nupc_render_biquads: phase_mode must be BFHIP_BIQUAD_OWN or BFHIP_BIQUAD_LINEAR");
+    if (base >= 0) { const int r = eq_base_check(n, base, taps); if (r < 0) return r; }
+    if (taps < 8 || (taps & (taps - 1)) || taps > n->eq.reserve)
+        return nfail(BFHIP_EINVAL, "nupc_render_biquads: taps must be a power of two, 8 .. max_taps");
+    std::string why;
+    if (!biquad_check(n_sections, coef, &j->q, &why)) return nfail(BFHIP_EINVAL, "nupc_render_biquads: " + why);
+    j->sections = true;
+    j->taps = taps; j->phase = phase_mode;
+    j->n_base = base >= 0 ? 1 : 0;
+    j->base[0] = base;
+    return BFHIP_OK;
+}
+
+// a synchronous render alone: the job's taps (or, onto a base, its y) into host memory
+int eq_render_sync(bfhip_nupc *n, const EqJob &j, const char *who, void *taps_out) {
+    if (!taps_out) return nfail(BFHIP_EINVAL, std::string(who) + ": null buffer");
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, std::string(who) + ": a rewrite is in flight (bfhip_nupc_update_busy)");
+    NCHK(hipSetDevice(n->device));
+    NCHK(eq_launch(n, j));
+    const void *from = j.n_base ? n->eq.app.y : n->eq.lin.taps;
+    const size_t bytes = (size_t)(j.n_base ? n->taps() : j.taps) * n->rs;
+    NCHK(hipMemcpyAsync(taps_out, from, bytes, hipMemcpyDeviceToHost, n->upd.stream));
+    NCHK(hipStreamSynchronize(n->upd.stream));
+    return BFHIP_OK;
+}
+
+// a group render behind its curve check (j holds bands or sections): every member is checked before
+// anything is enqueued; the message names the member
+int eq_group_start(bfhip_nupc *n, int n_members, const int filter[], const int coeff[], const int onto_base[],
+                   long eq_taps, EqJob &j) {
+    auto member = [&](int i, int code, const std::string &msg) {
+        return nfail(code, "nupc_render_eq_group: member " + std::to_string(i) + ": " + msg);
+    };
+    for (int i = 0; i < n_members; i++) {
+        if (!set_ok(n, filter[i], coeff[i])) return member(i, BFHIP_EINVAL, "no such filter or set");
+        if (onto_base && onto_base[i]) {
+            const int r = eq_base_check(n, filter[i], eq_taps);
+            if (r < 0) return member(i, r, bfhip_nupc_last_error());
+        }
+        if (n->sets.sched.set_in_use(filter[i], coeff[i]))
+            return member(i, BFHIP_ESTATE, "the set is live or part of a queued / in-flight switch");
+        for (int k = 0; k < i; k++)
+            if (filter[k] == filter[i] && coeff[k] == coeff[i]) return member(i, BFHIP_EINVAL, "the same set as member " + std::to_string(k));
+    }
+    OWNER(n);
+    { const int r = upd_poll(n); if (r < 0) return r; }
+    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq_group: a rewrite is in flight (bfhip_nupc_update_busy)");
+    UpdMember mem[kEqGroupMax];
+    j.n_base = 0;
+    for (int i = 0; i < n_members; i++) {
+        const bool base = onto_base && onto_base[i];
+        mem[i].filter = filter[i]; mem[i].set = coeff[i];
+        mem[i].n_taps = base ? n->taps() : eq_taps;
+        mem[i].src = (const uint8_t *)(base ? n->eq.app.ys[j.n_base] : n->eq.lin.taps);
+        if (base) j.base[j.n_base++] = filter[i];
+        if (past_set(n, filter[i], coeff[i], mem[i].src, true, mem[i].n_taps))
+            return member(i, BFHIP_EINVAL, "set 0 of this filter is shorter than these taps (add_filter's length)");
+    }
+    return upd_go(n, n_members, mem, true, nullptr, &j);
+}
+
+// the state and count checks of a group call, in front of its curve check
+int eq_group_check(const bfhip_nupc *n, int n_members, const int filter[], const int coeff[]) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->finalized || !n->eq.group)
+        return nfail(BFHIP_ESTATE, "nupc_render_eq_group: needs bfhip_nupc_reserve_eq_group before finalize, and finalize");
+    if (n_members < 1 || n_members > n->eq.group || !filter || !coeff)
+        return nfail(BFHIP_EINVAL, "nupc_render_eq_group: 1 .. max_members = " + std::to_string(n->eq.group) + " members, filter[] and coeff[]");
     return BFHIP_OK;
 }
 
@@ -440,15 +527,7 @@ int bfhip_nupc_render_eq_mode(bfhip_nupc *n, long taps, int n_bands, const doubl
                               const double phase[], int mode, void *taps_out) {
     EqJob j;
     { const int r = eq_check(n, taps, n_bands, freq, mag, phase, mode, &j); if (r < 0) return r; }
-    if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq: null buffer");
-    OWNER(n);
-    { const int r = upd_poll(n); if (r < 0) return r; }
-    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq: a rewrite is in flight (bfhip_nupc_update_busy)");
-    NCHK(hipSetDevice(n->device));
-    NCHK(eq_launch(n, j));
-    NCHK(hipMemcpyAsync(taps_out, n->eq.lin.taps, (size_t)taps * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
-    NCHK(hipStreamSynchronize(n->upd.stream));
-    return BFHIP_OK;
+    return eq_render_sync(n, j, "nupc_render_eq", taps_out);
 }
 
 int bfhip_nupc_render_eq(bfhip_nupc *n, long taps, int n_bands, const double freq[], const double mag[],
@@ -513,15 +592,7 @@ int bfhip_nupc_render_eq_base(bfhip_nupc *n, int filter, long eq_taps, int n_ban
     if (n && filter < 0) return nfail(BFHIP_EINVAL, "nupc_render_eq_base: no such filter");
     EqJob j;
     { const int r = eq_check(n, eq_taps, n_bands, freq, mag, phase, mode, &j, filter); if (r < 0) return r; }
-    if (!taps_out) return nfail(BFHIP_EINVAL, "nupc_render_eq_base: null buffer");
-    OWNER(n);
-    { const int r = upd_poll(n); if (r < 0) return r; }
-    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq_base: a rewrite is in flight (bfhip_nupc_update_busy)");
-    NCHK(hipSetDevice(n->device));
-    NCHK(eq_launch(n, j));
-    NCHK(hipMemcpyAsync(taps_out, n->eq.app.y, (size_t)n->taps() * n->rs, hipMemcpyDeviceToHost, n->upd.stream));
-    NCHK(hipStreamSynchronize(n->upd.stream));
-    return BFHIP_OK;
+    return eq_render_sync(n, j, "nupc_render_eq_base", taps_out);
 }
 
 // ---- one render across a group of filters ----------------------------------------------------
@@ -539,43 +610,56 @@ int bfhip_nupc_reserve_eq_group(bfhip_nupc *n, int max_members) {
 int bfhip_nupc_render_eq_group_async(bfhip_nupc *n, int n_members, const int filter[], const int coeff[],
                                      const int onto_base[], long eq_taps, int n_bands, const double freq[],
                                      const double mag[], const double phase[], int mode) {
-    if (!n) return nfail(BFHIP_EINVAL, "null");
-    if (!n->finalized || !n->eq.group)
-        return nfail(BFHIP_ESTATE, "nupc_render_eq_group: needs bfhip_nupc_reserve_eq_group before finalize, and finalize");
-    if (n_members < 1 || n_members > n->eq.group || !filter || !coeff)
-        return nfail(BFHIP_EINVAL, "nupc_render_eq_group: 1 .. max_members = " + std::to_string(n->eq.group) + " members, filter[] and coeff[]");
+    { const int r = eq_group_check(n, n_members, filter, coeff); if (r < 0) return r; }
     EqJob j;
     { const int r = eq_check(n, eq_taps, n_bands, freq, mag, phase, mode, &j); if (r < 0) return r; }
-    // every member is checked before anything is enqueued; the message names the member
-    auto member = [&](int i, int code, const std::string &msg) {
-        return nfail(code, "nupc_render_eq_group: member " + std::to_string(i) + ": " + msg);
-    };
-    for (int i = 0; i < n_members; i++) {
-        if (!set_ok(n, filter[i], coeff[i])) return member(i, BFHIP_EINVAL, "no such filter or set");
-        if (onto_base && onto_base[i]) {
-            const int r = eq_base_check(n, filter[i], eq_taps);
-            if (r < 0) return member(i, r, bfhip_nupc_last_error());
-        }
-        if (n->sets.sched.set_in_use(filter[i], coeff[i]))
-            return member(i, BFHIP_ESTATE, "the set is live or part of a queued / in-flight switch");
-        for (int k = 0; k < i; k++)
-            if (filter[k] == filter[i] && coeff[k] == coeff[i]) return member(i, BFHIP_EINVAL, "the same set as member " + std::to_string(k));
-    }
-    OWNER(n);
-    { const int r = upd_poll(n); if (r < 0) return r; }
-    if (n->upd.inflight) return nfail(BFHIP_ESTATE, "nupc_render_eq_group: a rewrite is in flight (bfhip_nupc_update_busy)");
-    UpdMember mem[kEqGroupMax];
-    j.n_base = 0;
-    for (int i = 0; i < n_members; i++) {
-        const bool base = onto_base && onto_base[i];
-        mem[i].filter = filter[i]; mem[i].set = coeff[i];
-        mem[i].n_taps = base ? n->taps() : eq_taps;
-        mem[i].src = (const uint8_t *)(base ? n->eq.app.ys[j.n_base] : n->eq.lin.taps);
-        if (base) j.base[j.n_base++] = filter[i];
-        if (past_set(n, filter[i], coeff[i], mem[i].src, true, mem[i].n_taps))
-            return member(i, BFHIP_EINVAL, "set 0 of this filter is shorter than these taps (add_filter's length)");
-    }
-    return upd_go(n, n_members, mem, true, nullptr, &j);
+    return eq_group_start(n, n_members, filter, coeff, onto_base, eq_taps, j);
+}
+
+// ---- parametric equaliser sections (eq_biquad.h, biquad_host.h) -------------------------------
+
+int bfhip_biquad_design(int type, double f0, double gain_db, double q, double coef[5]) {
+    if (!biquad_design(type, f0, gain_db, q, coef))
+        return nfail(BFHIP_EINVAL, "biquad_design: type 0 .. 6, 0 < f0 < 0.5, q > 0, gain_db finite, coef non-NULL");
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_render_biquads_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_sections, const double coef[],
+                                    int phase_mode) {
+    EqJob j;
+    { const int r = bq_check(n, taps, n_sections, coef, phase_mode, &j); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.lin.taps, true, taps, nullptr, &j);
+}
+
+int bfhip_nupc_render_biquads(bfhip_nupc *n, long taps, int n_sections, const double coef[], int phase_mode, void *taps_out) {
+    EqJob j;
+    { const int r = bq_check(n, taps, n_sections, coef, phase_mode, &j); if (r < 0) return r; }
+    return eq_render_sync(n, j, "nupc_render_biquads", taps_out);
+}
+
+int bfhip_nupc_render_biquads_base_async(bfhip_nupc *n, int filter, int coeff, long eq_taps, int n_sections,
+                                         const double coef[], int phase_mode) {
+    if (n && filter < 0) return nfail(BFHIP_EINVAL, "nupc_render_biquads_base: no such filter");
+    EqJob j;
+    { const int r = bq_check(n, eq_taps, n_sections, coef, phase_mode, &j, filter); if (r < 0) return r; }
+    return upd_start(n, filter, coeff, n->eq.app.y, true, n->taps(), nullptr, &j);
+}
+
+int bfhip_nupc_render_biquads_base(bfhip_nupc *n, int filter, long eq_taps, int n_sections, const double coef[],
+                                   int phase_mode, void *taps_out) {
+    if (n && filter < 0) return nfail(BFHIP_EINVAL, "nupc_render_biquads_base: no such filter");
+    EqJob j;
+    { const int r = bq_check(n, eq_taps, n_sections, coef, phase_mode, &j, filter); if (r < 0) return r; }
+    return eq_render_sync(n, j, "nupc_render_biquads_base", taps_out);
+}
+
+int bfhip_nupc_render_biquads_group_async(bfhip_nupc *n, int n_members, const int filter[], const int coeff[],
+                                          const int onto_base[], long eq_taps, int n_sections, const double coef[],
+                                          int phase_mode) {
+    { const int r = eq_group_check(n, n_members, filter, coeff); if (r < 0) return r; }
+    EqJob j;
+    { const int r = bq_check(n, eq_taps, n_sections, coef, phase_mode, &j); if (r < 0) return r; }
+    return eq_group_start(n, n_members, filter, coeff, onto_base, eq_taps, j);
 }
 
 }  // extern "C"

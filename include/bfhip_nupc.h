@@ -451,6 +451,94 @@ int bfhip_nupc_render_eq_group_async(bfhip_nupc *n, int n_members, const int fil
 /* result of member i of the last completed group (a single rewrite is a group of one, member 0):
    BFHIP_OK, BFHIP_EINVAL (non-finite), BFHIP_ESTATE while busy, BFHIP_EINVAL for i out of range */
 int bfhip_nupc_update_result_member(bfhip_nupc *n, int member);
+/* ---- parametric equaliser sections rendered on the device (an extension: bflogic_eq knows bands only) --
+ * The second curve producer in front of the same machinery.  A tone control holds second-order sections
+ * -- shelves, peaks, notches, high and low passes -- not knots; sampled into 130 cosine-joined knots they
+ * are approximate and lose their own (minimum) phase.  Here the host hands over 5 doubles per section and
+ * the device evaluates the cascade exactly, per bin, in float64: no host FFT, no upload of taps.
+ *
+ * Sections.  coef holds n_sections * 5 doubles, section k being b0, b1, b2, a1, a2 with a0 = 1:
+ *     H_k(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2)
+ * 1 <= n_sections <= BFHIP_BIQUAD_MAX; every value finite; every section strictly stable, |a2| < 1 and
+ * |a1| < 1 + a2 (which keeps the denominator off zero on the unit circle: a render has no device-side
+ * error path beyond the non-finite flag every rewrite has).  Anything else: BFHIP_EINVAL, the message
+ * names the section, nothing changes.
+ *
+ * Response.  R = taps, bin n = 0 .. R/2, s = sin^2(pi n / R), u = sin(2 pi n / R):
+ *     N_k  = ((b0 + b1) + b2) - 2 (b0 + b2) s + i (b0 - b2) u
+ *     D_k  = ((1  + a1) + a2) - 2 (1  + a2) s + i (1  - a2) u
+ *     G[n] = prod_k N_k / D_k          (k ascending, float64 complex for both precisions)
+ * = prod_k H_k(e^{i 2 pi n / R}); the common factor e^{-i w} cancels.  This form, not b0 + b1 z + b2 z^2:
+ * at low frequencies 1 + a1 + a2 is of the order w0^2, and the direct polynomial loses that many digits
+ * again at every bin.
+ *
+ * Phase.  BFHIP_BIQUAD_OWN:    X[n] = G[n] / R (0 < n < R/2), X[0] = Re G[0] / R, X[R/2] = Re G[R/2] / R.
+ *         BFHIP_BIQUAD_LINEAR: X[n] = (-1)^n |G[n]| / R,      X[0] = |G[0]| / R,  X[R/2] = |G[R/2]| / R.
+ * Any other value: BFHIP_EINVAL.  The taps are the unnormalised HC2R of X exactly as in the band render
+ * above: X is rounded to the convolver's real type once and the transform runs in that type.
+ * OWN gives taps[t] = sum_m h[t + m R], h the cascade's infinite impulse response: the response
+ * TIME-ALIASED at R.  It adds no delay; R must be long enough for h to have decayed (a Q = 30 notch at
+ * 50 Hz / 48 kHz rings for about 1e5 frames: what has not decayed wraps onto the first taps).  LINEAR
+ * gives the magnitude alone with R/2 frames of delay, like BFHIP_EQ_LINEAR.  There is no homomorphic mode
+ * for sections: a cascade that is minimum phase (peaks, shelves, low and high passes) is so under OWN.
+ * These constants are a namespace of their own: BFHIP_EQ_* and what the band calls answer are unchanged.
+ *
+ * Calls.  Each one is its band counterpart with (n_bands, freq, mag, phase, mode) replaced by
+ * (n_sections, coef, phase_mode); the reservations are the band calls' own (bfhip_nupc_reserve_eq,
+ * _reserve_eq_base, _reserve_eq_base_long, _reserve_eq_group): no new reservation and no new allocation,
+ * the sections travel as kernel arguments (at most 1280 bytes).  State rules, the taps and eq_taps limits,
+ * the set-0 length rule, busy / result / wait / bfhip_nupc_update_result_member, "one rewrite in flight",
+ * "no host wait, no allocation, no blocking copy, arguments copied at the call", "a failed check changes
+ * nothing" and the group's all-members-checked-first rule are the corresponding band call's, word for
+ * word.  A render is a pure function of its arguments; what the asynchronous call writes into a set has
+ * the bits of bfhip_nupc_update_coeff_async with the synchronous call's array; a group member's set has
+ * the bytes of the single call.  A convolver that never calls these allocates, launches and computes
+ * exactly as before, and the band renders keep their bytes.
+ */
+#define BFHIP_BIQUAD_MAX    32
+#define BFHIP_BIQUAD_OWN    0
+#define BFHIP_BIQUAD_LINEAR 1
+/* bfhip_nupc_render_eq_mode: synchronous, `taps` reals into host memory */
+int bfhip_nupc_render_biquads(bfhip_nupc *n, long taps, int n_sections, const double coef[], int phase_mode,
+                              void *taps_out);
+/* bfhip_nupc_render_eq_mode_async */
+int bfhip_nupc_render_biquads_async(bfhip_nupc *n, int filter, int coeff, long taps, int n_sections,
+                                    const double coef[], int phase_mode);
+/* bfhip_nupc_render_eq_base: synchronous, bfhip_nupc_taps() reals into host memory */
+int bfhip_nupc_render_biquads_base(bfhip_nupc *n, int filter, long eq_taps, int n_sections, const double coef[],
+                                   int phase_mode, void *taps_out);
+/* bfhip_nupc_render_eq_base_async */
+int bfhip_nupc_render_biquads_base_async(bfhip_nupc *n, int filter, int coeff, long eq_taps, int n_sections,
+                                         const double coef[], int phase_mode);
+/* bfhip_nupc_render_eq_group_async */
+int bfhip_nupc_render_biquads_group_async(bfhip_nupc *n, int n_members, const int filter[], const int coeff[],
+                                          const int onto_base[], long eq_taps, int n_sections,
+                                          const double coef[], int phase_mode);
+/* Section designer: host only, makes no HIP call and works on a machine without a device.  f0 is
+ * normalised like the bands' freq, 0 < f0 < 0.5; q > 0; gain_db finite (ignored by the last four types);
+ * type one of the seven below; coef non-NULL: BFHIP_EINVAL otherwise, and coef is untouched.  The
+ * audio-EQ-cookbook formulas, with
+ *     A = 10^(gain_db / 40),  w0 = 2 pi f0,  c = cos w0,  alpha = sin w0 / (2 q),  r = 2 sqrt(A) alpha,
+ *     S = sin^2(w0 / 2) = (1 - c) / 2,  C = cos^2(w0 / 2) = (1 + c) / 2   (written so: nothing is lost at low f0)
+ * and every value divided by a0:
+ *   PEAK        b = 1 + alpha A,  -2 c,  1 - alpha A                  a = 1 + alpha / A,  -2 c,  1 - alpha / A
+ *   LOW_SHELF   b0 = A ((A+1) - (A-1) c + r)   b1 =  2 A ((A-1) - (A+1) c)   b2 = A ((A+1) - (A-1) c - r)
+ *               a0 =    (A+1) + (A-1) c + r    a1 = -2   ((A-1) + (A+1) c)   a2 =    (A+1) + (A-1) c - r
+ *   HIGH_SHELF  b0 = A ((A+1) + (A-1) c + r)   b1 = -2 A ((A-1) + (A+1) c)   b2 = A ((A+1) + (A-1) c - r)
+ *               a0 =    (A+1) - (A-1) c + r    a1 =  2   ((A-1) - (A+1) c)   a2 =    (A+1) - (A-1) c - r
+ *   LOW_PASS    b = S,  2 S,  S                                       a = 1 + alpha,  -2 c,  1 - alpha
+ *   HIGH_PASS   b = C,  -2 C,  C                                      a = 1 + alpha,  -2 c,  1 - alpha
+ *   NOTCH       b = 1,  -2 c,  1                                      a = 1 + alpha,  -2 c,  1 - alpha
+ *   ALL_PASS    b = 1 - alpha,  -2 c,  1 + alpha                      a = 1 + alpha,  -2 c,  1 - alpha
+ * coef receives b0/a0, b1/a0, b2/a0, a1/a0, a2/a0. */
+#define BFHIP_BIQUAD_PEAK       0
+#define BFHIP_BIQUAD_LOW_SHELF  1
+#define BFHIP_BIQUAD_HIGH_SHELF 2
+#define BFHIP_BIQUAD_LOW_PASS   3
+#define BFHIP_BIQUAD_HIGH_PASS  4
+#define BFHIP_BIQUAD_NOTCH      5
+#define BFHIP_BIQUAD_ALL_PASS   6
+int bfhip_biquad_design(int type, double f0, double gain_db, double q, double coef[5]);
 /* per-output gain applied at the emit step, in force from the first frame of the next block call's
    output (a step, or the start of a ramp: bfhip_nupc_set_gain_ramp below); 0.0 mutes; default 1.0
    (multiplied into the 1/scale factor in float64: exact) */

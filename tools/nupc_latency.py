@@ -11,6 +11,7 @@ uniform engine's block time and I/O delay for the same filters.
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
                                    | --eq-base [--eq-mode minimum] [--eq-taps R] | --eq-group [--eq-mode minimum] [--eq-taps R]]
+                                  [--biquads [--biquad-phase own|linear]]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -35,7 +36,10 @@ synchronous renders are bfhip_nupc_render_eq_base at 8 and at --eq-taps taps (1 
 each).  --eq with the same --eq-taps is the plain render to hold it against.  --eq-group is the --eq-base
 round with all four filters in ONE call (bfhip_nupc_render_eq_group_async: one curve per round, every filter
 onto its own base); it reports what --eq-base reports.  Both report knob_to_switch: periods and frames from the
-first render call of a round to the block call that commits the switch.  --gain-ramp sets an
+first render call of a round to the block call that commits the switch.  --biquads, with --eq, --eq-base or
+--eq-group, gives every curve of the same rotation as a cascade of 32 second-order sections (a low shelf, a
+high shelf and 30 peaks, +-12 dB, seeded; bfhip_nupc_render_biquads*: the sections' own phase, or
+--biquad-phase linear) and reports what those options report.  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
 --dump-output writes the raw output of all timed
@@ -72,6 +76,8 @@ def main():
     ap.add_argument("--eq-base", action="store_true")
     ap.add_argument("--eq-group", action="store_true")
     ap.add_argument("--eq-taps", type=int)
+    ap.add_argument("--biquads", action="store_true")
+    ap.add_argument("--biquad-phase", choices=["own", "linear"], default="own")
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
@@ -108,7 +114,9 @@ def main():
     assert a.rewrite + a.rewrite_sync + a.eq + a.eq_base + a.eq_group <= 1
     a.eq_base = a.eq_base or a.eq_group
     a.eq = a.eq or a.eq_base
-    assert a.eq or (a.eq_mode == "linear" and a.eq_taps is None)
+    assert a.eq or (a.eq_mode == "linear" and a.eq_taps is None and not a.biquads)
+    assert a.biquads or a.biquad_phase == "own"
+    assert not (a.biquads and a.eq_mode == "minimum"), "sections have no homomorphic mode: their own phase is --biquad-phase own"
     eq_taps = a.eq_taps or (8192 if a.eq_base else 1048576)
     rewriting = a.rewrite or a.rewrite_sync or a.eq
     if a.rewrite or a.eq:
@@ -139,6 +147,27 @@ def main():
     def curve():
         freq = np.concatenate([[0.0], np.sort(rng.uniform(0.0005, 0.4995, 128)), [0.5]])
         return list(freq), list(10.0 ** (rng.uniform(-12, 12, 130) / 20) / 2000.0), list(rng.uniform(-3, 3, 130))
+
+
+    def sections():
+        s = [bf.biquad_design(bf.BIQUAD_LOW_SHELF, float(rng.uniform(0.001, 0.01)), float(rng.uniform(-12, 12)), 0.707),
+             bf.biquad_design(bf.BIQUAD_HIGH_SHELF, float(rng.uniform(0.1, 0.3)), float(rng.uniform(-12, 12)), 0.707)]
+        for _ in range(30):
+            s.append(bf.biquad_design(bf.BIQUAD_PEAK, float(np.exp(rng.uniform(np.log(0.0005), np.log(0.45)))),
+                                      float(rng.uniform(-12, 12)), float(rng.uniform(0.5, 8.0))))
+        s = np.array(s)
+        s[0, :3] /= 2000.0                                         # the band curves' level
+        return s
+    if a.biquads:
+        # the curve is (sections, phase) and every render call its section counterpart
+        curve = lambda: (sections(), a.biquad_phase)
+        kw = {}
+        render, render_async = nu.render_biquads, nu.render_biquads_async
+        render_base, render_base_async, render_group_async = nu.render_biquads_base, nu.render_biquads_base_async, nu.render_biquads_group_async
+    else:
+        kw = {"mode": a.eq_mode}
+        render, render_async = nu.render_eq, nu.render_eq_async
+        render_base, render_base_async, render_group_async = nu.render_eq_base, nu.render_eq_base_async, nu.render_eq_group_async
     render_ms = []
     if a.eq:
         # a synchronous render of 8 taps is the call, the wait and a copy of 64 bytes; one of 1 048 576
@@ -149,9 +178,9 @@ def main():
             for _ in range(5):
                 t0 = time.perf_counter()
                 if a.eq_base:
-                    nu.render_eq_base(0, n_taps, *c, mode=a.eq_mode)
+                    render_base(0, n_taps, *c, **kw)
                 else:
-                    nu.render_eq(n_taps, *c, mode=a.eq_mode)
+                    render(n_taps, *c, **kw)
                 render_ms.append((n_taps, (time.perf_counter() - t0) * 1e3))
     live_set, todo, round_no, due = 0, [], 0, False
     call_ms, call_copy_ms, busy_periods, started_at = [], [], [], None
@@ -213,11 +242,11 @@ def main():
                     c = curve()
                     t0 = time.perf_counter()
                     if a.eq_group:
-                        nu.render_eq_group_async(f, [1 - live_set] * 4, [1] * 4, eq_taps, *c, mode=a.eq_mode)
+                        render_group_async(f, [1 - live_set] * 4, [1] * 4, eq_taps, *c, **kw)
                     elif a.eq_base:
-                        nu.render_eq_base_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
+                        render_base_async(f, 1 - live_set, eq_taps, *c, **kw)
                     else:
-                        nu.render_eq_async(f, 1 - live_set, eq_taps, *c, mode=a.eq_mode)
+                        render_async(f, 1 - live_set, eq_taps, *c, **kw)
                     call_ms.append((time.perf_counter() - t0) * 1e3)
                     started_at = s
                 elif a.rewrite:
@@ -272,7 +301,7 @@ def main():
         "gain_ramp": {"ramp_frames": ramp_periods * L0, "outputs": [0, 1], "new_target_every_periods": 300,
                       "ramps": n_ramps, "step_ms_ramp_in_progress": dist(ts[rp]),
                       "step_ms_no_ramp": dist(ts[~rp])} if a.gain_ramp else None,
-        "rewrite": {"mode": ("eq-group" if a.eq_group else "eq-base" if a.eq_base else "eq") + ("" if a.eq_mode == "linear" else "-minimum") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
+        "rewrite": {"mode": ("eq-group" if a.eq_group else "eq-base" if a.eq_base else "eq") + ("" if a.eq_mode == "linear" else "-minimum") + ("-biquads-" + a.biquad_phase if a.biquads else "") if a.eq else "async" if a.rewrite else "sync", "every_periods": 300, "sets_per_round": 4,
                     "taps_per_set": int(nu.taps), "eq_taps": eq_taps if a.eq else None, "rounds": round_no,
                     "call_ms": dist(call_ms), "call_with_staging_copy_ms": dist(call_copy_ms),
                     "periods_to_idle": dist(busy_periods),
