@@ -267,6 +267,14 @@ def lib():
     L.bfhip_nupc_set_subdelay.argtypes = [vp, ci, ci, ci]
     L.bfhip_nupc_get_subdelay.argtypes = [vp, ci, ci]
     L.bfhip_selftest_subdelay_filter.argtypes = [ci, ci, ci, vp]
+    L.bfhip_nupc_enable_limiter.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_add_limiter_group.argtypes = [vp, ip, ci, cd]
+    L.bfhip_nupc_set_limiter_threshold.argtypes = [vp, ci, cd]
+    L.bfhip_nupc_get_limiter_threshold.restype = cd
+    L.bfhip_nupc_get_limiter_threshold.argtypes = [vp, ci]
+    L.bfhip_nupc_limiter_delay.argtypes = [vp]
+    L.bfhip_nupc_get_limiter_reduction.argtypes = [vp, ci, dp]
+    L.bfhip_selftest_limiter_envelope.argtypes = [ci, cd, C.c_long, dp, dp]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -991,6 +999,51 @@ class Nupc:
         if io not in (IN, OUT) or not 0 <= ch < (self.n_out if io == OUT else self.n_in):
             raise BfhipError("get_subdelay: bad argument")     # (a value may be negative: no code to tell by)
         return lib().bfhip_nupc_get_subdelay(self.h, io, ch)
+
+    # linked look-ahead peak limiter on the outputs (include/bfhip_nupc.h)
+    def enable_limiter(self, lookahead_frames, release_frames):
+        """before finalize: every output leaves lookahead_frames later"""
+        self._chk(lib().bfhip_nupc_enable_limiter(self.h, lookahead_frames, release_frames))
+
+    def add_limiter_group(self, out_channels, threshold):
+        """before finalize, after enable_limiter: the channels share one envelope; threshold is a linear
+        fraction of full scale (inf: never limits).  Returns the group index"""
+        chs = list(out_channels)
+        return self._chk(lib().bfhip_nupc_add_limiter_group(self.h, _iarr(chs), len(chs), threshold))
+
+    def set_limiter_threshold(self, group, threshold):
+        """in force for the frames of the next block call on"""
+        self._chk(lib().bfhip_nupc_set_limiter_threshold(self.h, group, threshold))
+
+    def limiter_threshold(self, group):
+        v = lib().bfhip_nupc_get_limiter_threshold(self.h, group)
+        if v != v:
+            raise BfhipError("limiter_threshold: bad group")
+        return v
+
+    def limiter_delay(self):
+        """the look-ahead D, 0 without a limiter"""
+        return lib().bfhip_nupc_limiter_delay(self.h)
+
+    def limiter_reduction(self, group):
+        """the smallest gain the group's envelope applied since the previous call (1.0 if none); waits
+        for the main stream"""
+        v = C.c_double(1.0)
+        self._chk(lib().bfhip_nupc_get_limiter_reduction(self.h, group, C.byref(v)))
+        return v.value
+
+
+def limiter_envelope(lookahead_frames, release_frames, p):
+    """s of the limiter's definition from p, fresh state (bfhip_selftest_limiter_envelope: host only,
+    needs no device)"""
+    p = np.ascontiguousarray(p, np.float64)
+    s = np.zeros(len(p), np.float64)
+    dp = C.POINTER(C.c_double)
+    r = lib().bfhip_selftest_limiter_envelope(lookahead_frames, release_frames, len(p), p.ctypes.data_as(dp),
+                                              s.ctypes.data_as(dp))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return s
 
 
 def device_count():

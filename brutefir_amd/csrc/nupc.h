@@ -17,6 +17,7 @@
 #include "eq_minphase.h"
 #include "eq_render.h"
 #include "kernels.h"
+#include "limiter_host.h"
 #include "nupc_sched.h"
 
 using namespace bfhip;
@@ -160,6 +161,31 @@ struct NupcEq {
     int group = 0;                         // bfhip_nupc_reserve_eq_group's max_members, 0 = none
 };
 
+// look-ahead peak limiter on the outputs (bfhip_nupc_enable_limiter).  Nothing of it exists in a convolver
+// that never enables it.  All of its state lives on the device and never crosses to the host per period.
+struct NupcLimGroup {                      // one row of the group table, host and device
+    int n_ch, pad;
+    int ch[kLimGroupMax];
+    double scale[kLimGroupMax];            // the members' fmt.scale (filled at finalize)
+};
+struct NupcLimThr { double v[kLimGroupsMax]; };     // this period's thresholds: a kernel argument
+struct NupcLimiter {
+    bool on = false;
+    int D = 0;                             // look-ahead in frames
+    double release = 0, a = 0;             // release_frames and exp(-1 / release_frames)
+    std::vector<NupcLimGroup> groups;
+    std::vector<double> thr;               // per group: in force from the next block call
+    std::vector<int> group_of;             // [n_out]: the channel's group, -1 = none
+    unsigned int meter_reset = 0;          // bit g: the next block call starts group g's meter afresh
+    void *d_ring = nullptr;                // [n_out][D + L0] reals: x_c, frame t in cell t mod (D + L0)
+    // [group][parity][2 D + 1] float64: the last D values of r, of e (e[t-1] is the last), and the meter's
+    // running minimum.  Period k reads parity k & 1 and the group's first member writes the other one.
+    double *d_state = nullptr;
+    NupcLimGroup *d_groups = nullptr;
+    int *d_group_of = nullptr;             // [n_out]
+    size_t state_stride() const { return (size_t)2 * D + 1; }
+};
+
 }  // namespace nupc_host
 
 using namespace nupc_host;
@@ -192,6 +218,7 @@ struct bfhip_nupc {
     NupcSubdelay sd;
     NupcUpdate upd;
     NupcEq eq;
+    NupcLimiter lim;
 
     int L0() const { return seg[0].L; }
     long taps() const { return seg.back().off + (long)seg.back().L * seg.back().N; }

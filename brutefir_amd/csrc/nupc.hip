@@ -147,7 +147,8 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     }
     void *p[] = {n->d_acc[0], n->d_acc[1], n->d_in, n->d_rawout, n->io.d_fmt[1], n->og.d, n->st.d_over, n->st.d_status,
                  n->st.d_arrive, n->dither.d_slot, n->dither.d_state, n->dither.d_table, n->dither.d_randmap,
-                 n->dither.d_stage, n->sd.d_bank, n->sd.d_hist[0], n->sd.d_hist[1], n->io.d_fmt[0], n->d_in_real, n->d_stage};
+                 n->dither.d_stage, n->sd.d_bank, n->sd.d_hist[0], n->sd.d_hist[1], n->io.d_fmt[0], n->d_in_real, n->d_stage,
+                 n->lim.d_ring, n->lim.d_group_of, n->lim.d_groups, n->lim.d_state};
     for (void *q : p) if (q) (void)hipFree(q);
     for (auto &side : n->dl) for (auto &d : side) if (d.arena) (void)hipFree(d.arena);
     void *h[] = {n->st.h_status, n->io.h_in, n->io.h_out, n->st.h_over, n->og.h};
@@ -544,6 +545,21 @@ int fin_segments(bfhip_nupc *n, int prio_least) {
     return BFHIP_OK;
 }
 
+// the limiter's rings, state and group table: only under bfhip_nupc_enable_limiter, behind everything else
+int fin_limiter(bfhip_nupc *n) {
+    NupcLimiter &lm = n->lim;
+    if (!lm.on) return BFHIP_OK;
+    for (auto &g : lm.groups)
+        for (int k = 0; k < g.n_ch; k++) g.scale[k] = n->io.fmt[1][g.ch[k]].scale;
+    STEP(dev_zeroed(&lm.d_ring, (size_t)n->n_out * (lm.D + n->L0()) * n->rs));      // x[t < 0] = 0
+    STEP(dev_copy(&lm.d_group_of, lm.group_of));
+    if (lm.groups.empty()) return BFHIP_OK;              // a pure delay of every output
+    STEP(dev_copy(&lm.d_groups, lm.groups));
+    const std::vector<double> fresh(lm.groups.size() * 2 * lm.state_stride(), 1.0);  // r = e = 1 before frame 0
+    STEP(dev_copy(&lm.d_state, fresh));
+    return BFHIP_OK;
+}
+
 int finalize_impl(bfhip_nupc *n) {
     OWNER(n);
     STEP(fin_subdelay_sides(n));
@@ -562,6 +578,7 @@ int finalize_impl(bfhip_nupc *n) {
     STEP(fin_spare_ring(n));
     STEP(fin_segments(n, prio_least));
     STEP(upd_finalize(n, prio_least));
+    STEP(fin_limiter(n));
     n->finalized = true;
     return BFHIP_OK;
 }
@@ -642,7 +659,8 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
         s.consumed_once = true;
     }
     // ---- emit; output delay and mute on the quantised block (block() copies it out behind this)
-    STEP(nupc_emit(n, opos, rawout_dev));
+    if (n->lim.on) STEP(nupc_limit_emit(n, opos, rawout_dev));
+    else STEP(nupc_emit(n, opos, rawout_dev));
     n->og.mirror.advance(L0);
     STEP(nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev));
     n->block++;
@@ -881,6 +899,80 @@ int bfhip_nupc_set_subdelay(bfhip_nupc *n, int io, int ch, int subdelay) {
 int bfhip_nupc_get_subdelay(const bfhip_nupc *n, int io, int ch) {
     if (!delay_channel_ok(n, io, ch)) return nfail(BFHIP_EINVAL, "nupc_get_subdelay: bad argument");
     return n->sd.val[io][ch];
+}
+
+// ---- look-ahead peak limiter (checks and the definition: limiter_host.h) ---------------------
+
+int bfhip_nupc_enable_limiter(bfhip_nupc *n, int lookahead_frames, double release_frames) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_enable_limiter after finalize");
+    if (n->lim.on) return nfail(BFHIP_ESTATE, "nupc_enable_limiter: the limiter is enabled already");
+    std::string why;
+    if (!limiter_check(lookahead_frames, release_frames, &why)) return nfail(BFHIP_EINVAL, "nupc_enable_limiter: " + why);
+    n->lim.on = true;
+    n->lim.D = lookahead_frames;
+    n->lim.release = release_frames;
+    n->lim.a = limiter_release_coef(release_frames);
+    n->lim.group_of.assign(n->n_out, -1);
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_add_limiter_group(bfhip_nupc *n, const int out_channels[], int n_ch, double threshold) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_add_limiter_group after finalize");
+    if (!n->lim.on) return nfail(BFHIP_ESTATE, "nupc_add_limiter_group: needs bfhip_nupc_enable_limiter first");
+    std::string why;
+    if (!limiter_check_group(n->lim.group_of, (int)n->lim.groups.size(), out_channels, n_ch, threshold, &why))
+        return nfail(BFHIP_EINVAL, "nupc_add_limiter_group: " + why);
+    NupcLimGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n_ch = n_ch;
+    const int index = (int)n->lim.groups.size();
+    for (int k = 0; k < n_ch; k++) { g.ch[k] = out_channels[k]; g.scale[k] = 1.0; n->lim.group_of[out_channels[k]] = index; }
+    n->lim.groups.push_back(g);
+    n->lim.thr.push_back(threshold);
+    return index;
+}
+
+int bfhip_nupc_set_limiter_threshold(bfhip_nupc *n, int group, double threshold) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (group < 0 || group >= (int)n->lim.groups.size()) return nfail(BFHIP_EINVAL, "nupc_set_limiter_threshold: bad group");
+    if (!limiter_threshold_ok(threshold))
+        return nfail(BFHIP_EINVAL, "nupc_set_limiter_threshold: the threshold must be > 0 (finite or +INFINITY)");
+    n->lim.thr[group] = threshold;                      // read by the next block call
+    return BFHIP_OK;
+}
+
+double bfhip_nupc_get_limiter_threshold(const bfhip_nupc *n, int group) {
+    if (!n || group < 0 || group >= (int)n->lim.groups.size()) { nfail(BFHIP_EINVAL, "nupc_get_limiter_threshold: bad argument"); return NAN; }
+    return n->lim.thr[group];
+}
+
+int bfhip_nupc_limiter_delay(const bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    return n->lim.on ? n->lim.D : 0;
+}
+
+int bfhip_nupc_get_limiter_reduction(bfhip_nupc *n, int group, double *min_gain) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!min_gain || group < 0 || group >= (int)n->lim.groups.size()) return nfail(BFHIP_EINVAL, "nupc_get_limiter_reduction: bad argument");
+    *min_gain = 1.0;
+    // nothing emitted since the previous call (or ever): the meter on the device is stale or fresh
+    if (!n->finalized || n->block == 0 || ((n->lim.meter_reset >> group) & 1u)) return BFHIP_OK;
+    OWNER(n);
+    NCHK(hipSetDevice(n->device));
+    NCHK(hipStreamSynchronize(n->stream));
+    // the parity the next block call reads
+    const double *cell = n->lim.d_state + ((size_t)group * 2 + (n->block & 1)) * n->lim.state_stride() + 2 * n->lim.D;
+    NCHK(hipMemcpy(min_gain, cell, sizeof(double), hipMemcpyDeviceToHost));
+    n->lim.meter_reset |= 1u << group;                  // travels with the next block call
+    return BFHIP_OK;
+}
+
+int bfhip_selftest_limiter_envelope(int lookahead_frames, double release_frames, long n, const double p[], double s_out[]) {
+    if (!limiter_envelope(lookahead_frames, release_frames, n, p, s_out))
+        return nfail(BFHIP_EINVAL, "selftest_limiter_envelope: bad argument");
+    return BFHIP_OK;
 }
 
 // the taps the device filters with (no HIP call: the bank is made of these)

@@ -290,6 +290,210 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
     }
 }
 
+// ---- look-ahead peak limiter (bfhip_nupc_enable_limiter; the definition is in include/bfhip_nupc.h and,
+// frame by frame, in limiter_host.h).  A convolver with a limiter launches these two kernels instead of
+// one of the emit kernels above, on the same grid: one workgroup per output channel.
+constexpr int kLimTile = 1024;     // frames of envelope per pass through LDS
+// LDS of the limit kernel: three float64 arrays [D + tile]
+static size_t nupc_lim_lds(int D, int tile) { return (size_t)3 * (D + tile) * sizeof(double); }
+
+// The front half of the emit step: the period's x_c -- emit_take times the frame's factor, behind the
+// sub-delay FIR if the channel has a filter, the very device functions of nupc_emit_kernel in their order --
+// into the channel's ring of R = D + L0 reals, frame t in cell t mod R (base = opos mod R).  The cells it
+// overwrites held frames opos - R .. opos - D - 1, which the previous period's limit kernel was the last
+// to need.  Ring cells of the accumulator are cleared by emit_take, the gain ramp advances here.
+template <typename T, bool SD>
+__global__ __launch_bounds__(256) void
+nupc_limit_stage_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsigned long long pos, int A, int n_out, int L0,
+                        long long rel0, int F, NupcGain *__restrict__ gain, T *__restrict__ ring, int R, int base,
+                        const NupcSd<T> sd) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sd_smem[];
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    GainFactor<T> sc;
+    sc.load(gain[ch], L0);
+    T *x = ring + (size_t)ch * R;
+    if (SD && sd.vals.v[ch] != -100)
+        sd_fir_period<T>(sd_smem, sd, ch, L0,
+                         [&](int n) { return emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n); },
+                         [&](int n, T y) { x[(base + n) % R] = y; });
+    else
+        for (int n = tid; n < L0; n += 256)
+            x[(base + n) % R] = emit_take(acc_old, acc_new, pos, A, n_out, ch, n, rel0, F) * sc.at(n);
+    __syncthreads();                                   // every thread has its copy of the record
+    if (tid == 0) gain_advance(gain + ch, L0);
+}
+
+// (A1, v1) o (A2, v2) = (A1 A2, max(A2 v1, v2)): the deficit d = 1 - e of the release recursion,
+// d[t] = max(1 - m[t], a d[t - 1]), composes with it, so a period's recursion is a prefix scan
+struct LimScan { double A, v; };
+__device__ __forceinline__ LimScan lim_op(const LimScan &p, const LimScan &c) { return {p.A * c.A, fmax(c.A * p.v, c.v)}; }
+
+// The group envelope of `cnt` frames (one tile), by the whole workgroup (256 threads, every thread calls).
+// On entry rr = [D history | cnt new] values of r and ee[0 .. D) the history of e; on return ee[D + n] is
+// e of the tile's frame n, and rr and ww hold scratch (the caller keeps r's history in registers).
+//   sliding minimum  m[n] = min rr[n .. n + D]: log-step doubling between rr and ww, k = floor(log2(D + 1))
+//       passes give the minima of 2^k cells, two of which cover the D + 1 (min is exact: any order, same bits)
+//   release          the scan above: each thread folds its `per` consecutive frames, the wave scans the
+//       threads' pairs with __shfl_up, the waves' totals go through LDS, and the thread walks its frames again
+//       from the deficit in front of it.  The carry into the tile is 1 - e of the frame before it.
+//   e[t] = min(m[t], 1 - d[t]): never above m[t], whatever the scan rounds.
+__device__ __forceinline__ void
+lim_envelope_tile(double *rr, double *ww, double *ee, int D, int cnt, double a) {
+    __shared__ LimScan wave_tot[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, total = D + cnt;
+    double *src = rr, *dst = ww;
+    int span = 1;
+    for (; 2 * span <= D + 1; span *= 2) {
+        for (int i = tid; i < total; i += 256) dst[i] = i >= span ? fmin(src[i], src[i - span]) : src[i];
+        __syncthreads();
+        double *t = src; src = dst; dst = t;
+    }
+    const int back = D + 1 - span;                     // the second window of `span` cells ends `back` cells earlier
+    const int per = (cnt + 255) / 256, n0 = tid * per, n1 = min(n0 + per, cnt);
+    LimScan mine = {1.0, 0.0};
+    for (int n = n0; n < n1; n++) {
+        const double m = fmin(src[D + n], src[D + n - back]);
+        dst[n] = m;                                    // each thread's own cells, read back below by itself only
+        mine = lim_op(mine, {a, 1.0 - m});
+    }
+    LimScan inc = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const LimScan p = {__shfl_up(inc.A, off), __shfl_up(inc.v, off)};
+        if (lane >= off) inc = lim_op(p, inc);
+    }
+    LimScan ex = {__shfl_up(inc.A, 1), __shfl_up(inc.v, 1)};
+    if (lane == 0) ex = {1.0, 0.0};
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    LimScan front = {1.0, 1.0 - ee[D - 1]};            // the deficit of the frame in front of the tile
+    for (int w = 0; w < wave; w++) front = lim_op(front, wave_tot[w]);
+    double d = lim_op(front, ex).v;
+    for (int n = n0; n < n1; n++) {
+        const double m = dst[n];
+        d = fmax(a * d, 1.0 - m);
+        ee[D + n] = fmin(m, 1.0 - d);
+    }
+    __syncthreads();
+}
+
+// The back half: the group's envelope for the period, y for this workgroup's channel, and the rest of the
+// emit step on y -- the Quantiser path or the dither chain (DITHER: through the stage buffer the dither
+// path already uses), overflow commit, the status hand-off of the n_out workgroups.  Every member of a
+// group computes the group's envelope itself from the members' staged x: the same code on the same
+// inputs gives the same bits, so the members agree without exchanging anything, and only the group's first
+// member writes the state, into the other parity.  A channel in no group takes x D frames late, unmultiplied.
+template <typename T, bool DITHER>
+__global__ __launch_bounds__(256) void
+nupc_limit_emit_kernel(const T *__restrict__ ring, int R, int base, int D, int L0, int tile, double a,
+                       const NupcLimGroup *__restrict__ groups, const int *__restrict__ group_of,
+                       double *__restrict__ state, int parity, const NupcLimThr thr, unsigned int meter_reset,
+                       const DevFormat *__restrict__ fmt, DevOverflow *__restrict__ over, uint8_t *__restrict__ raw,
+                       double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
+                       int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
+                       DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
+                       const T *__restrict__ randmap /* index -256..255 (centre pointer) */) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lim_smem[];
+    __shared__ T rmap[DITHER ? 512 : 1];
+    __shared__ double red_min[4], g_ceil[kLimGroupMax];
+    __shared__ int g_ch[kLimGroupMax];
+    const int ch = blockIdx.x, tid = threadIdx.x;
+    const DevFormat f = fmt[ch];
+    const int slot = DITHER ? dslot[ch] : -1;
+    const int g = group_of[ch];
+    const T *x = ring + (size_t)ch * R;
+    uint8_t *out = raw + f.byte_offset;
+    const size_t stride = (size_t)f.sample_spacing * f.bytes;
+    T *staged = slot < 0 ? nullptr : stage + (size_t)slot * L0;
+    DevOverflow of;
+    Quantiser<T> qz;
+    if (slot < 0) { of = over[ch]; qz.init(f, of, safety_limit); }
+    // frame n of the period leaves as x[n - D] (cell base + n + L0 mod R) times s
+    auto put = [&](int n, T y) {
+        if (slot < 0) qz.put(y, out + (size_t)n * stride);
+        else staged[n] = y;
+    };
+    if (g < 0) {
+        for (int n = tid; n < L0; n += 256) put(n, x[(base + n + L0) % R]);
+    } else {
+        // the group's row and its members' ceilings thr_g / scale_c through LDS: indexed by a loop counter
+        const NupcLimGroup *grp = groups + g;
+        const int n_ch = grp->n_ch;
+        if (tid < n_ch) { g_ch[tid] = grp->ch[tid]; g_ceil[tid] = thr.v[g] / grp->scale[tid]; }
+        const size_t ss = (size_t)2 * D + 1;
+        const double *st_in = state + ((size_t)g * 2 + parity) * ss;
+        double *st_out = state + ((size_t)g * 2 + (1 - parity)) * ss;
+        double *rr = reinterpret_cast<double *>(lim_smem), *ww = rr + D + tile, *ee = ww + D + tile;
+        for (int i = tid; i < D; i += 256) { rr[i] = st_in[i]; ee[i] = st_in[D + i]; }
+        __syncthreads();
+        double s_min = 1.0;
+        for (int t0 = 0; t0 < L0; t0 += tile) {
+            const int cnt = min(tile, L0 - t0);
+            for (int n = tid; n < cnt; n += 256) {
+                double p = 0.0;
+                for (int k = 0; k < n_ch; k++) {
+                    const double v = (double)ring[(size_t)g_ch[k] * R + (base + t0 + n) % R];
+                    if (isfinite(v)) p = fmax(p, fabs(v) / g_ceil[k]);
+                }
+                rr[D + n] = p > 1.0 ? 1.0 / p : 1.0;
+            }
+            __syncthreads();
+            double keep_r[kLimLookaheadMax / 256], keep_e[kLimLookaheadMax / 256];
+#pragma unroll
+            for (int i = 0; i < kLimLookaheadMax / 256; i++) { const int n = tid + i * 256; if (n < D) keep_r[i] = rr[cnt + n]; }
+            __syncthreads();
+            lim_envelope_tile(rr, ww, ee, D, cnt, a);
+            const double w1 = (double)(D + 1);
+            for (int n = tid; n < cnt; n += 256) {
+                double sum = 0.0;
+                for (int j = 0; j <= D; j++) sum += ee[D + n - j];
+                const double s = sum / w1;
+                s_min = fmin(s_min, s);
+                put(t0 + n, x[(base + t0 + n + L0) % R] * (T)s);
+            }
+            // the histories moved down: the last D values of r and of e in front of the next tile
+#pragma unroll
+            for (int i = 0; i < kLimLookaheadMax / 256; i++) { const int n = tid + i * 256; if (n < D) keep_e[i] = ee[cnt + n]; }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < kLimLookaheadMax / 256; i++) {
+                const int n = tid + i * 256;
+                if (n < D) { rr[n] = keep_r[i]; ee[n] = keep_e[i]; }
+            }
+            __syncthreads();
+        }
+        if (g_ch[0] == ch) {                          // the group's first member keeps its state
+            for (int i = tid; i < D; i += 256) { st_out[i] = rr[i]; st_out[D + i] = ee[i]; }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s_min = fmin(s_min, __shfl_down(s_min, off));
+            if ((tid & 63) == 0) red_min[tid >> 6] = s_min;
+            __syncthreads();
+            if (tid == 0) {
+                const double before = (meter_reset >> g) & 1u ? 1.0 : st_in[2 * D];
+                st_out[2 * D] = fmin(fmin(before, fmin(red_min[0], red_min[1])), fmin(red_min[2], red_min[3]));
+            }
+        }
+    }
+    if (slot < 0) {
+        qz.reduce(tid, 256);
+        if (tid == 0) {
+            qz.commit(of);
+            over[ch] = of;
+            if (qz.st) atomicOr(status, qz.st);
+            emit_hand_off(status, arrive, host_status);
+        }
+        return;
+    }
+    if constexpr (DITHER) {
+        for (int i = tid; i < 512; i += 256) rmap[i] = randmap[i - 256];
+        __syncthreads();              // the staged samples are visible to wave 0 (same workgroup)
+        if (tid < 64) {
+            dither_chain<T>(staged, dstate + slot, table, table_size, rmap, f, over + ch, raw, L0, safety_limit, status, tid);
+            if (tid == 0) emit_hand_off(status, arrive, host_status);
+        }
+    }
+}
+
 // ---- per-channel integer delay and mute on the raw I/O blocks: the device half of the delay machine
 // (the job, NupcDelayJob, and the host half that makes it, NupcDelay, are in nupc_sched.h)
 constexpr int kDelayJobs = 32;     // jobs per launch (2048 bytes of kernel arguments)
@@ -477,6 +681,39 @@ int nupc_emit(bfhip_nupc *n, unsigned long long opos, void *rawout_dev) {
                                (uint8_t *)rawout_dev, n->safety_limit, n->st.d_status, n->st.d_arrive, n->st.h_status, sd);
     });
     NCHK(hipGetLastError());
+    return BFHIP_OK;
+}
+
+// the emit step of a convolver with a limiter: the stage launch and the limit-and-emit launch, this period's
+// thresholds and the meters' reset bits as kernel arguments
+int nupc_limit_emit(bfhip_nupc *n, unsigned long long opos, void *rawout_dev) {
+    const Switcher &sw = n->sets.sched;
+    NupcLimiter &lm = n->lim;
+    void *acc_old = n->ring(sw.cur), *acc_new = sw.two_rings() ? n->ring(1 - sw.cur) : nullptr;
+    const long long rel0 = sw.rel0(opos);
+    const int L0 = n->L0(), R = lm.D + L0, base = (int)(opos % (unsigned long long)R), tile = std::min(L0, kLimTile);
+    NupcLimThr thr;
+    for (int g = 0; g < kLimGroupsMax; g++) thr.v[g] = g < (int)lm.thr.size() ? lm.thr[g] : 1.0;
+    nupc_dispatch(n, [&](auto t, auto sd_side) {
+        using T = decltype(t);
+        constexpr bool SD = decltype(sd_side)::value;
+        hipLaunchKernelGGL((nupc_limit_stage_kernel<T, SD>), dim3(n->n_out), dim3(256), SD ? nupc_sd_smem(n, 1) : 0, n->stream,
+                           (T *)acc_old, (T *)acc_new, opos, n->A, n->n_out, L0, rel0, sw.sw_F, n->og.d, (T *)lm.d_ring, R,
+                           base, nupc_sd_args<T>(n, 1));
+        auto back = [&](auto dith) {
+            constexpr bool DITHER = decltype(dith)::value;
+            hipLaunchKernelGGL((nupc_limit_emit_kernel<T, DITHER>), dim3(n->n_out), dim3(256), nupc_lim_lds(lm.D, tile),
+                               n->stream, (const T *)lm.d_ring, R, base, lm.D, L0, tile, lm.a, lm.d_groups, lm.d_group_of,
+                               lm.d_state, (int)(n->block & 1), thr, lm.meter_reset, n->io.d_fmt[1], n->st.d_over,
+                               (uint8_t *)rawout_dev, n->safety_limit, n->st.d_status, n->st.d_arrive, n->st.h_status,
+                               n->dither.d_slot, (T *)n->dither.d_stage, (DitherState<T> *)n->dither.d_state,
+                               n->dither.d_table, (int)n->dither.table.size(),
+                               DITHER ? (const T *)n->dither.d_randmap + 256 : nullptr);
+        };
+        if (!n->dither.ch.empty()) back(std::true_type()); else back(std::false_type());
+    });
+    NCHK(hipGetLastError());
+    lm.meter_reset = 0;
     return BFHIP_OK;
 }
 

@@ -689,6 +689,78 @@ int bfhip_nupc_get_subdelay(const bfhip_nupc *n, int io, int channel);
    (-100, 100); returns the tap count or a negative error.  Makes no HIP call. */
 int bfhip_selftest_subdelay_filter(int sdf_length, int subdelay, int realsize, void *out);
 
+/* ---- linked look-ahead peak limiter on the outputs ---------------------------------------------
+ * An extension (the reference's only answers to an over-range sample are the clip-and-count of
+ * real2raw.h and safety_limit, which ends the program): a brick-wall peak
+ * limiter inside the emit step, behind everything that can change level and in front of dither and
+ * quantisation, linked across the channels of a group, wholly on the device.
+ *
+ * Place in the chain.  Output side: cross-fade blend, output gain(frame) / scale, sub-delay FIR,
+ * LIMITER, dither / quantise with overflow accounting, integer delay line, mute.  Call x_c[t] the
+ * real of output channel c, frame t, that a convolver without a limiter hands to its quantiser or
+ * dither chain (in output units: full scale is 1 / fmt.scale); it is computed by the same device
+ * functions in the same order, so it has the same bits.  With a limiter, frame t is quantised or
+ * dithered from
+ *     y_c[t] = x_c[t - D] * (T) s_g[t]     c in group g   (product in the convolver's real type T)
+ *     y_c[t] = x_c[t - D]                  c in no group  (no multiply: the same bits, D frames later)
+ *     x_c[t < 0] = 0
+ * D is the look-ahead: every output gets D frames of extra delay, grouped or not, so channels stay
+ * aligned.  The overflow structs, status bits, safety_limit and the dither input all see y.  A
+ * non-finite x contributes nothing to the envelope; it reaches the quantiser as before and is
+ * reported as before.
+ *
+ * Envelope, per group g, float64 for both precisions, frames counted as in the switch section:
+ *     ceil_c = thr_g / fmt_c.scale       thr_g: the threshold in force at the block call that receives frame t
+ *     p[t]   = max over c in g of |x_c[t]| / ceil_c      (non-finite x_c[t]: 0)
+ *     r[t]   = 1 / p[t] if p[t] > 1, else 1              r[t < 0] = 1
+ *     m[t]   = min over 0 <= j <= D of r[t - j]
+ *     e[t]   = min(m[t], 1 - a (1 - e[t - 1]))           e[t < 0] = 1, a = exp(-1 / release_frames), release_frames == 0: a = 0
+ *     s[t]   = (sum over 0 <= j <= D of e[t - j]) / (D + 1)      (a division, not a multiplication by a reciprocal)
+ * the sliding-minimum + box-smoothed design: instant attack on the look-ahead minimum, exponential
+ * release, then a (D + 1)-frame box.  Two properties follow.
+ *   Ceiling.  Every e[t - j], 0 <= j <= D, is <= m[t - j] <= r[t - D], so s[t] <= r[t - D] up to the
+ *   rounding of the sum and |y_c[t]| <= ceil_c (1 + (D + 4) eps_T).
+ *   Idle exactness.  If no p exceeded 1 in the window every term is exactly 1, the sum exactly D + 1
+ *   and s[t] == 1.0: y_c[t] has the bits of x_c[t - D].
+ * The device evaluates the release recursion as a prefix scan of the deficit 1 - e and clamps the
+ * result to m[t]; it differs from the frame-by-frame evaluation (bfhip_selftest_limiter_envelope) by
+ * one rounding per step, which the recursion's decay bounds at about release_frames ulp of 1.0.
+ *
+ * - A threshold of 1.0 on an integer output still counts a sample of exactly +full scale as an
+ *   overflow, because real2raw's range ends at 2^(b-1) - 1.
+ * - bfhip_nupc_latency() stays L0; bfhip_nupc_limiter_delay() is what the limiter adds.
+ * - Output gain, gain ramps, per-filter gains, switches and cross-fades act in front of the limiter:
+ *   a gain raised at run time is caught.
+ * - The integer delay line and the mute act behind it, on the raw block.
+ * - A limiter with no group is legal: a pure D-frame delay of every output.
+ * - A convolver that never enables it allocates, launches and computes exactly as before.
+ * State (per output a ring of D + L0 reals; per group the last D values of r and of e and the
+ * meter's minimum, float64; the group table) lives on the device and never crosses to the host per
+ * period.  Two launches per period instead of the one emit launch; no host wait, no upload and no
+ * allocation on the audio path.  Cost: DESIGN.md section 4.
+ */
+#define BFHIP_NUPC_LIMIT_LOOKAHEAD_MAX 1024
+#define BFHIP_NUPC_LIMIT_GROUPS_MAX    32
+#define BFHIP_NUPC_LIMIT_GROUP_MAX     8      /* channels per group */
+/* before finalize (BFHIP_ESTATE after; twice: BFHIP_ESTATE).  1 <= lookahead_frames <= ..._LOOKAHEAD_MAX, any relation
+   to L0; release_frames finite, 0 or >= 1 and <= 1e7 (BFHIP_EINVAL). */
+int bfhip_nupc_enable_limiter(bfhip_nupc *n, int lookahead_frames, double release_frames);
+/* before finalize, after enable_limiter (BFHIP_ESTATE).  1 <= n_ch <= ..._GROUP_MAX, channels in range, pairwise
+   distinct and in no other group; threshold > 0, finite or +INFINITY (a group that never limits: r = 1), linear
+   fraction of full scale (float formats: of 1.0) (BFHIP_EINVAL, the message names the channel).  Returns the group index. */
+int bfhip_nupc_add_limiter_group(bfhip_nupc *n, const int out_channels[], int n_ch, double threshold);
+/* any time after add_limiter_group: in force for the frames x[t] of the next block call on (they leave D frames
+   later).  Travels as a kernel argument: no upload, no host wait. */
+int bfhip_nupc_set_limiter_threshold(bfhip_nupc *n, int group, double threshold);
+double bfhip_nupc_get_limiter_threshold(const bfhip_nupc *n, int group);      /* NaN on a bad handle / group */
+int bfhip_nupc_limiter_delay(const bfhip_nupc *n);                            /* D, 0 without a limiter; BFHIP_EINVAL on a bad handle */
+/* min of s_g over the frames emitted since the previous call for this group (1.0 if none), then reset; waits for
+   the main stream like bfhip_nupc_get_overflow: NOT for the audio thread */
+int bfhip_nupc_get_limiter_reduction(bfhip_nupc *n, int group, double *min_gain);
+/* host only, no HIP call: s[0..n) of the definition above from p[0..n), fresh state.  For tests and as the
+   definition in code. */
+int bfhip_selftest_limiter_envelope(int lookahead_frames, double release_frames, long n, const double p[], double s_out[]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ uniform engine's block time and I/O delay for the same filters.
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
                                    | --eq-base [--eq-mode minimum] [--eq-taps R] | --eq-group [--eq-mode minimum] [--eq-taps R]]
-                                  [--biquads [--biquad-phase own|linear]]
+                                  [--biquads [--biquad-phase own|linear]] [--limiter [--lookahead D]]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -42,6 +42,10 @@ high shelf and 30 peaks, +-12 dB, seeded; bfhip_nupc_render_biquads*: the sectio
 --biquad-phase linear) and reports what those options report.  --gain-ramp sets an
 output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs a new target (seeded,
 0 .. 2) every 300 periods; it reports step_ms split into periods with a ramp in progress and without.
+--limiter enables the look-ahead peak limiter (bfhip_nupc_enable_limiter: look-ahead 64 frames or --lookahead, release
+4800 frames) with one group over both outputs at a threshold of 0.5; the first third of the run is 12x
+louder (output peaks near 1.0), so the group limits there and idles once the filters' tail has decayed; it
+reports the smallest gain the meter saw.
 --dump-output writes the raw output of all timed
 and untimed periods to FILE (to compare two builds byte for byte).  --layout planar declares both
 sides as one non-interleaved device (a plane per channel, bfhip_nupc_set_buffer_bytes): the input
@@ -78,6 +82,8 @@ def main():
     ap.add_argument("--eq-taps", type=int)
     ap.add_argument("--biquads", action="store_true")
     ap.add_argument("--biquad-phase", choices=["own", "linear"], default="own")
+    ap.add_argument("--limiter", action="store_true")
+    ap.add_argument("--lookahead", type=int, default=64)
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
@@ -129,6 +135,9 @@ def main():
             nu.reserve_eq_base_long()
         if a.eq_group:
             nu.reserve_eq_group(4)
+    if a.limiter:
+        nu.enable_limiter(a.lookahead, 4800.0)
+        nu.add_limiter_group([0, 1], 0.5)
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -190,6 +199,7 @@ def main():
     x = rng.standard_normal((8, L0, 2)) * 0.1
     if a.layout == "planar":
         x = np.ascontiguousarray(x.transpose(0, 2, 1))             # [2][L0]: a plane per channel
+    x_loud, loud_until = x * 12.0, (steps + 256) // 3 if a.limiter else 0      # drives the group into limiting
     import gc
     gc.disable()                       # the timed loop allocates one small array per period
     ts = []
@@ -271,7 +281,7 @@ def main():
             flying = flying or started_at is not None
         in_flight.append(flying)
         t0 = time.perf_counter()
-        st, raw = nu.block(x[s & 7])
+        st, raw = nu.block((x_loud if s < loud_until else x)[s & 7])
         ts.append(time.perf_counter() - t0)
         assert st == 0
         if a.dump_output:
@@ -310,6 +320,8 @@ def main():
                     "render_eq_sync_ms": {str(k): dist([v for n_taps, v in render_ms if n_taps == k][1:])
                                           for k in sync_taps} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
+        "limiter": {"lookahead_frames": a.lookahead, "release_frames": 4800, "groups": [[0, 1]], "threshold": 0.5, "loud_periods": loud_until,
+                    "min_gain": round(nu.limiter_reduction(0), 4)} if a.limiter else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
