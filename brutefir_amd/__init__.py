@@ -275,6 +275,11 @@ def lib():
     L.bfhip_nupc_limiter_delay.argtypes = [vp]
     L.bfhip_nupc_get_limiter_reduction.argtypes = [vp, ci, dp]
     L.bfhip_selftest_limiter_envelope.argtypes = [ci, cd, C.c_long, dp, dp]
+    L.bfhip_nupc_set_limiter_detector.argtypes = [vp, ci]
+    L.bfhip_nupc_get_limiter_detector.argtypes = [vp]
+    L.bfhip_nupc_get_limiter_true_peak.argtypes = [vp, ci, dp]
+    L.bfhip_selftest_truepeak_filter.argtypes = [dp]
+    L.bfhip_selftest_truepeak.argtypes = [C.c_long, dp, dp]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -1032,6 +1037,22 @@ class Nupc:
         self._chk(lib().bfhip_nupc_get_limiter_reduction(self.h, group, C.byref(v)))
         return v.value
 
+    # true-peak detection for the limiter (include/bfhip_nupc.h)
+    def set_limiter_detector(self, detector):
+        """before finalize, after enable_limiter: LIMIT_SAMPLE_PEAK (the default) or LIMIT_TRUE_PEAK, which
+        needs a look-ahead of at least 2 * LIMIT_TP_HALF frames"""
+        self._chk(lib().bfhip_nupc_set_limiter_detector(self.h, detector))
+
+    def limiter_detector(self):
+        return self._chk(lib().bfhip_nupc_get_limiter_detector(self.h))
+
+    def limiter_true_peak(self, group):
+        """true-peak mode: the largest inter-sample peak of the group's channels detected since the previous
+        call, as a fraction of full scale (0.0 if none); waits for the main stream"""
+        v = C.c_double(0.0)
+        self._chk(lib().bfhip_nupc_get_limiter_true_peak(self.h, group, C.byref(v)))
+        return v.value
+
 
 def limiter_envelope(lookahead_frames, release_frames, p):
     """s of the limiter's definition from p, fresh state (bfhip_selftest_limiter_envelope: host only,
@@ -1044,6 +1065,30 @@ def limiter_envelope(lookahead_frames, release_frames, p):
     if r < 0:
         raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
     return s
+
+
+LIMIT_SAMPLE_PEAK, LIMIT_TRUE_PEAK, LIMIT_TP_HALF = 0, 1, 12
+
+
+def truepeak_filter():
+    """the true-peak interpolator's taps g[q - 1][k], q = 1 .. 3 (bfhip_selftest_truepeak_filter: host only)"""
+    g = np.zeros((3, 2 * LIMIT_TP_HALF), np.float64)
+    r = lib().bfhip_selftest_truepeak_filter(g.ctypes.data_as(C.POINTER(C.c_double)))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return g
+
+
+def truepeak(x):
+    """max over the four phases of |u_q[t]| for one channel, fresh history (bfhip_selftest_truepeak: host only,
+    needs no device)"""
+    x = np.ascontiguousarray(x, np.float64)
+    tp = np.zeros(len(x), np.float64)
+    dp = C.POINTER(C.c_double)
+    r = lib().bfhip_selftest_truepeak(len(x), x.ctypes.data_as(dp), tp.ctypes.data_as(dp))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return tp
 
 
 def device_count():

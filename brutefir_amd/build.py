@@ -20,7 +20,8 @@ LIB = os.path.join(HERE, "libbfhip.so")
 INC = os.path.join(HERE, "..", "include")
 PUBLIC = [os.path.join("..", "..", "include", h) for h in ("bfhip.h", "bfhip_convolver.h", "bfhip_nupc.h")]
 DEVICE = ["kernels.h", "fft_lds.h", "fft_wave.h", "bigfft.h"] + PUBLIC
-NUPC = DEVICE + ["nupc.h", "nupc_sched.h", "alloc.h", "eq_render.h", "eq_minphase.h", "eq_apply.h", "limiter_host.h"]
+NUPC = DEVICE + ["nupc.h", "nupc_sched.h", "alloc.h", "eq_render.h", "eq_minphase.h", "eq_apply.h", "limiter_host.h",
+               "truepeak_host.h"]
 # translation unit -> what it includes
 UNITS = {
     "bfhip.hip": DEVICE + ["engine.h", "channels.h", "passes.h", "conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],

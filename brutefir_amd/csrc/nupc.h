@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "limiter_host.h"
 #include "nupc_sched.h"
+#include "truepeak_host.h"
 
 using namespace bfhip;
 using namespace nupc_sched;
@@ -180,10 +181,18 @@ struct NupcLimiter {
     void *d_ring = nullptr;                // [n_out][D + L0] reals: x_c, frame t in cell t mod (D + L0)
     // [group][parity][2 D + 1] float64: the last D values of r, of e (e[t-1] is the last), and the meter's
     // running minimum.  Period k reads parity k & 1 and the group's first member writes the other one.
+    // (True-peak detection: De in place of D and one more cell, see state_stride.)
     double *d_state = nullptr;
     NupcLimGroup *d_groups = nullptr;
     int *d_group_of = nullptr;             // [n_out]
-    size_t state_stride() const { return (size_t)2 * D + 1; }
+    // true-peak detection (bfhip_nupc_set_limiter_detector): the envelope looks ahead De = D - H frames, and
+    // the state keeps De values each of r and e, the meter's minimum and the true-peak meter's maximum
+    int detector = kTpSamplePeak;
+    TruepeakTaps taps = {};                // filled when true-peak mode is selected: a kernel argument
+    unsigned int tp_reset = 0;             // bit g: the next block call starts group g's true-peak meter afresh
+    bool true_peak() const { return detector == kTpTruePeak; }
+    int De() const { return truepeak_envelope_lookahead(detector, D); }
+    size_t state_stride() const { return (size_t)2 * De() + (true_peak() ? 2 : 1); }
 };
 
 }  // namespace nupc_host

@@ -555,7 +555,9 @@ int fin_limiter(bfhip_nupc *n) {
     STEP(dev_copy(&lm.d_group_of, lm.group_of));
     if (lm.groups.empty()) return BFHIP_OK;              // a pure delay of every output
     STEP(dev_copy(&lm.d_groups, lm.groups));
-    const std::vector<double> fresh(lm.groups.size() * 2 * lm.state_stride(), 1.0);  // r = e = 1 before frame 0
+    std::vector<double> fresh(lm.groups.size() * 2 * lm.state_stride(), 1.0);        // r = e = 1 before frame 0
+    if (lm.true_peak())                                  // and nothing detected yet
+        for (size_t row = 0; row < lm.groups.size() * 2; row++) fresh[(row + 1) * lm.state_stride() - 1] = 0.0;
     STEP(dev_copy(&lm.d_state, fresh));
     return BFHIP_OK;
 }
@@ -963,9 +965,57 @@ int bfhip_nupc_get_limiter_reduction(bfhip_nupc *n, int group, double *min_gain)
     NCHK(hipSetDevice(n->device));
     NCHK(hipStreamSynchronize(n->stream));
     // the parity the next block call reads
-    const double *cell = n->lim.d_state + ((size_t)group * 2 + (n->block & 1)) * n->lim.state_stride() + 2 * n->lim.D;
+    const double *cell = n->lim.d_state + ((size_t)group * 2 + (n->block & 1)) * n->lim.state_stride() + 2 * n->lim.De();
     NCHK(hipMemcpy(min_gain, cell, sizeof(double), hipMemcpyDeviceToHost));
     n->lim.meter_reset |= 1u << group;                  // travels with the next block call
+    return BFHIP_OK;
+}
+
+// ---- true-peak detection for the limiter (taps, checks and the definition: truepeak_host.h) ----
+
+int bfhip_nupc_set_limiter_detector(bfhip_nupc *n, int detector) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_set_limiter_detector after finalize");
+    if (!n->lim.on) return nfail(BFHIP_ESTATE, "nupc_set_limiter_detector: needs bfhip_nupc_enable_limiter first");
+    std::string why;
+    if (!truepeak_check(detector, n->lim.D, &why)) return nfail(BFHIP_EINVAL, "nupc_set_limiter_detector: " + why);
+    n->lim.detector = detector;
+    if (n->lim.true_peak()) truepeak_filter(&n->lim.taps);
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_get_limiter_detector(const bfhip_nupc *n) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    return n->lim.detector;
+}
+
+int bfhip_nupc_get_limiter_true_peak(bfhip_nupc *n, int group, double *max_peak) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!max_peak || group < 0 || group >= (int)n->lim.groups.size()) return nfail(BFHIP_EINVAL, "nupc_get_limiter_true_peak: bad argument");
+    if (!n->lim.true_peak()) return nfail(BFHIP_ESTATE, "nupc_get_limiter_true_peak: the detector is BFHIP_NUPC_LIMIT_SAMPLE_PEAK");
+    *max_peak = 0.0;
+    // nothing detected since the previous call (or ever): the meter on the device is stale or fresh
+    if (!n->finalized || n->block == 0 || ((n->lim.tp_reset >> group) & 1u)) return BFHIP_OK;
+    OWNER(n);
+    NCHK(hipSetDevice(n->device));
+    NCHK(hipStreamSynchronize(n->stream));
+    // the parity the next block call reads
+    const double *cell = n->lim.d_state + ((size_t)group * 2 + (n->block & 1)) * n->lim.state_stride() + 2 * n->lim.De() + 1;
+    NCHK(hipMemcpy(max_peak, cell, sizeof(double), hipMemcpyDeviceToHost));
+    n->lim.tp_reset |= 1u << group;                     // travels with the next block call
+    return BFHIP_OK;
+}
+
+int bfhip_selftest_truepeak_filter(double g_out[]) {
+    if (!g_out) return nfail(BFHIP_EINVAL, "selftest_truepeak_filter: bad argument");
+    TruepeakTaps taps;
+    truepeak_filter(&taps);
+    memcpy(g_out, taps.g, sizeof(taps.g));
+    return BFHIP_OK;
+}
+
+int bfhip_selftest_truepeak(long n, const double x[], double tp_out[]) {
+    if (!truepeak_detect(n, x, tp_out)) return nfail(BFHIP_EINVAL, "selftest_truepeak: bad argument");
     return BFHIP_OK;
 }
 

@@ -294,8 +294,15 @@ nupc_emit_dither_kernel(T *__restrict__ acc_old, T *__restrict__ acc_new, unsign
 // frame by frame, in limiter_host.h).  A convolver with a limiter launches these two kernels instead of
 // one of the emit kernels above, on the same grid: one workgroup per output channel.
 constexpr int kLimTile = 1024;     // frames of envelope per pass through LDS
-// LDS of the limit kernel: three float64 arrays [D + tile]
+// LDS of the limit kernel: three float64 arrays [D + tile], D the envelope's look-ahead
 static size_t nupc_lim_lds(int D, int tile) { return (size_t)3 * (D + tile) * sizeof(double); }
+// and, under true-peak detection, the staging window of one member: the tile and the 2 H - 1 frames before it
+static size_t nupc_lim_tp_lds(int De, int tile) { return nupc_lim_lds(De, tile) + (size_t)(tile + kTpTaps - 1) * sizeof(double); }
+
+// What true-peak detection adds to the limit kernel's arguments: the interpolator's taps (truepeak_host.h)
+// and the reset bits of the true-peak meters.  The sample-peak instantiations take an empty placeholder.
+template <bool TP> struct NupcLimTp { int none; };
+template <> struct NupcLimTp<true> { TruepeakTaps taps; unsigned int tp_reset; };
 
 // The front half of the emit step: the period's x_c -- emit_take times the frame's factor, behind the
 // sub-delay FIR if the channel has a filter, the very device functions of nupc_emit_kernel in their order --
@@ -383,7 +390,16 @@ lim_envelope_tile(double *rr, double *ww, double *ee, int D, int cnt, double a) 
 // group computes the group's envelope itself from the members' staged x: the same code on the same
 // inputs gives the same bits, so the members agree without exchanging anything, and only the group's first
 // member writes the state, into the other parity.  A channel in no group takes x D frames late, unmultiplied.
-template <typename T, bool DITHER>
+// D is the envelope's look-ahead; the delay of x is in the ring's geometry (R - L0 frames).
+// TP (bfhip_nupc_set_limiter_detector, TRUE_PEAK): p is the peak over the four phases of the interpolator
+// instead of the sample's.  The ring holds frames opos - (R - L0) .. opos + L0 - 1 and the detector of frame
+// opos reads back to opos - (2 H - 1), inside it since R - L0 >= 2 H.  Per tile and member in turn, the member's
+// cnt + 2 H - 1 cells are staged into LDS as float64 (a non-finite one as 0; the window is shorter than the
+// ring, so it wraps at most once: two runs); each thread forms the three 24-tap sums of its frames, k
+// ascending, from consecutive doubles (consecutive lanes, consecutive cells: no bank conflict), takes phase 0
+// from cell n + H - 1, and folds the peak over its ceiling into rr[D + n], which no other thread touches.  D is
+// then the look-ahead less H, and the state gains the true-peak meter's maximum behind the reduction meter.
+template <typename T, bool DITHER, bool TP = false>
 __global__ __launch_bounds__(256) void
 nupc_limit_emit_kernel(const T *__restrict__ ring, int R, int base, int D, int L0, int tile, double a,
                        const NupcLimGroup *__restrict__ groups, const int *__restrict__ group_of,
@@ -392,10 +408,11 @@ nupc_limit_emit_kernel(const T *__restrict__ ring, int R, int base, int D, int L
                        double safety_limit, int *__restrict__ status, unsigned int *__restrict__ arrive,
                        int *__restrict__ host_status, const int *__restrict__ dslot, T *__restrict__ stage,
                        DitherState<T> *__restrict__ dstate, const int8_t *__restrict__ table, int table_size,
-                       const T *__restrict__ randmap /* index -256..255 (centre pointer) */) {
+                       const T *__restrict__ randmap /* index -256..255 (centre pointer) */, const NupcLimTp<TP> tp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lim_smem[];
     __shared__ T rmap[DITHER ? 512 : 1];
     __shared__ double red_min[4], g_ceil[kLimGroupMax];
+    __shared__ double red_max[TP ? 4 : 1], g_scale[TP ? kLimGroupMax : 1];
     __shared__ int g_ch[kLimGroupMax];
     const int ch = blockIdx.x, tid = threadIdx.x;
     const DevFormat f = fmt[ch];
@@ -419,23 +436,56 @@ nupc_limit_emit_kernel(const T *__restrict__ ring, int R, int base, int D, int L
         // the group's row and its members' ceilings thr_g / scale_c through LDS: indexed by a loop counter
         const NupcLimGroup *grp = groups + g;
         const int n_ch = grp->n_ch;
-        if (tid < n_ch) { g_ch[tid] = grp->ch[tid]; g_ceil[tid] = thr.v[g] / grp->scale[tid]; }
-        const size_t ss = (size_t)2 * D + 1;
+        if (tid < n_ch) {
+            g_ch[tid] = grp->ch[tid];
+            g_ceil[tid] = thr.v[g] / grp->scale[tid];
+            if constexpr (TP) g_scale[tid] = grp->scale[tid];
+        }
+        const size_t ss = (size_t)2 * D + (TP ? 2 : 1);
         const double *st_in = state + ((size_t)g * 2 + parity) * ss;
         double *st_out = state + ((size_t)g * 2 + (1 - parity)) * ss;
         double *rr = reinterpret_cast<double *>(lim_smem), *ww = rr + D + tile, *ee = ww + D + tile;
         for (int i = tid; i < D; i += 256) { rr[i] = st_in[i]; ee[i] = st_in[D + i]; }
         __syncthreads();
         double s_min = 1.0;
+        [[maybe_unused]] double tp_max = 0.0;
         for (int t0 = 0; t0 < L0; t0 += tile) {
             const int cnt = min(tile, L0 - t0);
-            for (int n = tid; n < cnt; n += 256) {
-                double p = 0.0;
+            if constexpr (TP) {
+                double *win = ee + D + tile;                    // [tile + 2 H - 1]: frames t0 - (2 H - 1) .. t0 + cnt - 1
+                const int len = cnt + kTpTaps - 1, start = (base + t0 - (kTpTaps - 1) + R) % R, first = min(len, R - start);
+                for (int n = tid; n < cnt; n += 256) rr[D + n] = 0.0;
                 for (int k = 0; k < n_ch; k++) {
-                    const double v = (double)ring[(size_t)g_ch[k] * R + (base + t0 + n) % R];
-                    if (isfinite(v)) p = fmax(p, fabs(v) / g_ceil[k]);
+                    const T *xk = ring + (size_t)g_ch[k] * R;
+                    for (int i = tid; i < first; i += 256) { const double v = (double)xk[start + i]; win[i] = isfinite(v) ? v : 0.0; }
+                    for (int i = first + tid; i < len; i += 256) { const double v = (double)xk[i - first]; win[i] = isfinite(v) ? v : 0.0; }
+                    __syncthreads();
+                    const double ceil_k = g_ceil[k], scale_k = g_scale[k];
+                    for (int n = tid; n < cnt; n += 256) {
+                        const double *w = win + n + kTpTaps - 1;            // frame t0 + n; frame t0 + n - j is w[-j]
+                        double peak = fabs(w[-kTpHalf]);
+#pragma unroll
+                        for (int q = 0; q < kTpPhases; q++) {
+                            double u = 0.0;
+#pragma unroll
+                            for (int j = 0; j < kTpTaps; j++) u += tp.taps.g[q][j] * w[-j];
+                            peak = fmax(peak, fabs(u));
+                        }
+                        tp_max = fmax(tp_max, peak * scale_k);
+                        rr[D + n] = fmax(rr[D + n], peak / ceil_k);
+                    }
+                    __syncthreads();                            // the window is free for the next member
                 }
-                rr[D + n] = p > 1.0 ? 1.0 / p : 1.0;
+                for (int n = tid; n < cnt; n += 256) { const double p = rr[D + n]; rr[D + n] = p > 1.0 ? 1.0 / p : 1.0; }
+            } else {
+                for (int n = tid; n < cnt; n += 256) {
+                    double p = 0.0;
+                    for (int k = 0; k < n_ch; k++) {
+                        const double v = (double)ring[(size_t)g_ch[k] * R + (base + t0 + n) % R];
+                        if (isfinite(v)) p = fmax(p, fabs(v) / g_ceil[k]);
+                    }
+                    rr[D + n] = p > 1.0 ? 1.0 / p : 1.0;
+                }
             }
             __syncthreads();
             double keep_r[kLimLookaheadMax / 256], keep_e[kLimLookaheadMax / 256];
@@ -467,10 +517,19 @@ nupc_limit_emit_kernel(const T *__restrict__ ring, int R, int base, int D, int L
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) s_min = fmin(s_min, __shfl_down(s_min, off));
             if ((tid & 63) == 0) red_min[tid >> 6] = s_min;
+            if constexpr (TP) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) tp_max = fmax(tp_max, __shfl_down(tp_max, off));
+                if ((tid & 63) == 0) red_max[tid >> 6] = tp_max;
+            }
             __syncthreads();
             if (tid == 0) {
                 const double before = (meter_reset >> g) & 1u ? 1.0 : st_in[2 * D];
                 st_out[2 * D] = fmin(fmin(before, fmin(red_min[0], red_min[1])), fmin(red_min[2], red_min[3]));
+                if constexpr (TP) {
+                    const double seen = (tp.tp_reset >> g) & 1u ? 0.0 : st_in[2 * D + 1];
+                    st_out[2 * D + 1] = fmax(fmax(seen, fmax(red_max[0], red_max[1])), fmax(red_max[2], red_max[3]));
+                }
             }
         }
     }
@@ -700,20 +759,28 @@ int nupc_limit_emit(bfhip_nupc *n, unsigned long long opos, void *rawout_dev) {
         hipLaunchKernelGGL((nupc_limit_stage_kernel<T, SD>), dim3(n->n_out), dim3(256), SD ? nupc_sd_smem(n, 1) : 0, n->stream,
                            (T *)acc_old, (T *)acc_new, opos, n->A, n->n_out, L0, rel0, sw.sw_F, n->og.d, (T *)lm.d_ring, R,
                            base, nupc_sd_args<T>(n, 1));
-        auto back = [&](auto dith) {
-            constexpr bool DITHER = decltype(dith)::value;
-            hipLaunchKernelGGL((nupc_limit_emit_kernel<T, DITHER>), dim3(n->n_out), dim3(256), nupc_lim_lds(lm.D, tile),
-                               n->stream, (const T *)lm.d_ring, R, base, lm.D, L0, tile, lm.a, lm.d_groups, lm.d_group_of,
+        // the detector picks the instantiation, its LDS and its extra arguments; everything else is shared
+        auto back = [&](auto dith, auto det, size_t lds) {
+            constexpr bool DITHER = decltype(dith)::value, TP = decltype(det)::value;
+            NupcLimTp<TP> tp = {};
+            if constexpr (TP) { tp.taps = lm.taps; tp.tp_reset = lm.tp_reset; }
+            hipLaunchKernelGGL((nupc_limit_emit_kernel<T, DITHER, TP>), dim3(n->n_out), dim3(256), lds,
+                               n->stream, (const T *)lm.d_ring, R, base, lm.De(), L0, tile, lm.a, lm.d_groups, lm.d_group_of,
                                lm.d_state, (int)(n->block & 1), thr, lm.meter_reset, n->io.d_fmt[1], n->st.d_over,
                                (uint8_t *)rawout_dev, n->safety_limit, n->st.d_status, n->st.d_arrive, n->st.h_status,
                                n->dither.d_slot, (T *)n->dither.d_stage, (DitherState<T> *)n->dither.d_state,
                                n->dither.d_table, (int)n->dither.table.size(),
-                               DITHER ? (const T *)n->dither.d_randmap + 256 : nullptr);
+                               DITHER ? (const T *)n->dither.d_randmap + 256 : nullptr, tp);
         };
-        if (!n->dither.ch.empty()) back(std::true_type()); else back(std::false_type());
+        auto detector = [&](auto dith) {
+            if (lm.true_peak()) back(dith, std::true_type(), nupc_lim_tp_lds(lm.De(), tile));
+            else back(dith, std::false_type(), nupc_lim_lds(lm.D, tile));
+        };
+        if (!n->dither.ch.empty()) detector(std::true_type()); else detector(std::false_type());
     });
     NCHK(hipGetLastError());
     lm.meter_reset = 0;
+    lm.tp_reset = 0;
     return BFHIP_OK;
 }
 

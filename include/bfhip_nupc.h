@@ -761,6 +761,62 @@ int bfhip_nupc_get_limiter_reduction(bfhip_nupc *n, int group, double *min_gain)
    definition in code. */
 int bfhip_selftest_limiter_envelope(int lookahead_frames, double release_frames, long n, const double p[], double s_out[]);
 
+/* ---- true-peak detection for the limiter --------------------------------------------------------
+ * The detector above looks at the samples.  What a DAC's reconstruction filter, a sample-rate
+ * converter or a lossy codec makes of them can exceed every sample: a sine at fs/4, 45 degrees off
+ * the sampling instants, has samples of 0.7071 of its amplitude, a true peak 3 dB above its sample
+ * peak.  In true-peak mode the detector looks at the waveform between the samples as well, the way
+ * ITU-R BS.1770 and EBU R128 meter it (dBTP): oversample by four, take the peak over all phases.
+ *
+ * Interpolator.  Four phases per frame, H = BFHIP_NUPC_LIMIT_TP_HALF = 12, Kaiser window, beta = 8;
+ * phase 0 is the sample itself:
+ *     g_q[k]   = sinc(v) I0(beta sqrt(1 - (v / H)^2)) / I0(beta),   v = k - H + q / 4,   q = 1, 2, 3,   k = 0 .. 2 H - 1
+ *     u_c,0[t] = x~_c[t - H]
+ *     u_c,q[t] = sum over k = 0 .. 2 H - 1 of g_q[k] x~_c[t - k]      (float64 for both precisions, k ascending)
+ *     x~_c[t]  = x_c[t] if finite, else 0;   x~_c[t < 0] = 0
+ * u_c,q[t] estimates the waveform at time t - H + q / 4.  The taps are computed on the host in float64
+ * (I0 by its power series) and travel to the kernel as an argument.  Interpolation error, measured in
+ * float64 on sines at 13 phases: at most 8e-5 of the amplitude up to 0.35 fs, 1.4e-3 at 0.40 fs,
+ * 2.1e-2 at 0.42 fs, 0.18 at 0.45 fs.  The droop near Nyquist is that of any short interpolator
+ * (BS.1770's own has 12 taps per phase).  Because phase 0 is exact, the true-peak reading is never
+ * below the sample peak.
+ *
+ * Detector and envelope, with D = lookahead_frames and D_e = D - H:
+ *     p[t]   = max over c in g, q = 0 .. 3 of |u_c,q[t]| / ceil_c     (ceil_c as above: thr_g in force at the call that receives frame t)
+ *     r, m, e, s: the formulas above with D_e in place of D
+ *     y_c[t] = x_c[t - D] * (T) s[t]
+ * The detector's H frames of latency come out of the look-ahead: every output still leaves exactly D
+ * frames late and bfhip_nupc_limiter_delay() still returns D; channels in no group are untouched.
+ * s[t] <= r[t - D_e], and r[t - D_e] was formed from the waveform at times t - D .. t - D + 3/4: the
+ * gain on sample x[t - D] knows about the inter-sample peak behind it.
+ *   Sample ceiling.  |y_c[t]| <= ceil_c (1 + (D_e + 4) eps_T) as above, because phase 0 is the sample.
+ *   Idle exactness.  As above: no p above 1 in the window gives s == 1.0 and the bits of x_c[t - D].
+ *   True peak.  Measured with the same interpolator applied to y, the true peak of y is held exactly
+ *   wherever s is constant over the interpolator's span; while s moves the bound is approximate.  A
+ *   float64 model gave 1 + 4.4e-7 of the ceiling over a whole run of the fs/4 sine above and 1.0104
+ *   over 60 white-noise bursts: a measured property of the definition, not a guarantee.
+ * Sample-peak mode is the default and does not change: a convolver that never selects true-peak mode,
+ * or selects SAMPLE_PEAK, allocates, launches and computes exactly as before.  True-peak mode costs
+ * one more double of group state and 72 float64 multiply-adds per member and frame; DESIGN.md section 4.
+ */
+#define BFHIP_NUPC_LIMIT_SAMPLE_PEAK 0      /* default: today's detector, today's bits */
+#define BFHIP_NUPC_LIMIT_TRUE_PEAK   1
+#define BFHIP_NUPC_LIMIT_TP_HALF     12     /* H: the interpolator spans 2 H frames */
+/* before finalize, after enable_limiter (BFHIP_ESTATE).  Any other detector value: BFHIP_EINVAL.  TRUE_PEAK needs
+   lookahead_frames >= 2 H = 24: BFHIP_EINVAL, the message names the limit, and nothing changes. */
+int bfhip_nupc_set_limiter_detector(bfhip_nupc *n, int detector);
+int bfhip_nupc_get_limiter_detector(const bfhip_nupc *n);                    /* BFHIP_EINVAL on a NULL handle */
+/* true-peak mode only (BFHIP_ESTATE in sample-peak mode; BFHIP_EINVAL on a bad handle or group): the maximum of
+   |u_c,q[t]| * fmt_c.scale over the group's channels, all four phases and all frames detected since the previous
+   call for this group, as a fraction of full scale (0 if none), then reset; waits for the main stream like
+   bfhip_nupc_get_limiter_reduction: NOT for the audio thread */
+int bfhip_nupc_get_limiter_true_peak(bfhip_nupc *n, int group, double *max_peak);
+/* host only, no HIP call: the taps g_q[k] above, g_out[(q - 1) * 2 H + k] */
+int bfhip_selftest_truepeak_filter(double g_out[3 * 2 * BFHIP_NUPC_LIMIT_TP_HALF]);
+/* host only, no HIP call: tp_out[t] = max over q = 0 .. 3 of |u_q[t]| for one channel x[0..n), fresh history,
+   evaluated frame by frame.  For tests and as the definition in code. */
+int bfhip_selftest_truepeak(long n, const double x[], double tp_out[]);
+
 #ifdef __cplusplus
 }
 #endif

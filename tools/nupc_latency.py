@@ -11,7 +11,7 @@ uniform engine's block time and I/O delay for the same filters.
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
                                    | --eq-base [--eq-mode minimum] [--eq-taps R] | --eq-group [--eq-mode minimum] [--eq-taps R]]
-                                  [--biquads [--biquad-phase own|linear]] [--limiter [--lookahead D]]
+                                  [--biquads [--biquad-phase own|linear]] [--limiter [--lookahead D] [--true-peak]]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -45,7 +45,8 @@ output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs 
 --limiter enables the look-ahead peak limiter (bfhip_nupc_enable_limiter: look-ahead 64 frames or --lookahead, release
 4800 frames) with one group over both outputs at a threshold of 0.5; the first third of the run is 12x
 louder (output peaks near 1.0), so the group limits there and idles once the filters' tail has decayed; it
-reports the smallest gain the meter saw.
+reports the smallest gain the meter saw.  --true-peak (with --limiter) selects the true-peak detector
+(bfhip_nupc_set_limiter_detector) and also reports the true-peak meter's reading over the run.
 --dump-output writes the raw output of all timed
 and untimed periods to FILE (to compare two builds byte for byte).  --layout planar declares both
 sides as one non-interleaved device (a plane per channel, bfhip_nupc_set_buffer_bytes): the input
@@ -84,6 +85,7 @@ def main():
     ap.add_argument("--biquad-phase", choices=["own", "linear"], default="own")
     ap.add_argument("--limiter", action="store_true")
     ap.add_argument("--lookahead", type=int, default=64)
+    ap.add_argument("--true-peak", action="store_true")
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
@@ -137,6 +139,8 @@ def main():
             nu.reserve_eq_group(4)
     if a.limiter:
         nu.enable_limiter(a.lookahead, 4800.0)
+        if a.true_peak:
+            nu.set_limiter_detector(bf.LIMIT_TRUE_PEAK)
         nu.add_limiter_group([0, 1], 0.5)
     rng = np.random.default_rng(5)
     for o in range(2):
@@ -321,7 +325,8 @@ def main():
                                           for k in sync_taps} if a.eq else None,
                     "step_ms_rewrite_in_flight": dist(ts[fl]), "step_ms_no_rewrite": dist(ts[~fl])} if rewriting else None,
         "limiter": {"lookahead_frames": a.lookahead, "release_frames": 4800, "groups": [[0, 1]], "threshold": 0.5, "loud_periods": loud_until,
-                    "min_gain": round(nu.limiter_reduction(0), 4)} if a.limiter else None,
+                    "min_gain": round(nu.limiter_reduction(0), 4), "detector": "true_peak" if a.true_peak else "sample_peak",
+                    "true_peak": round(nu.limiter_true_peak(0), 4) if a.true_peak else None} if a.limiter else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},

@@ -10,9 +10,12 @@ gfx950 with -Rpass-analysis=kernel-resource-usage (device side only; no GPU need
 every kernel whose name starts with `nupc_`.  With --parent the same is done for another checkout and the two
 are put side by side; "same" says whether every figure of every kernel is equal.  With --eq-base the unit is
 brutefir_amd/csrc/nupc_update.hip and the kernels are those of eq_apply.h (the render onto a base), whose names
-start with `eq_apply_`; with --biquads the kernels are those of eq_biquad.h (the section render, `bq_`):
+start with `eq_apply_`; with --biquads the kernels are those of eq_biquad.h (the section render, `bq_`);
+with --limiter the unit stays nupc.hip and the kernels are the limiter's two (`nupc_limit_`), the true-peak
+instantiations of the limit kernel (third template argument true) beside the sample-peak ones:
 
-    python3 tools/nupc_resources.py --biquads > profiles/nupc_biquads_resources.json"""
+    python3 tools/nupc_resources.py --biquads > profiles/nupc_biquads_resources.json
+    python3 tools/nupc_resources.py --limiter [--parent OTHER_TREE] > profiles/nupc_truepeak_resources.json"""
 import json
 import os
 import re
@@ -52,7 +55,8 @@ def kernels(tree, unit="nupc.hip", prefix="nupc_"):
 
 def main(argv):
     unit, prefix = ("nupc_update.hip", "eq_apply_") if "--eq-base" in argv else \
-                   ("nupc_update.hip", "bq_") if "--biquads" in argv else ("nupc.hip", "nupc_")
+                   ("nupc_update.hip", "bq_") if "--biquads" in argv else \
+                   ("nupc.hip", "nupc_limit_") if "--limiter" in argv else ("nupc.hip", "nupc_")
     new = kernels(ROOT, unit, prefix)
     res = {"flags": "hipcc " + " ".join(FLAGS) + " brutefir_amd/csrc/" + unit, "columns": COLUMNS}
     if "--parent" in argv:
