@@ -6,6 +6,7 @@ package is the thin Python binding used by tests/ and bench.py: it mirrors the C
 one and adds nothing.  There is no CPU path: if the library or a HIP device is missing every
 call raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -40,6 +41,21 @@ class Overflow(C.Structure):
 
     def astuple(self):
         return (self.n_overflows, self.intlargest, self.largest, self.max)
+
+
+class LoudnessStruct(C.Structure):
+    """bfhip_loudness (include/bfhip_nupc.h)"""
+    _fields_ = [("momentary", C.c_double), ("short_term", C.c_double), ("integrated", C.c_double),
+                ("subblocks", C.c_longlong), ("first", C.c_longlong), ("wrapped", C.c_int)]
+
+
+# what Nupc.loudness and loudness_gate return: LUFS (-inf where undefined), complete sub-blocks since finalize, the
+# first sub-block the integrated value covers, and whether the history ring has dropped sub-blocks since the reset
+Loudness = collections.namedtuple("Loudness", "momentary short_term integrated subblocks first wrapped")
+
+
+def _loudness(s):
+    return Loudness(s.momentary, s.short_term, s.integrated, s.subblocks, s.first, bool(s.wrapped))
 
 
 class Format(C.Structure):
@@ -280,6 +296,14 @@ def lib():
     L.bfhip_nupc_get_limiter_true_peak.argtypes = [vp, ci, dp]
     L.bfhip_selftest_truepeak_filter.argtypes = [dp]
     L.bfhip_selftest_truepeak.argtypes = [C.c_long, dp, dp]
+    L.bfhip_nupc_enable_loudness.argtypes = [vp, ci, ci]
+    L.bfhip_nupc_add_loudness_group.argtypes = [vp, ip, dp, ci]
+    L.bfhip_nupc_get_loudness.argtypes = [vp, ci, C.POINTER(LoudnessStruct)]
+    L.bfhip_nupc_get_loudness_energy.argtypes = [vp, ci, C.c_longlong, ci, dp]
+    L.bfhip_nupc_reset_loudness.argtypes = [vp, ci]
+    L.bfhip_selftest_kweighting.argtypes = [ci, dp]
+    L.bfhip_selftest_loudness_energy.argtypes = [ci, C.c_long, dp, dp]
+    L.bfhip_selftest_loudness_gate.argtypes = [ci, C.c_long, dp, C.POINTER(LoudnessStruct)]
     L.bfhip_engine_set_overlap.argtypes = [vp, ci]
     _lib = L
     return L
@@ -1052,6 +1076,69 @@ class Nupc:
         v = C.c_double(0.0)
         self._chk(lib().bfhip_nupc_get_limiter_true_peak(self.h, group, C.byref(v)))
         return v.value
+
+
+    # BS.1770 loudness meter on the outputs (include/bfhip_nupc.h)
+    def enable_loudness(self, sample_rate, history_subblocks=36000):
+        """before finalize: sub-blocks of sample_rate / 10 frames, the last history_subblocks of them kept per
+        group (36 000: one hour)"""
+        self._chk(lib().bfhip_nupc_enable_loudness(self.h, sample_rate, history_subblocks))
+
+    def add_loudness_group(self, out_channels, weights=None):
+        """before finalize, after enable_loudness: the channels are metered as one programme with BS.1770's channel
+        weights G (None: all 1.0).  Returns the group index"""
+        chs = list(out_channels)
+        w = None if weights is None else _darr([float(v) for v in weights])
+        assert weights is None or len(weights) == len(chs)
+        return self._chk(lib().bfhip_nupc_add_loudness_group(self.h, _iarr(chs), w, len(chs)))
+
+    def loudness(self, group):
+        """momentary, short-term and gated integrated loudness of the group; waits for the main stream"""
+        s = LoudnessStruct()
+        self._chk(lib().bfhip_nupc_get_loudness(self.h, group, C.byref(s)))
+        return _loudness(s)
+
+    def loudness_energy(self, group, first, count):
+        """E[first .. first + count) of the group: complete sub-blocks that are still in the ring"""
+        e = np.zeros(max(count, 0), np.float64)
+        self._chk(lib().bfhip_nupc_get_loudness_energy(self.h, group, first, count, e.ctypes.data_as(C.POINTER(C.c_double))))
+        return e
+
+    def reset_loudness(self, group):
+        """the integrated value starts afresh with the next block call; no device work"""
+        self._chk(lib().bfhip_nupc_reset_loudness(self.h, group))
+
+
+def kweighting(sample_rate):
+    """the K-weighting sections at sample_rate (bfhip_selftest_kweighting: host only): shelf b0 b1 b2 a1 a2,
+    high-pass b0 b1 b2 a1 a2"""
+    c = np.zeros(10, np.float64)
+    r = lib().bfhip_selftest_kweighting(sample_rate, c.ctypes.data_as(C.POINTER(C.c_double)))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return c
+
+
+def loudness_energy(sample_rate, v):
+    """E[j] of the complete sub-blocks of one channel v (fractions of full scale), weight 1, fresh state
+    (bfhip_selftest_loudness_energy: host only, frame by frame)"""
+    v = np.ascontiguousarray(v, np.float64)
+    e = np.zeros(len(v) // max(sample_rate // 10, 1) + 1, np.float64)
+    dp = C.POINTER(C.c_double)
+    r = lib().bfhip_selftest_loudness_energy(sample_rate, len(v), v.ctypes.data_as(dp), e.ctypes.data_as(dp))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return e[:r]
+
+
+def loudness_gate(sample_rate, E):
+    """the read-outs of sub-block energies E[0..) (bfhip_selftest_loudness_gate: host only) -> Loudness"""
+    E = np.ascontiguousarray(E, np.float64)
+    s = LoudnessStruct()
+    r = lib().bfhip_selftest_loudness_gate(sample_rate, len(E), E.ctypes.data_as(C.POINTER(C.c_double)), C.byref(s))
+    if r < 0:
+        raise BfhipError("bfhip nupc error %d: %s" % (r, lib().bfhip_nupc_last_error().decode()))
+    return _loudness(s)
 
 
 def limiter_envelope(lookahead_frames, release_frames, p):

@@ -21,7 +21,7 @@ INC = os.path.join(HERE, "..", "include")
 PUBLIC = [os.path.join("..", "..", "include", h) for h in ("bfhip.h", "bfhip_convolver.h", "bfhip_nupc.h")]
 DEVICE = ["kernels.h", "fft_lds.h", "fft_wave.h", "bigfft.h"] + PUBLIC
 NUPC = DEVICE + ["nupc.h", "nupc_sched.h", "alloc.h", "eq_render.h", "eq_minphase.h", "eq_apply.h", "limiter_host.h",
-               "truepeak_host.h"]
+               "truepeak_host.h", "loudness_host.h"]
 # translation unit -> what it includes
 UNITS = {
     "bfhip.hip": DEVICE + ["engine.h", "channels.h", "passes.h", "conv_shared.h", "alloc.h", "coeff_async.h", "dither_init.h", "subdelay_filter.h"],
@@ -29,7 +29,7 @@ UNITS = {
     "plan.hip": DEVICE + ["engine.h", "channels.h", "alloc.h"],
     "channels.hip": DEVICE + ["engine.h", "channels.h", "alloc.h", "dither_init.h", "subdelay_filter.h"],
     "convolver_abi.hip": DEVICE + ["conv_shared.h"],
-    "nupc.hip": NUPC + ["nupc_kernels.h", "dither_init.h", "subdelay_filter.h"],
+    "nupc.hip": NUPC + ["nupc_kernels.h", "nupc_loudness.h", "dither_init.h", "subdelay_filter.h"],
     "nupc_update.hip": NUPC + ["coeff_async.h", "eq_biquad.h", "biquad_host.h"],
     "host_ops.cpp": ["host_fft.h", "conv_shared.h"] + PUBLIC,
 }

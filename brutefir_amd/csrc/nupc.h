@@ -18,6 +18,7 @@
 #include "eq_render.h"
 #include "kernels.h"
 #include "limiter_host.h"
+#include "loudness_host.h"
 #include "nupc_sched.h"
 #include "truepeak_host.h"
 
@@ -195,6 +196,32 @@ struct NupcLimiter {
     size_t state_stride() const { return (size_t)2 * De() + (true_peak() ? 2 : 1); }
 };
 
+// BS.1770 loudness meter on the emitted block (bfhip_nupc_enable_loudness).  Nothing of it exists in a convolver
+// that never enables it.  The filter states, the open sub-block's partial sum and the ring of sub-block energies
+// live on the device; the frame counter (block count x L0) and the reset points are the host's.
+struct NupcLoudGroup {                     // one row of the group table, host and device
+    int n_ch, pad;
+    int ch[kLoudGroupMax];
+    double weight[kLoudGroupMax];
+    double scale[kLoudGroupMax];           // the members' fmt.scale (filled at finalize)
+};
+// the sections' coefficients and, for the chunked scan, the powers M^(2^i) of the transition matrix M over one
+// chunk of zero input (kweighting_transition): a kernel argument
+struct NupcLoudCoef { double c[10]; double mp[8][16]; };
+struct NupcLoudness {
+    bool on = false;
+    int rate = 0, S = 0, history = 0;      // S = rate / 10 frames per sub-block
+    int chunk = 0;                         // frames per lane (fixed at finalize): L0 = one lane walks the period
+    std::vector<NupcLoudGroup> groups;
+    std::vector<long long> reset;          // per group: the first sub-block the integrated value covers
+    NupcLoudCoef coef = {};
+    NupcLoudGroup *d_groups = nullptr;
+    double *d_state = nullptr;             // [group][kLoudGroupMax][4]: shelf s1 s2, high-pass s1 s2 per member
+    double *d_open = nullptr;              // [group]: the open sub-block's partial sum
+    double *d_ring = nullptr;              // [group][history]: sub-block j in cell j mod history
+    std::vector<double> h_ring;            // the read-outs' copy of one group's ring (not on the audio path)
+};
+
 }  // namespace nupc_host
 
 using namespace nupc_host;
@@ -228,6 +255,7 @@ struct bfhip_nupc {
     NupcUpdate upd;
     NupcEq eq;
     NupcLimiter lim;
+    NupcLoudness loud;
 
     int L0() const { return seg[0].L; }
     long taps() const { return seg.back().off + (long)seg.back().L * seg.back().N; }

@@ -35,6 +35,7 @@
 
 #include "dither_init.h"
 #include "nupc_kernels.h"
+#include "nupc_loudness.h"
 #include "subdelay_filter.h"
 
 static thread_local std::string n_err;
@@ -148,7 +149,8 @@ void bfhip_nupc_destroy(bfhip_nupc *n) {
     void *p[] = {n->d_acc[0], n->d_acc[1], n->d_in, n->d_rawout, n->io.d_fmt[1], n->og.d, n->st.d_over, n->st.d_status,
                  n->st.d_arrive, n->dither.d_slot, n->dither.d_state, n->dither.d_table, n->dither.d_randmap,
                  n->dither.d_stage, n->sd.d_bank, n->sd.d_hist[0], n->sd.d_hist[1], n->io.d_fmt[0], n->d_in_real, n->d_stage,
-                 n->lim.d_ring, n->lim.d_group_of, n->lim.d_groups, n->lim.d_state};
+                 n->lim.d_ring, n->lim.d_group_of, n->lim.d_groups, n->lim.d_state,
+                 n->loud.d_groups, n->loud.d_state, n->loud.d_open, n->loud.d_ring};
     for (void *q : p) if (q) (void)hipFree(q);
     for (auto &side : n->dl) for (auto &d : side) if (d.arena) (void)hipFree(d.arena);
     void *h[] = {n->st.h_status, n->io.h_in, n->io.h_out, n->st.h_over, n->og.h};
@@ -562,6 +564,23 @@ int fin_limiter(bfhip_nupc *n) {
     return BFHIP_OK;
 }
 
+// the meter's group table, filter states, open partials and rings: only under bfhip_nupc_enable_loudness, behind
+// everything else.  The chunk length of the kernel's scan and the transition-matrix powers are fixed here.
+int fin_loudness(bfhip_nupc *n) {
+    NupcLoudness &ld = n->loud;
+    if (!ld.on || ld.groups.empty()) return BFHIP_OK;    // a meter without a group: nothing to launch
+    for (auto &g : ld.groups)
+        for (int k = 0; k < g.n_ch; k++) g.scale[k] = n->io.fmt[1][g.ch[k]].scale;
+    ld.chunk = n->L0() <= kLoudSerialMax ? n->L0() : kLoudChunk;
+    kweighting_transition(ld.coef.c, ld.chunk, ld.coef.mp[0]);
+    for (int i = 1; i < 8; i++) loudness_mat_mul(ld.coef.mp[i - 1], ld.coef.mp[i - 1], ld.coef.mp[i]);
+    STEP(dev_copy(&ld.d_groups, ld.groups));
+    STEP(dev_zeroed(&ld.d_state, ld.groups.size() * kLoudGroupMax * 4 * sizeof(double)));
+    STEP(dev_zeroed(&ld.d_open, ld.groups.size() * sizeof(double)));
+    STEP(dev_zeroed(&ld.d_ring, ld.groups.size() * (size_t)ld.history * sizeof(double)));
+    return BFHIP_OK;
+}
+
 int finalize_impl(bfhip_nupc *n) {
     OWNER(n);
     STEP(fin_subdelay_sides(n));
@@ -581,6 +600,7 @@ int finalize_impl(bfhip_nupc *n) {
     STEP(fin_segments(n, prio_least));
     STEP(upd_finalize(n, prio_least));
     STEP(fin_limiter(n));
+    STEP(fin_loudness(n));
     n->finalized = true;
     return BFHIP_OK;
 }
@@ -665,6 +685,8 @@ int bfhip_nupc_block_dev(bfhip_nupc *n, const void *rawin_dev, void *rawout_dev)
     else STEP(nupc_emit(n, opos, rawout_dev));
     n->og.mirror.advance(L0);
     STEP(nupc_delay_side(n, BFHIP_OUT, (uint8_t *)rawout_dev));
+    // ---- the loudness meter reads what leaves
+    if (n->loud.d_groups) STEP(nupc_loudness(n, opos, rawout_dev));
     n->block++;
     sched.end_period(end);
     return BFHIP_OK;
@@ -1022,6 +1044,134 @@ int bfhip_selftest_truepeak(long n, const double x[], double tp_out[]) {
 int bfhip_selftest_limiter_envelope(int lookahead_frames, double release_frames, long n, const double p[], double s_out[]) {
     if (!limiter_envelope(lookahead_frames, release_frames, n, p, s_out))
         return nfail(BFHIP_EINVAL, "selftest_limiter_envelope: bad argument");
+    return BFHIP_OK;
+}
+
+// ---- BS.1770 loudness meter (checks, design, definition and read-outs: loudness_host.h) ------
+
+static_assert(sizeof(bfhip_loudness) == sizeof(LoudnessReadout), "bfhip_loudness is LoudnessReadout");
+static_assert(BFHIP_NUPC_LOUD_GROUPS_MAX == kLoudGroupsMax && BFHIP_NUPC_LOUD_GROUP_MAX == kLoudGroupMax, "loudness limits");
+
+int bfhip_nupc_enable_loudness(bfhip_nupc *n, int sample_rate, int history_subblocks) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_enable_loudness after finalize");
+    if (n->loud.on) return nfail(BFHIP_ESTATE, "nupc_enable_loudness: the meter is enabled already");
+    std::string why;
+    if (!loudness_check(sample_rate, history_subblocks, &why)) return nfail(BFHIP_EINVAL, "nupc_enable_loudness: " + why);
+    n->loud.on = true;
+    n->loud.rate = sample_rate;
+    n->loud.S = sample_rate / 10;
+    n->loud.history = history_subblocks;
+    kweighting_design(sample_rate, n->loud.coef.c);
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_add_loudness_group(bfhip_nupc *n, const int out_channels[], const double weight[], int n_ch) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (n->finalized) return nfail(BFHIP_ESTATE, "nupc_add_loudness_group after finalize");
+    if (!n->loud.on) return nfail(BFHIP_ESTATE, "nupc_add_loudness_group: needs bfhip_nupc_enable_loudness first");
+    std::string why;
+    if (!loudness_check_group(n->n_out, (int)n->loud.groups.size(), out_channels, weight, n_ch, &why))
+        return nfail(BFHIP_EINVAL, "nupc_add_loudness_group: " + why);
+    NupcLoudGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n_ch = n_ch;
+    for (int k = 0; k < n_ch; k++) { g.ch[k] = out_channels[k]; g.weight[k] = weight ? weight[k] : 1.0; g.scale[k] = 1.0; }
+    n->loud.groups.push_back(g);
+    n->loud.reset.push_back(0);
+    return (int)n->loud.groups.size() - 1;
+}
+
+}  // extern "C"
+
+namespace {
+
+// what the three calls below share: the handle, the meter, the group
+int loud_group_ok(const bfhip_nupc *n, int group, const char *who) {
+    if (!n) return nfail(BFHIP_EINVAL, "null");
+    if (!n->loud.on) return nfail(BFHIP_ESTATE, std::string(who) + ": needs bfhip_nupc_enable_loudness before finalize");
+    if (group < 0 || group >= (int)n->loud.groups.size()) return nfail(BFHIP_EINVAL, std::string(who) + ": bad group");
+    return BFHIP_OK;
+}
+
+// waits for the main stream and downloads cells [lo, hi) of the group's ring, sub-block j into h_ring[j mod history]
+int loud_download(bfhip_nupc *n, int group, long long lo, long long hi) {
+    NupcLoudness &ld = n->loud;
+    NCHK(hipSetDevice(n->device));
+    NCHK(hipStreamSynchronize(n->stream));
+    ld.h_ring.resize((size_t)ld.history);
+    const double *ring = ld.d_ring + (size_t)group * ld.history;
+    const long long H = ld.history, a = lo % H, cnt = hi - lo;
+    const long long first = std::min(cnt, H - a);
+    if (first > 0) NCHK(hipMemcpy(ld.h_ring.data() + a, ring + a, (size_t)first * sizeof(double), hipMemcpyDeviceToHost));
+    if (cnt > first) NCHK(hipMemcpy(ld.h_ring.data(), ring, (size_t)(cnt - first) * sizeof(double), hipMemcpyDeviceToHost));
+    return BFHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bfhip_nupc_get_loudness(bfhip_nupc *n, int group, bfhip_loudness *out) {
+    STEP(loud_group_ok(n, group, "nupc_get_loudness"));
+    if (!out) return nfail(BFHIP_EINVAL, "nupc_get_loudness: bad argument");
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_get_loudness before finalize");
+    OWNER(n);
+    NupcLoudness &ld = n->loud;
+    const long long done = (long long)(n->block * (unsigned long long)n->L0() / (unsigned long long)ld.S);
+    STEP(loud_download(n, group, std::max(0LL, done - ld.history), done));
+    LoudnessReadout r;
+    loudness_readout(ld.rate, done, ld.history, ld.reset[group],
+                     [&](long long j) { return ld.h_ring[(size_t)(j % ld.history)]; }, &r);
+    memcpy(out, &r, sizeof(r));
+    return BFHIP_OK;
+}
+
+int bfhip_nupc_get_loudness_energy(bfhip_nupc *n, int group, long long first, int count, double E_out[]) {
+    STEP(loud_group_ok(n, group, "nupc_get_loudness_energy"));
+    if (!n->finalized) return nfail(BFHIP_ESTATE, "nupc_get_loudness_energy before finalize");
+    NupcLoudness &ld = n->loud;
+    const long long done = (long long)(n->block * (unsigned long long)n->L0() / (unsigned long long)ld.S);
+    if (first < 0 || count < 0 || (count > 0 && !E_out)) return nfail(BFHIP_EINVAL, "nupc_get_loudness_energy: bad argument");
+    if (first + count > done)
+        return nfail(BFHIP_EINVAL, "nupc_get_loudness_energy: sub-block " + std::to_string(first + count - 1) + " is not complete yet (" +
+                     std::to_string(done) + " are)");
+    if (first < done - ld.history)
+        return nfail(BFHIP_EINVAL, "nupc_get_loudness_energy: sub-block " + std::to_string(first) + " has left the history ring of " +
+                     std::to_string(ld.history));
+    if (count == 0) return BFHIP_OK;
+    OWNER(n);
+    STEP(loud_download(n, group, first, first + count));
+    for (int i = 0; i < count; i++) E_out[i] = ld.h_ring[(size_t)((first + i) % ld.history)];
+    return BFHIP_OK;
+}
+
+// host bookkeeping only: the first sub-block whose first frame is at or behind the next block call's
+int bfhip_nupc_reset_loudness(bfhip_nupc *n, int group) {
+    STEP(loud_group_ok(n, group, "nupc_reset_loudness"));
+    const unsigned long long frames = n->block * (unsigned long long)n->L0(), S = (unsigned long long)n->loud.S;
+    n->loud.reset[group] = (long long)((frames + S - 1) / S);
+    return BFHIP_OK;
+}
+
+int bfhip_selftest_kweighting(int sample_rate, double coef_out[10]) {
+    std::string why;
+    if (!coef_out) return nfail(BFHIP_EINVAL, "selftest_kweighting: bad argument");
+    if (!loudness_rate_ok(sample_rate, &why)) return nfail(BFHIP_EINVAL, "selftest_kweighting: " + why);
+    kweighting_design(sample_rate, coef_out);
+    return BFHIP_OK;
+}
+
+int bfhip_selftest_loudness_energy(int sample_rate, long n, const double v[], double E_out[]) {
+    const long r = loudness_energy(sample_rate, n, v, E_out);
+    if (r < 0) return nfail(BFHIP_EINVAL, "selftest_loudness_energy: bad argument");
+    return (int)r;
+}
+
+int bfhip_selftest_loudness_gate(int sample_rate, long n_sub, const double E[], bfhip_loudness *out) {
+    LoudnessReadout r;
+    if (!loudness_gate(sample_rate, n_sub, E, out ? &r : nullptr)) return nfail(BFHIP_EINVAL, "selftest_loudness_gate: bad argument");
+    memcpy(out, &r, sizeof(r));
     return BFHIP_OK;
 }
 

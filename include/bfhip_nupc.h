@@ -817,6 +817,92 @@ int bfhip_selftest_truepeak_filter(double g_out[3 * 2 * BFHIP_NUPC_LIMIT_TP_HALF
    evaluated frame by frame.  For tests and as the definition in code. */
 int bfhip_selftest_truepeak(long n, const double x[], double tp_out[]);
 
+/* ---- BS.1770 loudness meter on the outputs ------------------------------------------------------
+ *
+ * The limiter and its true-peak detector say how high the programme may reach; this meter says how loud
+ * it is (ITU-R BS.1770-4 / EBU R128: LUFS), per group of output channels, on the device, once per period,
+ * with no host wait, upload or allocation on the audio path.  An extension: the reference's only level
+ * read-out is the peak field of struct bfoverflow.
+ *
+ * Tap.  The meter reads the raw output block of the period after everything: the block rawout_dev holds
+ * when bfhip_nupc_block_dev returns it -- behind the limiter, dither, quantisation with clipping, the integer
+ * delay line and mute.  For output channel c, frame t:
+ *     v_c[t] = (double) load_raw<double>(sample of channel c, frame t) * (double) fmt_c.scale     (fraction of full scale)
+ *     v_c[t] = 0 where that value is not finite (float formats)
+ * The sample's address comes from the channel's own byte_offset, sample_spacing and bytes, as the emit
+ * step uses them, so every layout bfhip_nupc_set_format / bfhip_nupc_set_buffer_bytes can declare is
+ * metered, in all 13 formats; and a float64 model of the meter needs only the bytes the convolver returned.
+ *
+ * K-weighting.  Two second-order sections per (group, member), float64 for both precisions, state zero at
+ * finalize and kept across periods; the shelf first, then the high-pass, each in transposed direct form II:
+ *     o = b0 v + s1;   s1 = b1 v - a1 o + s2;   s2 = b2 v - a2 o
+ * The coefficients are for any rate, by the bilinear redesign of the BS.1770 prototype.  K = tan(pi f0 / fs):
+ *     shelf:      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *                 Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2
+ *                 b0 = (Vh + Vb K/Q + K^2)/a0   b1 = 2 (K^2 - Vh)/a0   b2 = (Vh - Vb K/Q + K^2)/a0
+ *                 a1 = 2 (K^2 - 1)/a0           a2 = (1 - K/Q + K^2)/a0
+ *     high-pass:  f0 = 38.13547087602444, Q = 0.5003270373238773, a0 = 1 + K/Q + K^2
+ *                 b = (1, -2, 1)                a1 = 2 (K^2 - 1)/a0    a2 = (1 - K/Q + K^2)/a0
+ * At fs = 48000 these reproduce the table of BS.1770-4 to all 14 printed digits.  Call the output z_c[t].
+ *
+ * Sub-blocks.  S = sample_rate / 10 frames (100 ms).  Sub-block j covers frames [j S, (j + 1) S), frames
+ * counted from finalize as in the switch section; its boundaries bear no relation to L0.  For group g with
+ * members c and weights G_c:
+ *     E_g[j] = sum over c of G_c * (sum over t in sub-block j of z_c[t]^2)
+ * The device keeps the last history_subblocks values of E_g in a ring (cell j mod history_subblocks) and
+ * the partial sum of the open sub-block.  Two runs of the same input give the same bits of E: no
+ * floating-point atomics, every sum in a fixed order.
+ *
+ * Read-outs, formed on the host from the ring, with l(m) = -0.691 + 10 log10(m), l(0) = -INFINITY, and J
+ * the last complete sub-block:
+ *     momentary   = l((E[J-3] + ... + E[J]) / (4 S))        needs 4 complete sub-blocks, else -INFINITY
+ *     short_term  = l((E[J-29] + ... + E[J]) / (30 S))      needs 30, else -INFINITY
+ *     gating blocks  B_j = (E[j-3] + ... + E[j]) / (4 S)  for every j with j - 3 >= first, where first is the
+ *                    later of the reset point and J - history_subblocks + 1 (400 ms blocks, 75 % overlap)
+ *     integrated  = l(mean of the B_j with l(B_j) > -70 and l(B_j) > l(mean of the B_j with l(B_j) > -70) - 10)
+ *                   -INFINITY if no block passes
+ * Loudness range (EBU Tech 3342) is not computed; bfhip_nupc_get_loudness_energy hands a host what it needs.
+ *
+ * Costs.  One more launch per period, one workgroup per group; per (group, member) four doubles of state, per
+ * group 8 bytes per sub-block of history (one hour: 36 000 sub-blocks, 288 kB).  A convolver that never enables
+ * the meter allocates, launches and computes exactly as before.  DESIGN.md section 4.
+ */
+#define BFHIP_NUPC_LOUD_GROUPS_MAX 32
+#define BFHIP_NUPC_LOUD_GROUP_MAX  16      /* channels per group: 7.1.4 without its LFE is 11 */
+typedef struct {
+    double momentary, short_term, integrated;   /* LUFS; -INFINITY where undefined */
+    long long subblocks;                        /* complete sub-blocks since finalize (J + 1) */
+    long long first;                            /* first sub-block the integrated value covers */
+    int wrapped;                                /* 1: the history ring has dropped sub-blocks since the reset */
+} bfhip_loudness;
+
+/* before finalize (after: BFHIP_ESTATE; twice: BFHIP_ESTATE).  sample_rate: a multiple of 10 in 8000 .. 768000 (the
+   shelf needs fs well above 2 x 1682 Hz); history_subblocks: 30 .. 2^22.  Anything else: BFHIP_EINVAL, the message
+   names the limit. */
+int bfhip_nupc_enable_loudness(bfhip_nupc *n, int sample_rate, int history_subblocks);
+/* before finalize, after enable_loudness (BFHIP_ESTATE).  1 <= n_ch <= ..._GROUP_MAX, channels in range and pairwise
+   distinct within the group, weights finite and >= 0 (weight == NULL: all 1.0).  A channel may be in several groups
+   (a stereo pair and the whole programme): each (group, member) filters for itself.  Returns the group index. */
+int bfhip_nupc_add_loudness_group(bfhip_nupc *n, const int out_channels[], const double weight[], int n_ch);
+/* after finalize: wait for the main stream like bfhip_nupc_get_limiter_reduction (NOT for the audio thread), download
+   the group's ring and do the rest on the host.  get_loudness_energy copies sub-blocks [first, first + count):
+   BFHIP_EINVAL if any of them is not complete yet or has left the ring. */
+int bfhip_nupc_get_loudness(bfhip_nupc *n, int group, bfhip_loudness *out);
+int bfhip_nupc_get_loudness_energy(bfhip_nupc *n, int group, long long first, int count, double E_out[]);
+/* host bookkeeping only, no device work, no wait: the integrated value from now on covers the complete sub-blocks
+   whose first frame is at or behind the frame of the next block call.  Filter state, ring, momentary and short_term
+   are untouched. */
+int bfhip_nupc_reset_loudness(bfhip_nupc *n, int group);
+/* On a convolver that never enabled the meter the five calls above return BFHIP_ESTATE; BFHIP_EINVAL on a NULL handle
+   or a bad group. */
+/* host only, no HIP call: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 */
+int bfhip_selftest_kweighting(int sample_rate, double coef_out[10]);
+/* host only, one channel, weight 1, fresh state, frame by frame: E_out takes the n / S complete sub-blocks of
+   v[0..n); returns their number */
+int bfhip_selftest_loudness_energy(int sample_rate, long n, const double v[], double E_out[]);
+/* host only: the read-outs of E[0..n_sub), sub-blocks 0 on, nothing dropped, no reset */
+int bfhip_selftest_loudness_gate(int sample_rate, long n_sub, const double E[], bfhip_loudness *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ uniform engine's block time and I/O delay for the same filters.
     python3 tools/nupc_latency.py [L0 [steps]] [--out-format S24_4LE] [--dither] [--delay] [--subdelay]
                                   [--gain-ramp] [--rewrite | --rewrite-sync | --eq [--eq-mode minimum] [--eq-taps R]
                                    | --eq-base [--eq-mode minimum] [--eq-taps R] | --eq-group [--eq-mode minimum] [--eq-taps R]]
-                                  [--biquads [--biquad-phase own|linear]] [--limiter [--lookahead D] [--true-peak]]
+                                  [--biquads [--biquad-phase own|linear]] [--limiter [--lookahead D] [--true-peak]] [--loudness]
                                   [--dump-output FILE] [--layout {interleaved,planar}]
 
 --out-format sets the output sample format (default FLOAT64_LE); --dither enables HP-TPDF dither
@@ -47,6 +47,9 @@ output gain ramp of 5 periods (bfhip_nupc_set_gain_ramp) and gives both outputs 
 louder (output peaks near 1.0), so the group limits there and idles once the filters' tail has decayed; it
 reports the smallest gain the meter saw.  --true-peak (with --limiter) selects the true-peak detector
 (bfhip_nupc_set_limiter_detector) and also reports the true-peak meter's reading over the run.
+--loudness enables the BS.1770 loudness meter (bfhip_nupc_enable_loudness: 48 kHz, one hour of history) with one
+stereo group on outputs 0, 1 -- one more launch per period -- and reports its three read-outs at the end of the run;
+the limiter flags stay usable beside it.
 --dump-output writes the raw output of all timed
 and untimed periods to FILE (to compare two builds byte for byte).  --layout planar declares both
 sides as one non-interleaved device (a plane per channel, bfhip_nupc_set_buffer_bytes): the input
@@ -86,6 +89,7 @@ def main():
     ap.add_argument("--limiter", action="store_true")
     ap.add_argument("--lookahead", type=int, default=64)
     ap.add_argument("--true-peak", action="store_true")
+    ap.add_argument("--loudness", action="store_true")
     ap.add_argument("--dump-output")
     ap.add_argument("--layout", choices=["interleaved", "planar"], default="interleaved")
     a = ap.parse_args()
@@ -142,6 +146,9 @@ def main():
         if a.true_peak:
             nu.set_limiter_detector(bf.LIMIT_TRUE_PEAK)
         nu.add_limiter_group([0, 1], 0.5)
+    if a.loudness:
+        nu.enable_loudness(48000, 36000)
+        nu.add_loudness_group([0, 1])
     rng = np.random.default_rng(5)
     for o in range(2):
         for i in range(2):
@@ -296,6 +303,12 @@ def main():
     fl = np.array(in_flight[256:], bool)
     rp = np.array(ramping[256:], bool)
 
+    def loudness_report(nu):
+        r = nu.loudness(0)
+        lufs = lambda v: round(v, 3) if np.isfinite(v) else None
+        return {"sample_rate": 48000, "history_subblocks": 36000, "groups": [[0, 1]], "momentary_lufs": lufs(r.momentary),
+                "short_term_lufs": lufs(r.short_term), "integrated_lufs": lufs(r.integrated), "subblocks": r.subblocks}
+
     def dist(v):
         v = np.asarray(v, float)
         if len(v) == 0:
@@ -327,6 +340,7 @@ def main():
         "limiter": {"lookahead_frames": a.lookahead, "release_frames": 4800, "groups": [[0, 1]], "threshold": 0.5, "loud_periods": loud_until,
                     "min_gain": round(nu.limiter_reduction(0), 4), "detector": "true_peak" if a.true_peak else "sample_peak",
                     "true_peak": round(nu.limiter_true_peak(0), 4) if a.true_peak else None} if a.limiter else None,
+        "loudness": loudness_report(nu) if a.loudness else None,
         "io_delay_frames": L0, "period_ms_at_48k": L0 / 48.0,
         "step_ms": {"median": round(float(np.median(ts)), 4), "p99": round(float(np.percentile(ts, 99)), 4),
                     "p99.9": round(float(np.percentile(ts, 99.9)), 4), "max": round(float(ts.max()), 4)},
